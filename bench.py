@@ -11,9 +11,15 @@ the default since the round-4 root cause) and measured no faster.
 per-crop pose records are all-gathered over RCCL after every step.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 64] [--size 120] [--points 1000]
+                    [--dump-outputs DIR] [--full]
 
-Rank 0 prints ONE JSON line (metric, value = crops/s over all ranks, roofline of the dominant
-kernel measured with HIP events, cpu_baseline = the CPU oracle on a bounded sample).
+Rank 0 prints ONE JSON line (metric, value = crops/s over all ranks, ms_per_step = the wall time
+of one of the K timed steps). A plain run does only that: set up, warm up, time the steps.
+--dump-outputs DIR then writes what the last timed step computed (DIR/<name>.npy; the inputs are
+seeded, so the same arguments give the same step on every run). --full adds the legs that take
+runs of their own after the timed loop: the roofline of the dominant kernel measured with HIP
+events (--no-profile leaves it out) and the CPU leg (cpu_baseline = the CPU oracle on a bounded
+sample, and the ADD(-S) accuracy check against it; --no-cpu leaves it out).
 """
 from __future__ import annotations
 
@@ -381,6 +387,8 @@ def bench_config3(args, rank: int, world: int, local: int):
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         el = float(tt.item())
     ms = el / args.steps * 1e3
+    if rank == 0 and args.dump_outputs and pipes:
+        dump_outputs(args.dump_outputs, step_outputs(pipes))
     if rank == 0:
         line = {
             "metric": METRIC, "value": round(args.global_batch * args.steps / el, 2), "unit": "crops/s",
@@ -403,6 +411,42 @@ def bench_config3(args, rank: int, world: int, local: int):
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.destroy_process_group()
+
+
+DUMP_BYTES = 60 * 2 ** 20  # --dump-outputs writes at most this much in all
+
+
+def step_outputs(pipes):
+    """What a caller of the timed step receives, of the step that ran last: results() of every
+    pipeline (R, t, pred_t, inliers; config 3: this rank's buckets concatenated in the order it
+    runs them) and, for the default one-graph step, the dense model coordinates `xyz` the pose is
+    computed from."""
+    res = [pl.results() for pl in pipes]
+    out = {k: torch.cat([r[k] for r in res]) for k in res[0]}
+    if len(pipes) == 1 and isinstance(pipes[0], BatchPipeline):
+        out["xyz"] = torch.cat([pt.kp.xyz for pt in pipes[0].parts])
+    return out
+
+
+def dump_outputs(dirname: str, outputs):
+    """DIR/<name>.npy per output, float32 (float64 stays float64). When the outputs together
+    exceed DUMP_BYTES, every array above its even share of the budget is written as a fixed
+    sample instead: the flat elements at sorted indices drawn without replacement by
+    numpy default_rng(0), which depend only on the array's size."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    arrs = {}
+    for k, v in outputs.items():
+        a = v.detach().cpu().numpy()
+        arrs[k] = np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+    if sum(a.nbytes for a in arrs.values()) > DUMP_BYTES:
+        share = DUMP_BYTES // len(arrs)
+        for k, a in arrs.items():
+            if a.nbytes > share:
+                idx = np.sort(np.random.default_rng(0).choice(a.size, size=share // a.itemsize, replace=False))
+                arrs[k] = a.reshape(-1)[idx]
+    for k, a in arrs.items():
+        np.save(os.path.join(dirname, f"{k}.npy"), a)
 
 
 def launch_ranks(n: int) -> int:
@@ -449,8 +493,15 @@ def main():
                     help="NUM_CLS (1 = LineMOD 'cat' config 2; 13 = LineMOD all; 5 = the ClearGrasp-sized head)")
     ap.add_argument("--frame", default="480x640", help="source frame HxW (config 5: 960x1280)")
     ap.add_argument("--no-graph", action="store_true")
-    ap.add_argument("--no-profile", action="store_true")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU leg (baseline + accuracy)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the legs that take runs of their own: the per-kernel "
+                         "profile / roofline and the CPU leg (config 2; a plain run has roofline, cpu_baseline and "
+                         "accuracy null)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write what the last one computed (R, t, pred_t, inliers, xyz) as "
+                         "DIR/<name>.npy")
+    ap.add_argument("--no-profile", action="store_true", help="with --full: skip the per-kernel profile / roofline")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU leg (baseline + accuracy)")
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="torch threads of the CPU leg (0 = the CPUs this process may use: cgroup quota / affinity)")
     ap.add_argument("--cpu-reps", type=int, default=10, help="timed B=64 CPU batches (BASELINE.md §2 protocol: 10)")
@@ -474,6 +525,12 @@ def main():
                          "the two-stage pipeline (pipeline.PipelinedPipeline) split there, its stages side by side on two "
                          "streams (KRRN_STREAMS=1; measured no faster than one graph)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and args.dry_run:
+        ap.error("--dump-outputs needs a real run: a --dry-run step computes nothing")
+    if args.breakdown and (not args.full or args.no_profile):
+        ap.error("--breakdown needs the per-kernel profile: pass --full (without --no-profile)")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(launch_ranks(args.gpus))
@@ -540,9 +597,13 @@ def main():
     ms = el / args.steps * 1e3
     value = world * B * args.steps / el
 
+    # the outputs of the last timed step, before anything below runs the step again
+    if rank == 0 and step is not None and args.dump_outputs:
+        dump_outputs(args.dump_outputs, step_outputs([step]))
+
     roof, breakdown = None, None
     extra = {}
-    if rank == 0 and step is not None and not args.no_profile:
+    if args.full and rank == 0 and step is not None and not args.no_profile:
         step.profile()  # warm the eager path once
         prof = step.profile()
         roof, breakdown = roofline_from_profile(prof, B)
@@ -558,7 +619,7 @@ def main():
             with open(args.breakdown, "w") as f:
                 json.dump({"roofline": roof, "kernels": breakdown}, f, indent=1)
     cpu, acc = None, None
-    if rank == 0 and world == 1 and step is not None and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and step is not None and not args.no_cpu:
         acc = cpu_leg_accuracy(dev)
         threads = args.cpu_threads or cpu_quota()
         cpu = cpu_baseline(S, N, threads, args.cpu_reps, args.cpu_warmup)

@@ -1,10 +1,10 @@
-"""Summarise a rocprofv3 --kernel-trace CSV of bench.py into per-kernel device time per step.
+"""Summarise a rocprofv3 --kernel-trace CSV of bench.py --full into per-kernel device time per step.
 
-bench.py runs (in order) an eager warm-up pass, a serial per-op profile pass (every launch on
-one stream), then the graph warm-up / timed replays (several streams, kernels overlap, so their
-rocprof durations include contention). This script finds the serial pass (the longest window
-of libkrrn_hip kernels with no overlap) and reports each kernel's isolated duration there, plus the
-wall-clock of each graph replay window.
+bench.py --full runs an eager warm-up pass, the graph warm-up / timed replays (several streams,
+kernels overlap, so their rocprof durations include contention) and a serial per-op profile pass
+(every launch on one stream; a plain run without --full has none). This script finds the serial
+pass (the longest window of libkrrn_hip kernels with no overlap) and reports each kernel's
+isolated duration there, plus the wall-clock of each graph replay window.
 
 usage: python profiles/kernel_trace_summary.py <run_kernel_trace.csv> [out.json]
 """
