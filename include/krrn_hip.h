@@ -344,6 +344,31 @@ int krrn_pnp_ransac_f32(const float* xyz, int HW, const long long* choose, int N
                         const double* lfborder, const int* subsets, int H, float thr, double conf, float* workspace,
                         float* R, float* t, int* inliers, unsigned char* inlier_mask, int B, void* stream);
 
+/* Model points of the chosen pixels (tools/script/eval.py:128's coordinate_choosed_all, de-normalised
+ * as trainer.py:415-421 does): out[b][i] = float(xyz[b][:, choose[b][i]] * extent[b] + lfborder[b]),
+ * f64 math then f32 -- the same expression krrn_pnp_ransac_f32 uses for its object points.
+ * xyz [B][3][HW], choose int64 [B][N] (a pixel outside [0, HW) gives NaN), out [B][N][3]. */
+int krrn_model_points_f32(const float* xyz, int HW, const long long* choose, int N, const double* extent,
+                          const double* lfborder, float* out, int B, void* stream);
+
+/* estimateSimilarityTransform (lib/transform/umeyama.py:8-98), batched: RANSAC over 5-point Umeyama
+ * fits of dst ~ s R src + t, then a refit on the inliers of the best one. src / dst f32 [B][N][3]
+ * (5 <= N <= 4096); subsets int32 [B][H][5] (indices in [0, N), duplicates allowed; H <= 8192);
+ * hyp_counts int32 [B][H] (workspace and diagnostic: every hypothesis's inlier count); outputs
+ * scale [B], R [B][9] row-major, t [B][3], inliers [B] (0 = failed -> scale 1, R = I, t = 0),
+ * best_hyp [B] (optional, -1 on failure), inlier_mask uint8 [B][N] (optional).
+ * All arithmetic in f64. Threshold s_h * inlier_frac * 2 * max_i |src_i - mean(src)| (:16-20, the
+ * reference's inlier_frac is 0.1), strict <; a hypothesis whose scale is not finite and positive
+ * counts 0. Selection: the reference's loop over the hypotheses in order on the counts scored in
+ * parallel (:31-49): a strictly larger count becomes the best, and the loop stops after iteration i
+ * (zero-based) once 1 - (1 - best_ratio^5)^i > conf (0.99 there); best_ratio < min_ratio (0.1) is
+ * the reference's None (:50-52). Two launches: scoring (16 hypotheses per wave, one lane each),
+ * then one block per crop for the selection and the refit (fixed-order sums, no atomics). */
+int krrn_umeyama_ransac_f32(const float* src, const float* dst, int N, const int* subsets, int H,
+                            double inlier_frac, double conf, double min_ratio, int* hyp_counts,
+                            float* scale, float* R, float* t, int* inliers, int* best_hyp,
+                            unsigned char* inlier_mask, int B, void* stream);
+
 /* torch.randperm(n)[:k] per row (gcn3d.py:239, trainer.py:407) from a counter-based generator
  * seeded by *seed_ptr (device memory) and `stream_id`; n <= 4096. out int32 [rows][k]. */
 int krrn_randperm_i32(const unsigned long long* seed_ptr, unsigned int stream_id, int n, int k, int rows, int* out,

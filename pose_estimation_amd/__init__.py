@@ -5,6 +5,8 @@ arithmetic step in the gfx950 HIP library libkrrn_hip.so (include/krrn_hip.h).
 Drop-in API (the reference's names):
     KRRN(num_cls, cfg)                    lib/network/krrn.py
     get_pose(pred, data)                  tools/trainer.py:383-438 (Trainer.get_pose)
+    estimateSimilarityTransform(src, dst) lib/transform/umeyama.py:8-98 (Umeyama-RANSAC, batched)
+    get_pose_umeyama(pred, data)          tools/script/eval.py:128,151 (the depth-based pose)
     PoseDataset / make_batch              dataset/linemod/batchdataset.py (synthetic frames)
     Metric                                lib/utils/metric.py
     KRRNLoss                              lib/network/loss.py (eval-time terms)
@@ -17,6 +19,8 @@ from .config import CONFIG, Cfg, make_config  # noqa: F401
 from .krrn import KRRN  # noqa: F401
 from . import bpnp, dataset, fps  # noqa: F401  (register their C-ABI signatures)
 from .loss import KRRNLoss  # noqa: F401
-from .pose import get_pose  # noqa: F401
+from .pose import add_umeyama_ops, get_pose, get_pose_umeyama  # noqa: F401
+from .umeyama import estimateSimilarityTransform  # noqa: F401
 
-__all__ = ["KRRN", "KRRNLoss", "get_pose", "make_config", "CONFIG", "Cfg"]
+__all__ = ["KRRN", "KRRNLoss", "get_pose", "get_pose_umeyama", "add_umeyama_ops", "estimateSimilarityTransform",
+           "make_config", "CONFIG", "Cfg"]

@@ -34,7 +34,7 @@ from .dataset import PoseDataset
 from .krrn import KRRN
 from .loss import map_losses
 from .metric import Metric, add_metric, rt_errors
-from .pose import get_pose
+from .pose import get_pose, get_pose_umeyama
 
 ROT_THR_DEG = 5.0     # trainer.py:156
 TRANS_THR_M = 0.05    # trainer.py:157
@@ -56,7 +56,7 @@ def _batches(buckets: Dict[int, List[int]], bs: int):
 
 @torch.no_grad()
 def eval_records(model: KRRN, dataset: PoseDataset, indices: Dict[int, List[int]], bs: int, device,
-                 opt_pose: bool = True, with_loss: bool = True) -> torch.Tensor:
+                 opt_pose: bool = True, with_loss: bool = True, pose_solver: str = "pnp") -> torch.Tensor:
     """Run the eval path over {S: [crop indices]} in batches of <= bs; returns f64 [n, len(REC)]
     (rows in the order evaluated). Every batch's inputs, forward, pose and ADD(-S) are queued on
     the device without a host round trip; the per-crop records are read back once at the end (the
@@ -67,7 +67,13 @@ def eval_records(model: KRRN, dataset: PoseDataset, indices: Dict[int, List[int]
     run on another beside batch j+1's forward (one workgroup per crop: latency-bound launches that
     fill the CUs the forward leaves idle). The pose reads a copy of the forward's 3-channel xyz map
     (the plan's buffer is rewritten by the next forward of the same shape). Host draws keep the
-    serial order: forward j's pool perms, then get_pose j's point subsets, then forward j+1's."""
+    serial order: forward j's pool perms, then get_pose j's point subsets, then forward j+1's.
+
+    pose_solver: "pnp" (get_pose, the reference's test loop) or "umeyama" (get_pose_umeyama: the base
+    R / t from the depth-based Umeyama-RANSAC of tools/script/eval.py:151; everything else unchanged)."""
+    if pose_solver not in ("pnp", "umeyama"):
+        raise ValueError(f"pose_solver must be 'pnp' or 'umeyama', got {pose_solver!r}")
+    solve_pose = get_pose if pose_solver == "pnp" else get_pose_umeyama
     metric = Metric(dataset.sym_obj)
     pending = []
     batches = list(_batches(indices, bs))
@@ -111,7 +117,7 @@ def eval_records(model: KRRN, dataset: PoseDataset, indices: Dict[int, List[int]
             if pred_t is not None:
                 pred_t.record_stream(pstr)
             with torch.cuda.stream(pstr):
-                base_r, base_t = get_pose({"xyz": xyz}, data)
+                base_r, base_t = solve_pose({"xyz": xyz}, data)
                 add_b = add_metric(base_r, base_t.reshape(B, 3), data["model_points"], data["target"],
                                    data["cls_id"], metric.sys)
                 add_f = None
@@ -226,10 +232,11 @@ def gather_epoch_records(local: torch.Tensor, shard_sizes: Sequence[int], device
 @torch.no_grad()
 def test_epoch(model: KRRN, dataset: PoseDataset, bs: int = 64, device=None, opt_pose: bool = True,
                criterion=None, world: Optional[int] = None, rank: Optional[int] = None,
-               group=None) -> Dict[str, object]:
+               group=None, pose_solver: str = "pnp") -> Dict[str, object]:
     """Trainer.test_epoch over `dataset`. world/rank default to the initialised process group
     (1/0 without one). `criterion` enables the per-crop map-loss terms (dis_xyz / dis_mask /
-    dis_normal) when the batches carry GT maps; the reference always evaluates it (:167)."""
+    dis_normal) when the batches carry GT maps; the reference always evaluates it (:167).
+    `pose_solver` as in eval_records."""
     device = torch.device(device) if device is not None else next(model.parameters()).device
     if world is None:
         world = dist.get_world_size(group) if dist.is_initialized() else 1
@@ -239,7 +246,8 @@ def test_epoch(model: KRRN, dataset: PoseDataset, bs: int = 64, device=None, opt
         raise ValueError(f"rank {rank} outside world {world}")
     sizes = [dataset.crop_size(i) for i in range(len(dataset))]
     mine = kd.bucket_shard(sizes, world, rank)
-    local = eval_records(model, dataset, mine, bs, device, opt_pose=opt_pose, with_loss=criterion is not None)
+    solver = {} if pose_solver == "pnp" else {"pose_solver": pose_solver}  # the default call is unchanged
+    local = eval_records(model, dataset, mine, bs, device, opt_pose=opt_pose, with_loss=criterion is not None, **solver)
     shard_sizes = [sum(len(v) for v in kd.bucket_shard(sizes, world, r).values()) for r in range(world)]
     allrec = gather_epoch_records(local, shard_sizes, device, group) if world > 1 else local
     metric = Metric(dataset.sym_obj)

@@ -19,12 +19,15 @@ from typing import Dict, Optional
 import torch
 
 from .runtime import P, Plan, h2d, ptr
-from . import _lib
+from . import _lib, umeyama
 
 NUM_POINTS = 256
 N_HYP = 100
 THRESHOLD = 1.0
 CONFIDENCE = 0.9999
+# counter-RNG stream ids (krrn.py's pool draws use 0-4, the PnP step 5-7, umeyama.py's own draws 8)
+UMEYAMA_STREAM = 9
+UMEYAMA_PLAN_STREAM = 10
 
 _seeds: Dict[int, torch.Tensor] = {}
 
@@ -85,6 +88,61 @@ def get_pose(pred, data, num_points: int = NUM_POINTS, n_hyp: int = N_HYP, thr: 
     if return_info:
         return R, t, {"inliers": inl, "mask": mask, "sel": sel, "subsets": subsets, "workspace": ws}
     return R, t
+
+
+def get_pose_umeyama(pred, data, n_hyp: int = umeyama.N_HYP, subsets: Optional[torch.Tensor] = None,
+                     return_info: bool = False):
+    """(R [B, 3, 3], t [B, 3]) from the depth: Umeyama-RANSAC (umeyama.estimateSimilarityTransform,
+    lib/transform/umeyama.py:8-98) on the 3D-3D pairs tools/script/eval.py:128,151 feeds it:
+    source = model coordinates of all N chosen pixels (xyz * extent + lfborder, f64 then f32,
+    krrn_model_points_f32), target = data['cloud']. `info` carries the similarity's `scale`, `src`, and the
+    solver's inliers / best_hyp / hyp_counts / mask / subsets; a failed crop has inliers == 0, R = I, t = 0.
+    Without `subsets` [B, H, 5] the samples are drawn on the device (krrn_ransac_subsets: 5 DISTINCT
+    indices per hypothesis, where the reference's np.random.randint draws with replacement);
+    explicit subsets cover exact parity with the reference."""
+    xyz = pred["xyz"]
+    if not xyz.is_cuda:
+        raise RuntimeError("get_pose_umeyama runs on the HIP path only (pred['xyz'] must be a GPU tensor)")
+    dev = xyz.device
+    xyz = xyz.to(torch.float32).contiguous()
+    B, _, H, W = xyz.shape
+    choose = _dev(data["choose"].reshape(B, -1), dev, torch.int64)
+    N = choose.shape[1]
+    cloud = _dev(data["cloud"].reshape(B, N, 3), dev, torch.float32)
+    ext = _dev(data["extent"].reshape(B, 3), dev, torch.float64)
+    lfb = _dev(data["lfborder"].reshape(B, 3), dev, torch.float64)
+    stream = P(torch.cuda.current_stream(dev).cuda_stream)
+    src = torch.empty((B, N, 3), dtype=torch.float32, device=dev)
+    _lib.check(_lib.lib().krrn_model_points_f32(ptr(xyz), H * W, ptr(choose), N, ptr(ext), ptr(lfb), ptr(src), B,
+                                                stream), "krrn_model_points_f32")
+    scale, R, t, info = umeyama.solve(src, cloud, subsets, n_hyp, seed=_seed(dev), stream_id=UMEYAMA_STREAM)
+    if return_info:
+        info.update(scale=scale, src=src)
+        return R, t, info
+    return R, t
+
+
+def add_umeyama_ops(plan: Plan, xyz: torch.Tensor, choose: torch.Tensor, cloud: torch.Tensor, B: int, N: int,
+                    ext: torch.Tensor, lfb: torch.Tensor, seed: torch.Tensor, n_hyp: int = umeyama.N_HYP):
+    """Append the Umeyama-RANSAC pose step to a plan (graph-capturable: subsets drawn on the device from
+    `seed`; the caller's plan advances the seed). Returns (R, t, inliers, info) buffers; info holds
+    scale, src, subsets, hyp_counts, best_hyp, mask."""
+    H, W = xyz.shape[2], xyz.shape[3]
+    src = plan.buf((B, N, 3))
+    subsets = plan.buf((B, n_hyp, 5), torch.int32)
+    counts = plan.buf((B, n_hyp), torch.int32)
+    scale = plan.buf((B,))
+    R = plan.buf((B, 3, 3))
+    t = plan.buf((B, 3))
+    inl = plan.buf((B,), torch.int32)
+    best = plan.buf((B,), torch.int32)
+    mask = plan.buf((B, N), torch.uint8)
+    plan.add("krrn_model_points_f32", ptr(xyz), H * W, ptr(choose), N, ptr(ext), ptr(lfb), ptr(src), B)
+    plan.add("krrn_ransac_subsets", ptr(seed), UMEYAMA_PLAN_STREAM, B, n_hyp, N, ptr(subsets))
+    plan.add("krrn_umeyama_ransac_f32", ptr(src), ptr(cloud), N, ptr(subsets), n_hyp, umeyama.INLIER_FRAC,
+             umeyama.CONFIDENCE, umeyama.MIN_RATIO, ptr(counts), ptr(scale), ptr(R), ptr(t), ptr(inl), ptr(best),
+             ptr(mask), B)
+    return R, t, inl, dict(scale=scale, src=src, subsets=subsets, hyp_counts=counts, best_hyp=best, mask=mask)
 
 
 def add_pose_ops(plan: Plan, xyz: torch.Tensor, choose: torch.Tensor, B: int, N: int, xm: torch.Tensor,

@@ -38,6 +38,8 @@ _lib.register("krrn_gather_rows_f32", [P, I, L, I, P, L, I, P, L, I, I, I, P])
 _lib.register("krrn_tbase_tail_f32", [P, I, I, I, P, P, P, P, P, P])
 _lib.register("krrn_gather2_add_f32", [P, P, L, I, P, P, L, I, I, I, P, P, P, I, P, L, I, I, P])
 _lib.register("krrn_pnp_ransac_f32", [P, I, P, I, P, I, P, P, P, P, P, P, I, F, D, P, P, P, P, P, I, P])
+_lib.register("krrn_model_points_f32", [P, I, P, I, P, P, P, I, P])
+_lib.register("krrn_umeyama_ransac_f32", [P, P, I, P, I, D, D, D, P, P, P, P, P, P, P, I, P])
 _lib.register("krrn_randperm_i32", [P, U, I, I, I, P, P])
 _lib.register("krrn_ransac_subsets", [P, U, I, I, I, P, P])
 _lib.register("krrn_randperm_multi_i32", [P, I, P, P, P, P, P])
