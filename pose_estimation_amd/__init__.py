@@ -17,7 +17,7 @@ Drop-in API (the reference's names):
 """
 from .config import CONFIG, Cfg, make_config  # noqa: F401
 from .krrn import KRRN  # noqa: F401
-from . import bpnp, dataset, fps  # noqa: F401  (register their C-ABI signatures)
+from . import bpnp, dataset, fps  # noqa: F401
 from .loss import KRRNLoss  # noqa: F401
 from .pose import add_umeyama_ops, get_pose, get_pose_umeyama  # noqa: F401
 from .umeyama import estimateSimilarityTransform  # noqa: F401

@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import ctypes
 import os
+import re
 import threading
 
 import torch  # noqa: F401  (loads the HIP runtime libamdhip64.so.7 before our library)
@@ -26,19 +27,48 @@ _ERRORS = {-1: "KRRN_EARG (null pointer / bad argument)",
            -3: "KRRN_EALIGN (16-byte alignment / channel stride violation)",
            -4: "KRRN_EUNSUPPORTED (hipBLASLt rejected the problem)"}
 
-# name -> (argtypes). Every entry point returns int.
-_P = ctypes.c_void_p
-_I = ctypes.c_int
-_F = ctypes.c_float
-_U64 = ctypes.c_uint64
-SIGNATURES = {
-    "krrn_conv2d_f32": [_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _I, _P, _P, _P, _I,
-                        _P, _I, _I, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P],
-}
+# include/krrn_hip.h is the ABI, and the ctypes signatures are read from it: every declaration there is
+# `int krrn_name(type name, ...);` with a pointer or one of these scalar types per parameter
+_HEADER = os.path.join(os.path.dirname(_HERE), "include", "krrn_hip.h")
+_SCALARS = {"int": ctypes.c_int, "unsigned int": ctypes.c_uint, "long long": ctypes.c_longlong,
+            "float": ctypes.c_float, "double": ctypes.c_double}
+
+
+def parse_signatures(src: str) -> dict:
+    """C declarations `int krrn_*(...);` -> {name: argtypes}. Every entry point returns int. Raises on a
+    parameter that is neither a pointer nor one of _SCALARS (not a C parser: the header is that regular)."""
+    src = re.sub(r"/\*.*?\*/|//[^\n]*", " ", src, flags=re.S)
+    sigs = {}
+    for name, params in re.findall(r"\bint\s+(krrn_\w+)\s*\(([^()]*)\)\s*;", src):
+        argtypes = []
+        for param in params.split(","):
+            words = param.split()
+            if "*" in param:
+                argtypes.append(ctypes.c_void_p)
+            elif " ".join(words[:-1]) in _SCALARS:  # the last word is the parameter's name
+                argtypes.append(_SCALARS[" ".join(words[:-1])])
+            else:
+                raise ValueError(f"{name}: no ctypes type for parameter '{' '.join(words)}'")
+        sigs[name] = argtypes
+    return sigs
+
+
+with open(_HEADER) as _f:
+    SIGNATURES = parse_signatures(_f.read())  # name -> argtypes
+
+
+def _bind(handle, name, argtypes):
+    fn = getattr(handle, name)
+    fn.argtypes = argtypes
+    fn.restype = ctypes.c_int
 
 
 def register(name, argtypes):
-    SIGNATURES[name] = argtypes
+    """Signature of a symbol the public header does not declare (a diagnostics build's krrn_diag.h)."""
+    with _lock:
+        SIGNATURES[name] = argtypes
+        if _lib is not None:
+            _bind(_lib, name, argtypes)
 
 
 def lib():
@@ -54,9 +84,7 @@ def lib():
                     "(the KRRN HIP path has no fallback)")
             handle = ctypes.CDLL(LIB_PATH)
             for name, argtypes in SIGNATURES.items():
-                fn = getattr(handle, name)
-                fn.argtypes = argtypes
-                fn.restype = ctypes.c_int
+                _bind(handle, name, argtypes)
             _lib = handle
     return _lib
 

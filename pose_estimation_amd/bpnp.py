@@ -14,17 +14,11 @@ All tensors on the GPU; there is no CPU path.
 """
 from __future__ import annotations
 
-import ctypes
-
 import torch
 import torch.nn as nn
 
 from . import _lib
 from .runtime import P, ptr
-
-_I = ctypes.c_int
-_lib.register("krrn_bpnp_solve_f32", [P, P, _I, P, P, P, _I, _I, _I, P, P, P])
-_lib.register("krrn_bpnp_backward_f32", [P, P, P, _I, P, P, _I, _I, P, P, P, P, P])
 
 LM_ITERS = 50
 RANSAC_THR = 3.0  # reprojectionError of the reference's solvePnPRansac (BPnP.py:36-38)

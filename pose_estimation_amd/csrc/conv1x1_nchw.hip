@@ -11,6 +11,7 @@
 // consecutive pixels: the NCHW store is a 64-B run per channel. One ds_read_b128 of a pixel's
 // (or a weight row's) 4 k-values feeds 4 MFMAs (k = 4g + s over the 4 lane groups).
 #include "krrn_common.h"
+#include "krrn_split.h"
 
 namespace {
 
@@ -132,26 +133,12 @@ __global__ __launch_bounds__(256) void conv1x1_nchw_kernel(const float* __restri
 // in registers into [h h] / [m l] operands. Per 16 k and channel tile three
 // v_mfma_f32_16x16x32_bf16 (W[h l] x X[h h], W[m h] x X[h m], W[m h] x X[m l]: the six term
 // products hh lh mh hm mm hl at f32 accuracy).
-typedef __bf16 nx_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 nx_bf16x2 __attribute__((ext_vector_type(2)));
-typedef float nx_f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned nx_u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned nx_u32x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ unsigned nx_pk(float a, float b) {
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(nx_f32x2{a, b}, nx_bf16x2));  // RNE
+// x (4 k of a pixel) -> the operand quads [h h] and [m l]
+__device__ __forceinline__ void split_quads(const f32x4 x, u32x4& p0, u32x4& p1) {
+  const KrrnSplit3 s = krrn_split3(x);
+  p0 = u32x4{s.h0, s.h1, s.h0, s.h1};
+  p1 = u32x4{s.m0, s.m1, s.l0, s.l1};
 }
-__device__ __forceinline__ void nx_split(const f32x4 x, nx_u32x4& p0, nx_u32x4& p1) {
-  const unsigned h0 = nx_pk(x[0], x[1]), h1 = nx_pk(x[2], x[3]);
-  const float r0 = x[0] - __builtin_bit_cast(float, h0 << 16), r1 = x[1] - __builtin_bit_cast(float, h0 & 0xFFFF0000u);
-  const float r2 = x[2] - __builtin_bit_cast(float, h1 << 16), r3 = x[3] - __builtin_bit_cast(float, h1 & 0xFFFF0000u);
-  const unsigned m0 = nx_pk(r0, r1), m1 = nx_pk(r2, r3);
-  const unsigned l0 = nx_pk(r0 - __builtin_bit_cast(float, m0 << 16), r1 - __builtin_bit_cast(float, m0 & 0xFFFF0000u));
-  const unsigned l1 = nx_pk(r2 - __builtin_bit_cast(float, m1 << 16), r3 - __builtin_bit_cast(float, m1 & 0xFFFF0000u));
-  p0 = nx_u32x4{h0, h1, h0, h1};
-  p1 = nx_u32x4{m0, m1, l0, l1};
-}
-__device__ __forceinline__ nx_bf16x8 nx_op(const nx_u32x4 v) { return __builtin_bit_cast(nx_bf16x8, v); }
 
 constexpr int kX3Steps = 8;         // K = 128: 8 steps of 16 k (4 channel quads x 4 lane groups)
 constexpr int kX3Q = 4 * kX3Steps;  // channel quads per pixel
@@ -165,15 +152,15 @@ __global__ __launch_bounds__(64 * kX3Waves) __attribute__((amdgpu_waves_per_eu(4
                                                                         const float* __restrict__ bias,
                                                                         float* __restrict__ out, int out_cs,
                                                                         int out_co) {
-  __shared__ nx_u32x4 smh[NT * kX3Steps * 64];  // [tile][step][lane]: m0..m3 h0..h3
-  __shared__ nx_u32x2 sl[NT * kX3Steps * 64];   // l0..l3
+  __shared__ u32x4 smh[NT * kX3Steps * 64];  // [tile][step][lane]: m0..m3 h0..h3
+  __shared__ u32x2 sl[NT * kX3Steps * 64];   // l0..l3
   __shared__ float ssc[16 * NT], sbi[16 * NT];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int fr = lane & 15, g = lane >> 4;
   {
     const unsigned nrec = (unsigned)(16 * NT * kX3Q);
-    const nx_u32x4* wmh_g = reinterpret_cast<const nx_u32x4*>(w3);
-    const nx_u32x2* wl_g = reinterpret_cast<const nx_u32x2*>(w3 + 4 * nrec);
+    const u32x4* wmh_g = reinterpret_cast<const u32x4*>(w3);
+    const u32x2* wl_g = reinterpret_cast<const u32x2*>(w3 + 4 * nrec);
     for (int e = tid; e < NT * kX3Steps * 64; e += 64 * kX3Waves) {
       const int l = e & 63, ts = e >> 6, t = ts / kX3Steps, st = ts - t * kX3Steps;
       const int r = (16 * t + (l & 15)) * kX3Q + 4 * st + (l >> 4);
@@ -218,21 +205,21 @@ __global__ __launch_bounds__(64 * kX3Waves) __attribute__((amdgpu_waves_per_eu(4
 #pragma unroll
     for (int st = 0; st < kX3Steps; ++st) {
       asm volatile("" : "+v"(wl_off));
-      nx_u32x4 x0, x1;
-      nx_split(xr[st], x0, x1);
+      u32x4 x0, x1;
+      split_quads(xr[st], x0, x1);
       if (more && (st & 1)) {  // steps 2j, 2j + 1 are the two halves of one 128-B line: request them together
         xr[st - 1] = nok ? *reinterpret_cast<const f32x4*>(np + 16 * (st - 1)) : f32x4{0.f, 0.f, 0.f, 0.f};
         xr[st] = nok ? *reinterpret_cast<const f32x4*>(np + 16 * st) : f32x4{0.f, 0.f, 0.f, 0.f};
       }
-      const nx_u32x4 xhm = nx_u32x4{x0[0], x0[1], x1[0], x1[1]};
+      const u32x4 xhm = u32x4{x0[0], x0[1], x1[0], x1[1]};
 #pragma unroll
       for (int t = 0; t < NT; ++t) {
-        const nx_u32x4 wmh = smh[(t * kX3Steps + st) * 64 + wl_off];
-        const nx_u32x2 wl = sl[(t * kX3Steps + st) * 64 + wl_off];
-        const nx_u32x4 whl = nx_u32x4{wmh[2], wmh[3], wl[0], wl[1]};
-        acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(nx_op(whl), nx_op(x0), acc[t], 0, 0, 0);
-        acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(nx_op(wmh), nx_op(xhm), acc[t], 0, 0, 0);
-        acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(nx_op(wmh), nx_op(x1), acc[t], 0, 0, 0);
+        const u32x4 wmh = smh[(t * kX3Steps + st) * 64 + wl_off];
+        const u32x2 wl = sl[(t * kX3Steps + st) * 64 + wl_off];
+        const u32x4 whl = u32x4{wmh[2], wmh[3], wl[0], wl[1]};
+        acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(krrn_op(whl), krrn_op(x0), acc[t], 0, 0, 0);
+        acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(krrn_op(wmh), krrn_op(xhm), acc[t], 0, 0, 0);
+        acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(krrn_op(wmh), krrn_op(x1), acc[t], 0, 0, 0);
       }
     }
     // acc[t][i] = (channel 16 t + 4 g + i, pixel 16 (c % spi) + fr): 64-B NCHW runs per channel.

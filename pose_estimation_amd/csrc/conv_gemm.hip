@@ -39,6 +39,7 @@
 // store into an NCHW tensor is coalesced (used for the heads' final 1x1 convs, whose
 // outputs are the NCHW `xyz/mask/region/normal` maps of KRRN.forward, krrn.py:100-108).
 #include "krrn_common.h"
+#include "krrn_split.h"
 
 namespace {
 
@@ -109,28 +110,10 @@ struct Cfg {
 // activations are split once while staged, into the LDS chain [h h m l] per 4 k, the weights on
 // the host into [m h l 0] (ops.conv_weights_x3), so the three MFMAs per 8 k read register slices:
 //   A[0:3] x B[2:5] = hh + hl,   A[2:5] x B[0:3] = hm + mh,   A[4:7] x B[0:3] = mm + lh.
-typedef __bf16 cg_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 cg_bf16x2 __attribute__((ext_vector_type(2)));
-typedef float cg_f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned cg_u32x8 __attribute__((ext_vector_type(8)));
-typedef unsigned cg_u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ unsigned cg_pk(float a, float b) {
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(cg_f32x2{a, b}, cg_bf16x2));  // RNE
-}
-
-__device__ __forceinline__ cg_u32x8 cg_split_chain(const f32x4 x) {
-  const unsigned h0 = cg_pk(x[0], x[1]), h1 = cg_pk(x[2], x[3]);
-  const float r0 = x[0] - __builtin_bit_cast(float, h0 << 16), r1 = x[1] - __builtin_bit_cast(float, h0 & 0xFFFF0000u);
-  const float r2 = x[2] - __builtin_bit_cast(float, h1 << 16), r3 = x[3] - __builtin_bit_cast(float, h1 & 0xFFFF0000u);
-  const unsigned m0 = cg_pk(r0, r1), m1 = cg_pk(r2, r3);
-  const unsigned l0 = cg_pk(r0 - __builtin_bit_cast(float, m0 << 16), r1 - __builtin_bit_cast(float, m0 & 0xFFFF0000u));
-  const unsigned l1 = cg_pk(r2 - __builtin_bit_cast(float, m1 << 16), r3 - __builtin_bit_cast(float, m1 & 0xFFFF0000u));
-  return cg_u32x8{h0, h1, h0, h1, m0, m1, l0, l1};
-}
-
-__device__ __forceinline__ cg_bf16x8 cg_sub4(const cg_u32x8& c, int o) {
-  return __builtin_bit_cast(cg_bf16x8, cg_u32x4{c[o], c[o + 1], c[o + 2], c[o + 3]});
+// x (4 k) -> the activation chain [h h m l]
+__device__ __forceinline__ u32x8 split_chain(const f32x4 x) {
+  const KrrnSplit3 s = krrn_split3(x);
+  return u32x8{s.h0, s.h1, s.h0, s.h1, s.m0, s.m1, s.l0, s.l1};
 }
 
 template <int AL, int BL, bool X3>
@@ -247,10 +230,10 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a, const int bid, cons
       const int r = srow + C::RPP * i;
       if (!(C::A_FULL || r < BM)) continue;
       if constexpr (X3) {
-        const cg_u32x8 c = cg_split_chain(st.a[i]);
+        const u32x8 c = split_chain(st.a[i]);
         unsigned* d = reinterpret_cast<unsigned*>(As) + r * PX + 2 * kq;
-        *reinterpret_cast<cg_u32x4*>(d) = cg_u32x4{c[0], c[1], c[2], c[3]};
-        *reinterpret_cast<cg_u32x4*>(d + 4) = cg_u32x4{c[4], c[5], c[6], c[7]};
+        *reinterpret_cast<u32x4*>(d) = u32x4{c[0], c[1], c[2], c[3]};
+        *reinterpret_cast<u32x4*>(d + 4) = u32x4{c[4], c[5], c[6], c[7]};
       } else {
         *reinterpret_cast<f32x4*>(As + r * PITCH + kq) = st.a[i];
       }
@@ -284,12 +267,12 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a, const int bid, cons
 #pragma unroll
     for (int g = 0; g < BK / 8; ++g) {
       const int q = 2 * g + fh;  // this lane half's 4 k of the 8-wide group
-      cg_u32x8 af[MI], bf[NI];
+      u32x8 af[MI], bf[NI];
 #pragma unroll
       for (int i = 0; i < MI; ++i) {
         const unsigned* p = As + (wm * C::WTM + i * 32 + frow) * PX + 8 * q;
-        const cg_u32x4 lo = *reinterpret_cast<const cg_u32x4*>(p), hi = *reinterpret_cast<const cg_u32x4*>(p + 4);
-        af[i] = cg_u32x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+        const u32x4 lo = *reinterpret_cast<const u32x4*>(p), hi = *reinterpret_cast<const u32x4*>(p + 4);
+        af[i] = u32x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
         // one 8-register tuple: both LDS reads land in it and the MFMA operands are its
         // sub-registers (LLVM otherwise rebuilt the overlapping slices with register copies)
         asm volatile("" : "+v"(af[i]));
@@ -297,8 +280,8 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a, const int bid, cons
 #pragma unroll
       for (int j = 0; j < NI; ++j) {
         const unsigned* p = Bs + (wn * C::WTN + j * 32 + frow) * PX + 8 * q;
-        const cg_u32x4 lo = *reinterpret_cast<const cg_u32x4*>(p), hi = *reinterpret_cast<const cg_u32x4*>(p + 4);
-        bf[j] = cg_u32x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+        const u32x4 lo = *reinterpret_cast<const u32x4*>(p), hi = *reinterpret_cast<const u32x4*>(p + 4);
+        bf[j] = u32x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
         asm volatile("" : "+v"(bf[j]));
       }
 #pragma unroll
@@ -307,13 +290,13 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a, const int bid, cons
         for (int j = 0; j < NI; ++j) {
           f32x16& d = acc[i][j];
           if constexpr (NCHW) {
-            d = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cg_sub4(bf[j], 2), cg_sub4(af[i], 0), d, 0, 0, 0);
-            d = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cg_sub4(bf[j], 0), cg_sub4(af[i], 2), d, 0, 0, 0);
-            d = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cg_sub4(bf[j], 0), cg_sub4(af[i], 4), d, 0, 0, 0);
+            d = __builtin_amdgcn_mfma_f32_32x32x16_bf16(krrn_sub4(bf[j], 2), krrn_sub4(af[i], 0), d, 0, 0, 0);
+            d = __builtin_amdgcn_mfma_f32_32x32x16_bf16(krrn_sub4(bf[j], 0), krrn_sub4(af[i], 2), d, 0, 0, 0);
+            d = __builtin_amdgcn_mfma_f32_32x32x16_bf16(krrn_sub4(bf[j], 0), krrn_sub4(af[i], 4), d, 0, 0, 0);
           } else {
-            d = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cg_sub4(af[i], 0), cg_sub4(bf[j], 2), d, 0, 0, 0);
-            d = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cg_sub4(af[i], 2), cg_sub4(bf[j], 0), d, 0, 0, 0);
-            d = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cg_sub4(af[i], 4), cg_sub4(bf[j], 0), d, 0, 0, 0);
+            d = __builtin_amdgcn_mfma_f32_32x32x16_bf16(krrn_sub4(af[i], 0), krrn_sub4(bf[j], 2), d, 0, 0, 0);
+            d = __builtin_amdgcn_mfma_f32_32x32x16_bf16(krrn_sub4(af[i], 2), krrn_sub4(bf[j], 0), d, 0, 0, 0);
+            d = __builtin_amdgcn_mfma_f32_32x32x16_bf16(krrn_sub4(af[i], 4), krrn_sub4(bf[j], 0), d, 0, 0, 0);
           }
         }
     }

@@ -23,15 +23,9 @@
 // missing taps, which are never read). One barrier per chunk. Epilogue: BN scale / bias, ReLU, stored
 // straight from the accumulators (each store instruction = two 128-B channel runs).
 #include "krrn_common.h"
+#include "krrn_split.h"
 
 namespace {
-
-typedef __bf16 ct_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 ct_bf16x2 __attribute__((ext_vector_type(2)));
-typedef float ct_f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned ct_u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned ct_u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned ct_u32x6 __attribute__((ext_vector_type(6)));
 
 constexpr int kR = 4, kCg = 32;                  // grid rows / cols per block
 constexpr int kSR = kR + 2, kSC = kCg + 2;       // staged rows / cols (halo 1 on each side)
@@ -58,24 +52,10 @@ struct ConvTArgs {
   int gyn, gxn;       // blocks per image column / row
 };
 
-__device__ __forceinline__ unsigned ct_pk(float a, float b) {
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(ct_f32x2{a, b}, ct_bf16x2));  // RNE
-}
-__device__ __forceinline__ float ct_lo(unsigned p) { return __builtin_bit_cast(float, p << 16); }
-__device__ __forceinline__ float ct_hi(unsigned p) { return __builtin_bit_cast(float, p & 0xFFFF0000u); }
-
-// x (4 channels) -> [m0 m1 h0 h1 l0 l1] (winograd4.hip split3)
-__device__ __forceinline__ ct_u32x6 ct_split3(const f32x4 x) {
-  const unsigned h0 = ct_pk(x[0], x[1]), h1 = ct_pk(x[2], x[3]);
-  const float r0 = x[0] - ct_lo(h0), r1 = x[1] - ct_hi(h0);
-  const float r2 = x[2] - ct_lo(h1), r3 = x[3] - ct_hi(h1);
-  const unsigned m0 = ct_pk(r0, r1), m1 = ct_pk(r2, r3);
-  const unsigned l0 = ct_pk(r0 - ct_lo(m0), r1 - ct_hi(m0)), l1 = ct_pk(r2 - ct_lo(m1), r3 - ct_hi(m1));
-  return ct_u32x6{m0, m1, h0, h1, l0, l1};
-}
-
-__device__ __forceinline__ ct_bf16x8 ct_sub4(const ct_u32x6& c, int o) {
-  return __builtin_bit_cast(ct_bf16x8, ct_u32x4{c[o], c[o + 1], c[o + 2], c[o + 3]});
+// x (4 channels) -> [m0 m1 h0 h1 l0 l1]
+__device__ __forceinline__ u32x6 split3(const f32x4 x) {
+  const KrrnSplit3 s = krrn_split3(x);
+  return u32x6{s.m0, s.m1, s.h0, s.h1, s.l0, s.l1};
 }
 
 __global__ __launch_bounds__(512, 1) void convt_s2_x3_kernel(const ConvTArgs a) {
@@ -103,10 +83,10 @@ __global__ __launch_bounds__(512, 1) void convt_s2_x3_kernel(const ConvTArgs a) 
   };
   auto store_raw = [&](int buf, const f32x4 x) {
     if (!sitem) return;
-    const ct_u32x6 c = ct_split3(x);
+    const u32x6 c = split3(x);
     char* base = smem + buf * kBuf;
-    *reinterpret_cast<ct_u32x4*>(base + 16 * sslot) = ct_u32x4{c[0], c[1], c[2], c[3]};
-    *reinterpret_cast<ct_u32x2*>(base + kMH + 8 * sslot) = ct_u32x2{c[4], c[5]};
+    *reinterpret_cast<u32x4*>(base + 16 * sslot) = u32x4{c[0], c[1], c[2], c[3]};
+    *reinterpret_cast<u32x2*>(base + kMH + 8 * sslot) = u32x2{c[4], c[5]};
   };
 
   // ---- this wave: class cls, channels 64 nh .. + 63 ------------------------------------------------
@@ -124,8 +104,8 @@ __global__ __launch_bounds__(512, 1) void convt_s2_x3_kernel(const ConvTArgs a) 
   const unsigned wrec = (unsigned)(2 * (64 * nh + fr) + h);  // channel tile j adds 64 records
   // weights of step s = ck * nt + t (chunk ck, tap t): both channel tiles' chains
   struct W2 {
-    ct_u32x4 mh[2];
-    ct_u32x2 l[2];
+    u32x4 mh[2];
+    u32x2 l[2];
   };
   auto load_w = [&](int s) {
     W2 w;
@@ -133,9 +113,9 @@ __global__ __launch_bounds__(512, 1) void convt_s2_x3_kernel(const ConvTArgs a) 
     const unsigned srec = (unsigned)((ck * 16 + cls * 4 + min(t, 3)) * kN * 2);  // uniform
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
-      w.mh[j] = __builtin_bit_cast(ct_u32x4, __builtin_amdgcn_raw_buffer_load_b128(
+      w.mh[j] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(
                                                  rsMH, (wrec + 64u * j) * 16u, srec * 16u, 0));
-      w.l[j] = __builtin_bit_cast(ct_u32x2, __builtin_amdgcn_raw_buffer_load_b64(
+      w.l[j] = __builtin_bit_cast(u32x2, __builtin_amdgcn_raw_buffer_load_b64(
                                                 rsL, (wrec + 64u * j) * 8u, srec * 8u, 0));
     }
     return w;
@@ -147,9 +127,9 @@ __global__ __launch_bounds__(512, 1) void convt_s2_x3_kernel(const ConvTArgs a) 
   };
   auto chain = [&](int buf, int slot) {
     const char* base = smem + buf * kBuf;
-    const ct_u32x4 mh = *reinterpret_cast<const ct_u32x4*>(base + 16 * slot);
-    const ct_u32x2 l = *reinterpret_cast<const ct_u32x2*>(base + kMH + 8 * slot);
-    return ct_u32x6{mh[0], mh[1], mh[2], mh[3], l[0], l[1]};
+    const u32x4 mh = *reinterpret_cast<const u32x4*>(base + 16 * slot);
+    const u32x2 l = *reinterpret_cast<const u32x2*>(base + kMH + 8 * slot);
+    return u32x6{mh[0], mh[1], mh[2], mh[3], l[0], l[1]};
   };
 
   f32x16 acc[kR][2];
@@ -171,29 +151,29 @@ __global__ __launch_bounds__(512, 1) void convt_s2_x3_kernel(const ConvTArgs a) 
     const int p = ck & 1;
     for (int t = 0; t < nt; ++t, ++s) {
       const int tc = a.tap[cls][t];
-      ct_u32x6 bc[2];  // this step's weight chains as single register tuples
+      u32x6 bc[2];  // this step's weight chains as single register tuples
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
-        bc[j] = ct_u32x6{w0.mh[j][0], w0.mh[j][1], w0.mh[j][2], w0.mh[j][3], w0.l[j][0], w0.l[j][1]};
+        bc[j] = u32x6{w0.mh[j][0], w0.mh[j][1], w0.mh[j][2], w0.mh[j][3], w0.l[j][0], w0.l[j][1]};
         asm volatile("" : "+v"(bc[j]));
       }
       W2 w2 = load_w(s + 2);  // two steps ahead (past the end: a harmless repeat)
-      ct_u32x6 an = chain(p, a_off(tc, 0));
+      u32x6 an = chain(p, a_off(tc, 0));
 #pragma unroll
       for (int r = 0; r < kR; ++r) {
-        ct_u32x6 ac = an;
+        u32x6 ac = an;
         if (r + 1 < kR) an = chain(p, a_off(tc, r + 1));
         asm volatile("" : "+v"(ac));  // one register tuple: the MFMA operands are its sub-registers
         // the two channel tiles' term products interleaved: no MFMA waits on the one before it
 #pragma unroll
         for (int j = 0; j < 2; ++j)
-          acc[r][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ct_sub4(ac, 0), ct_sub4(bc[j], 0), acc[r][j], 0, 0, 0);
+          acc[r][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(krrn_sub4(ac, 0), krrn_sub4(bc[j], 0), acc[r][j], 0, 0, 0);
 #pragma unroll
         for (int j = 0; j < 2; ++j)
-          acc[r][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ct_sub4(ac, 0), ct_sub4(bc[j], 2), acc[r][j], 0, 0, 0);
+          acc[r][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(krrn_sub4(ac, 0), krrn_sub4(bc[j], 2), acc[r][j], 0, 0, 0);
 #pragma unroll
         for (int j = 0; j < 2; ++j)
-          acc[r][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ct_sub4(ac, 2), ct_sub4(bc[j], 0), acc[r][j], 0, 0, 0);
+          acc[r][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(krrn_sub4(ac, 2), krrn_sub4(bc[j], 0), acc[r][j], 0, 0, 0);
       }
       w0 = w1;
       w1 = w2;

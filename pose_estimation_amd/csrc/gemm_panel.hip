@@ -24,6 +24,7 @@
 // The row panels of a launch split into `csplit` column ranges when the panels alone cannot fill
 // the chip (level 1: M = 16000 -> 125 panels x 4 column ranges).
 #include "krrn_common.h"
+#include "krrn_split.h"
 
 namespace {
 
@@ -37,13 +38,6 @@ constexpr int kPanelMaxN = 2048;  // columns whose bias a block stages in LDS
 #define KRRN_GP_NW128 4
 #endif
 
-typedef __bf16 gp_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 gp_bf16x2 __attribute__((ext_vector_type(2)));
-typedef float gp_f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned gp_u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned gp_u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned gp_u32x8 __attribute__((ext_vector_type(8)));
-
 struct PanelArgs {
   const float* a;
   const unsigned* w;  // [N/32][K/8][384] u32 (ops.gemm_weights_panel)
@@ -55,13 +49,10 @@ struct PanelArgs {
   int vec;              // float4 epilogue: out / res / bias 16-B aligned, ldo / ldr % 4 == 0
 };
 
-__device__ __forceinline__ unsigned gp_pk(float a, float b) {
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(gp_f32x2{a, b}, gp_bf16x2));  // RNE
-}
-
-__device__ __forceinline__ gp_bf16x8 gp_op(const gp_u32x4 v) { return __builtin_bit_cast(gp_bf16x8, v); }
-__device__ __forceinline__ gp_bf16x8 gp_sub4(const gp_u32x8& c, int o) {
-  return __builtin_bit_cast(gp_bf16x8, gp_u32x4{c[o], c[o + 1], c[o + 2], c[o + 3]});
+// x (4 k of a row) -> the activation chain [h h m l]
+__device__ __forceinline__ u32x8 split_chain(const f32x4 x) {
+  const KrrnSplit3 s = krrn_split3(x);
+  return u32x8{s.h0, s.h1, s.h0, s.h1, s.m0, s.m1, s.l0, s.l1};
 }
 
 // ---- Two blocks per CU, weights staged by LDS DMA (gemm_pdma_x3_kernel) --------------------------
@@ -100,7 +91,7 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void gemm_pdma_x3_kernel(const Pan
   const int nl = lane & 31, fh = lane >> 5;
   const int m0 = blockIdx.x * (32 * NW) + wave * 32;
 
-  gp_u32x8 ca[G];
+  u32x8 ca[G];
   {
     const int row = m0 + nl;
     const float* ap = g.a + (size_t)row * g.lda + 4 * fh;
@@ -109,16 +100,7 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void gemm_pdma_x3_kernel(const Pan
     for (int gi = 0; gi < G; ++gi)
       x[gi] = row < g.M ? *reinterpret_cast<const f32x4*>(ap + 8 * gi) : f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-    for (int gi = 0; gi < G; ++gi) {
-      const f32x4 v = x[gi];
-      const unsigned h0 = gp_pk(v[0], v[1]), h1 = gp_pk(v[2], v[3]);
-      const float r0 = v[0] - __builtin_bit_cast(float, h0 << 16), r1 = v[1] - __builtin_bit_cast(float, h0 & 0xFFFF0000u);
-      const float r2 = v[2] - __builtin_bit_cast(float, h1 << 16), r3 = v[3] - __builtin_bit_cast(float, h1 & 0xFFFF0000u);
-      const unsigned mm0 = gp_pk(r0, r1), mm1 = gp_pk(r2, r3);
-      const unsigned l0 = gp_pk(r0 - __builtin_bit_cast(float, mm0 << 16), r1 - __builtin_bit_cast(float, mm0 & 0xFFFF0000u));
-      const unsigned l1 = gp_pk(r2 - __builtin_bit_cast(float, mm1 << 16), r3 - __builtin_bit_cast(float, mm1 & 0xFFFF0000u));
-      ca[gi] = gp_u32x8{h0, h1, h0, h1, mm0, mm1, l0, l1};
-    }
+    for (int gi = 0; gi < G; ++gi) ca[gi] = split_chain(x[gi]);
   }
 
   const int ct0 = blockIdx.y * g.ntile_per_split;
@@ -164,7 +146,7 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void gemm_pdma_x3_kernel(const Pan
     if (KRRN_GP_EXP & 1) {
       if (v[0] == 1234.5f) g.out[0] = v[1];
     } else if (g.vec) {
-      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(gp_u32x4, v), rsO, vo, ctp * 128, 0);
+      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rsO, vo, ctp * 128, 0);
     } else {
       // out / ldo not 16-B aligned: four dword stores. (Not __builtin_bit_cast(unsigned, v[e]): on an
       // ext_vector element clang (ROCm 7.2) reads element 0 whatever e is -- the IR extracts lane 0 for
@@ -215,15 +197,15 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void gemm_pdma_x3_kernel(const Pan
 #pragma unroll
     for (int gi = 0; gi < G; ++gi) {
       if (live && has) {
-        const gp_u32x4 mh = *reinterpret_cast<const gp_u32x4*>(bp + gi * 384);  // [m h]
-        const gp_u32x2 lp = *reinterpret_cast<const gp_u32x2*>(cur + gi * 384 + 256 + lane * 2);
-        const gp_u32x4 hl = {mh[2], mh[3], lp[0], lp[1]};  // [h l]
+        const u32x4 mh = *reinterpret_cast<const u32x4*>(bp + gi * 384);  // [m h]
+        const u32x2 lp = *reinterpret_cast<const u32x2*>(cur + gi * 384 + 256 + lane * 2);
+        const u32x4 hl = {mh[2], mh[3], lp[0], lp[1]};  // [h l]
 #if KRRN_GP_EXP & 2
         acc[gi & 15] += __uint_as_float(hl[0] ^ mh[1] ^ ca[gi][0]);
 #else
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(gp_op(hl), gp_sub4(ca[gi], 0), acc, 0, 0, 0);  // hh + lh
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(gp_op(mh), gp_sub4(ca[gi], 2), acc, 0, 0, 0);  // mh + hm
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(gp_op(mh), gp_sub4(ca[gi], 4), acc, 0, 0, 0);  // mm + hl
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(krrn_op(hl), krrn_sub4(ca[gi], 0), acc, 0, 0, 0);  // hh + lh
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(krrn_op(mh), krrn_sub4(ca[gi], 2), acc, 0, 0, 0);  // mh + hm
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(krrn_op(mh), krrn_sub4(ca[gi], 4), acc, 0, 0, 0);  // mm + hl
 #endif
       }
       if (st && gi % (G / 4) == 0) epilogue_t(ct - 1, gi / (G / 4));

@@ -32,13 +32,9 @@
 // TBase conv1 by linearity (posenet.py: the fusion's level rows times W1, BN / bias / one-hot
 // column folded into them) feeding conv2 directly, so the 1024-wide h1 is never written to HBM.
 #include "krrn_common.h"
+#include "krrn_split.h"
 
 namespace {
-
-typedef __bf16 gx_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 gx_bf16x2 __attribute__((ext_vector_type(2)));
-typedef float gx_f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned gx_u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int BM = 128, BN = 128;
 constexpr int KC = 16;          // k per LDS chunk
@@ -62,24 +58,13 @@ struct GemmArgs {
   int mt, nt, total;  // row tiles, column tiles per group; tiles in the grid
 };
 
-__device__ __forceinline__ unsigned gx_pk(float a, float b) {
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(gx_f32x2{a, b}, gx_bf16x2));  // RNE
-}
-
 // 4 consecutive k of one row -> the three MFMA operand quads [h h] [h m] [m l]
-__device__ __forceinline__ void gx_split(const f32x4 x, gx_u32x4& q0, gx_u32x4& q1, gx_u32x4& q2) {
-  const unsigned h0 = gx_pk(x[0], x[1]), h1 = gx_pk(x[2], x[3]);
-  const float r0 = x[0] - __builtin_bit_cast(float, h0 << 16), r1 = x[1] - __builtin_bit_cast(float, h0 & 0xFFFF0000u);
-  const float r2 = x[2] - __builtin_bit_cast(float, h1 << 16), r3 = x[3] - __builtin_bit_cast(float, h1 & 0xFFFF0000u);
-  const unsigned m0 = gx_pk(r0, r1), m1 = gx_pk(r2, r3);
-  const unsigned l0 = gx_pk(r0 - __builtin_bit_cast(float, m0 << 16), r1 - __builtin_bit_cast(float, m0 & 0xFFFF0000u));
-  const unsigned l1 = gx_pk(r2 - __builtin_bit_cast(float, m1 << 16), r3 - __builtin_bit_cast(float, m1 & 0xFFFF0000u));
-  q0 = gx_u32x4{h0, h1, h0, h1};
-  q1 = gx_u32x4{h0, h1, m0, m1};
-  q2 = gx_u32x4{m0, m1, l0, l1};
+__device__ __forceinline__ void split_quads(const f32x4 x, u32x4& q0, u32x4& q1, u32x4& q2) {
+  const KrrnSplit3 s = krrn_split3(x);
+  q0 = u32x4{s.h0, s.h1, s.h0, s.h1};
+  q1 = u32x4{s.h0, s.h1, s.m0, s.m1};
+  q2 = u32x4{s.m0, s.m1, s.l0, s.l1};
 }
-
-__device__ __forceinline__ gx_bf16x8 gx_op(const gx_u32x4 v) { return __builtin_bit_cast(gx_bf16x8, v); }
 
 template <bool GA>
 __global__ __launch_bounds__(256, 2) void gemm_x3_kernel(const GemmArgs g) {
@@ -147,25 +132,25 @@ __global__ __launch_bounds__(256, 2) void gemm_x3_kernel(const GemmArgs g) {
     unsigned* d = smem + s * BM * PX;
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
-      gx_u32x4 q0, q1, q2;
+      u32x4 q0, q1, q2;
       f32x4 x = ra[s][i];
       if constexpr (GA) {
         x += rq[s][i];
 #pragma unroll
         for (int e = 0; e < 4; ++e) x[e] = fmaxf(x[e], 0.f);
       }
-      gx_split(x, q0, q1, q2);
+      split_quads(x, q0, q1, q2);
       unsigned* p = d + (srow + 64 * i) * PX + 3 * kq;
-      *reinterpret_cast<gx_u32x4*>(p) = q0;
-      *reinterpret_cast<gx_u32x4*>(p + 4) = q1;
-      *reinterpret_cast<gx_u32x4*>(p + 8) = q2;
+      *reinterpret_cast<u32x4*>(p) = q0;
+      *reinterpret_cast<u32x4*>(p + 4) = q1;
+      *reinterpret_cast<u32x4*>(p + 8) = q2;
     }
   };
-  gx_u32x4 wr[4][2];  // weight quads of 4 groups (ring): [h h | l l]-paired P0 and [m m | h h] P1
+  u32x4 wr[4][2];  // weight quads of 4 groups (ring): [h h | l l]-paired P0 and [m m | h h] P1
   auto load_w = [&](int gi, int s) {
     const unsigned* p = wb + (size_t)min(gi, G - 1) * 512;
-    wr[s][0] = *reinterpret_cast<const gx_u32x4*>(p);
-    wr[s][1] = *reinterpret_cast<const gx_u32x4*>(p + 256);
+    wr[s][0] = *reinterpret_cast<const u32x4*>(p);
+    wr[s][1] = *reinterpret_cast<const u32x4*>(p + 256);
   };
 
   f32x16 acc[4];
@@ -175,23 +160,23 @@ __global__ __launch_bounds__(256, 2) void gemm_x3_kernel(const GemmArgs g) {
     for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
   // a group's activation operands: 4 row blocks x the quads [h h] [h m] [m l], each one
   // ds_read_b128 (no register shuffles); read one group ahead of its MFMAs
-  typedef gx_u32x4 Frag[4][3];
+  typedef u32x4 Frag[4][3];
   auto read_frag = [&](int buf, int gl, Frag& f) {
     const unsigned* As = smem + buf * BM * PX;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const unsigned* p = As + (i * 32 + frow) * PX + 12 * (2 * gl + fh);
 #pragma unroll
-      for (int q = 0; q < 3; ++q) f[i][q] = *reinterpret_cast<const gx_u32x4*>(p + 4 * q);
+      for (int q = 0; q < 3; ++q) f[i][q] = *reinterpret_cast<const u32x4*>(p + 4 * q);
     }
   };
   auto mma = [&](const Frag& f, int s) {
-    const gx_bf16x8 p0 = gx_op(wr[s][0]), p1 = gx_op(wr[s][1]);
+    const bf16x8 p0 = krrn_op(wr[s][0]), p1 = krrn_op(wr[s][1]);
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(gx_op(f[i][0]), p0, acc[i], 0, 0, 0);  // hh + hl
-      acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(gx_op(f[i][1]), p1, acc[i], 0, 0, 0);  // hm + mh
-      acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(gx_op(f[i][2]), p1, acc[i], 0, 0, 0);  // mm + lh
+      acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(krrn_op(f[i][0]), p0, acc[i], 0, 0, 0);  // hh + hl
+      acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(krrn_op(f[i][1]), p1, acc[i], 0, 0, 0);  // hm + mh
+      acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(krrn_op(f[i][2]), p1, acc[i], 0, 0, 0);  // mm + lh
     }
   };
 

@@ -40,6 +40,7 @@
 // cluster (+2 %), a 32-wide N tile at 3 blocks/CU (1.54-1.56 ms), a ping-pong kernel with two
 // wave groups (1.95 ms), LDS-DMA weights (1.49 ms).
 #include "krrn_common.h"
+#include "krrn_split.h"
 
 namespace {
 
@@ -456,33 +457,10 @@ __global__ __launch_bounds__(256, 2) void wino_f23_ring_kernel(const WinoArgs a)
 // block (2 components x 2 tile-blocks x 2 n-blocks per wave: half the weight loads per MFMA and a
 // bank-conflict-free ring layout, but one block per CU: 1.05-1.12 ms), sched_barrier-pinned
 // reloads (no change).
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ unsigned pk_bf16(float a, float b) {
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{a, b}, bf16x2));  // RNE
-}
-__device__ __forceinline__ float bf_lo(unsigned p) { return __builtin_bit_cast(float, p << 16); }
-__device__ __forceinline__ float bf_hi(unsigned p) { return __builtin_bit_cast(float, p & 0xFFFF0000u); }
-
-typedef unsigned u32x6 __attribute__((ext_vector_type(6)));
-
 // x (4 channels) -> the A chain [x_m x_h x_l] as packed bf16 pairs
 __device__ __forceinline__ u32x6 split3_chain(const f32x4 x) {
-  const unsigned h0 = pk_bf16(x[0], x[1]), h1 = pk_bf16(x[2], x[3]);
-  const float r0 = x[0] - bf_lo(h0), r1 = x[1] - bf_hi(h0);
-  const float r2 = x[2] - bf_lo(h1), r3 = x[3] - bf_hi(h1);
-  const unsigned m0 = pk_bf16(r0, r1), m1 = pk_bf16(r2, r3);
-  const unsigned l0 = pk_bf16(r0 - bf_lo(m0), r1 - bf_hi(m0)), l1 = pk_bf16(r2 - bf_lo(m1), r3 - bf_hi(m1));
-  return u32x6{m0, m1, h0, h1, l0, l1};
-}
-
-__device__ __forceinline__ bf16x8 sub4(const u32x6& c, int o) {
-  return __builtin_bit_cast(bf16x8, u32x4{c[o], c[o + 1], c[o + 2], c[o + 3]});
+  const KrrnSplit3 s = krrn_split3(x);
+  return u32x6{s.m0, s.m1, s.h0, s.h1, s.l0, s.l1};
 }
 
 template <bool HEAD>
@@ -631,9 +609,9 @@ __global__ __launch_bounds__(256, 2) void wino_f23_x3_kernel(const WinoArgs a) {
 #if KRRN_WINO_EXP == 7  // timing experiment: no MFMAs (operands still formed and loaded)
         acc[v][j][0] += __uint_as_float(ac[0] ^ ac[4] ^ bc[0] ^ bc[4]);
 #else
-        acc[v][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(sub4(ac, 0), sub4(bc, 0), acc[v][j], 0, 0, 0);  // mm + hh
-        acc[v][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(sub4(ac, 0), sub4(bc, 2), acc[v][j], 0, 0, 0);  // mh + hl
-        acc[v][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(sub4(ac, 2), sub4(bc, 0), acc[v][j], 0, 0, 0);  // hm + lh
+        acc[v][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(krrn_sub4(ac, 0), krrn_sub4(bc, 0), acc[v][j], 0, 0, 0);  // mm + hh
+        acc[v][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(krrn_sub4(ac, 0), krrn_sub4(bc, 2), acc[v][j], 0, 0, 0);  // mh + hl
+        acc[v][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(krrn_sub4(ac, 2), krrn_sub4(bc, 0), acc[v][j], 0, 0, 0);  // hm + lh
 #endif
       }
       load_wv(ck + 1, v);

@@ -46,16 +46,9 @@
 #include <type_traits>
 
 #include "krrn_common.h"
+#include "krrn_split.h"
 
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x3 __attribute__((ext_vector_type(3)));
-typedef unsigned u32x6 __attribute__((ext_vector_type(6)));
 
 constexpr int kGX = 16, kGY = 2, kT = kGX * kGY;  // tiles per block
 constexpr int kN = 64;                            // output channels per block
@@ -142,32 +135,16 @@ __device__ __forceinline__ float dpp_f(float x) {
   return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), CTRL, 0xF, 0xF, false));
 }
 
-__device__ __forceinline__ unsigned pk_bf16(float a, float b) {
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{a, b}, bf16x2));  // RNE
-}
-__device__ __forceinline__ float bf_lo(unsigned p) { return __builtin_bit_cast(float, p << 16); }
-__device__ __forceinline__ float bf_hi(unsigned p) { return __builtin_bit_cast(float, p & 0xFFFF0000u); }
-
-// x (4 channels) -> the operand chain [x_m x_h x_l] as packed bf16 pairs (winograd.hip split3_chain)
+// x (4 channels) -> the operand chain [x_m x_h x_l] as packed bf16 pairs
 __device__ __forceinline__ u32x6 split3(const f32x4 x) {
-  const unsigned h0 = pk_bf16(x[0], x[1]), h1 = pk_bf16(x[2], x[3]);
-  const float r0 = x[0] - bf_lo(h0), r1 = x[1] - bf_hi(h0);
-  const float r2 = x[2] - bf_lo(h1), r3 = x[3] - bf_hi(h1);
-  const unsigned m0 = pk_bf16(r0, r1), m1 = pk_bf16(r2, r3);
-  const unsigned l0 = pk_bf16(r0 - bf_lo(m0), r1 - bf_hi(m0)), l1 = pk_bf16(r2 - bf_lo(m1), r3 - bf_hi(m1));
-  return u32x6{m0, m1, h0, h1, l0, l1};
-}
-
-__device__ __forceinline__ bf16x8 sub4(const u32x6& c, int o) {
-  return __builtin_bit_cast(bf16x8, u32x4{c[o], c[o + 1], c[o + 2], c[o + 3]});
+  const KrrnSplit3 s = krrn_split3(x);
+  return u32x6{s.m0, s.m1, s.h0, s.h1, s.l0, s.l1};
 }
 
 // x (a channel pair) -> its packed bf16 terms {m, h, l}
 __device__ __forceinline__ u32x3 split3_pair(const f32x2 x) {
-  const unsigned hh = pk_bf16(x[0], x[1]);
-  const float r0 = x[0] - bf_lo(hh), r1 = x[1] - bf_hi(hh);
-  const unsigned m = pk_bf16(r0, r1);
-  return u32x3{m, hh, pk_bf16(r0 - bf_lo(m), r1 - bf_hi(m))};
+  const KrrnSplit3Pair s = krrn_split3_pair(x);
+  return u32x3{s.m, s.h, s.l};
 }
 
 // row K of B^T applied to x[0..5] (scalar f32, element-wise over the vector's channels)
@@ -611,9 +588,9 @@ __global__ __launch_bounds__(512, 1) void wino_f43_x3_kernel(const Wino4Args a) 
 #if KRRN_W4_EXP & 1
       acc[k][0] += __uint_as_float(ac[0] ^ ac[4] ^ bc[0] ^ bc[4]);
 #else
-      acc[k] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(sub4(ac, 0), sub4(bc, 0), acc[k], 0, 0, 0);  // mm + hh
-      acc[k] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(sub4(ac, 0), sub4(bc, 2), acc[k], 0, 0, 0);  // mh + hl
-      acc[k] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(sub4(ac, 2), sub4(bc, 0), acc[k], 0, 0, 0);  // hm + lh
+      acc[k] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(krrn_sub4(ac, 0), krrn_sub4(bc, 0), acc[k], 0, 0, 0);  // mm + hh
+      acc[k] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(krrn_sub4(ac, 0), krrn_sub4(bc, 2), acc[k], 0, 0, 0);  // mh + hl
+      acc[k] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(krrn_sub4(ac, 2), krrn_sub4(bc, 0), acc[k], 0, 0, 0);  // hm + lh
 #endif
 #if !(KRRN_W4_EXP & 2)
       if (k < 6) load_w(ck, k + 3); else load_w(ck + 1, k - 6);

@@ -32,7 +32,6 @@ with an object bump, LineMOD intrinsics and models_info extents, a GT pose and m
 """
 from __future__ import annotations
 
-import ctypes
 import os
 import random
 from collections import OrderedDict
@@ -46,11 +45,6 @@ from . import _lib
 from .config import CONFIG, LM_OBJLIST, OBJ_DICT, SYM_OBJ, models_info
 from .runtime import P, h2d, ptr
 from .synthetic import LM_K, rand_rotation
-
-_I = ctypes.c_int
-_F = ctypes.c_float
-_lib.register("krrn_crop_inputs_u8", [P, P, P, P, _I, _I, _I, P, P, _I, _I, P, P, P])
-_lib.register("krrn_choose_points", [P, _I, _I, _I, P, _I, _I, P, P, P, _F, P, _I, P, P, P, P, P, P])
 
 # batchdataset.py:823
 BORDER_LIST = [-1] + list(range(40, 640, 40)) + [640]

@@ -6,14 +6,10 @@ head, batchdataset.py:723-728). One workgroup per point set (krrn_fps_f32).
 """
 from __future__ import annotations
 
-import ctypes
-
 import torch
 
 from . import _lib
 from .runtime import P, ptr
-
-_lib.register("krrn_fps_f32", [P, ctypes.c_int, ctypes.c_int, ctypes.c_int, P, P])
 
 
 def farthest_point_sampling(points: torch.Tensor, n_samples: int) -> torch.Tensor:

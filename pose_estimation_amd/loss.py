@@ -23,14 +23,6 @@ from . import _lib
 from .config import CONFIG, SYM_OBJ
 from .runtime import P, ptr
 
-_I = ctypes.c_int
-_L = ctypes.c_longlong
-_lib.register("krrn_map_losses_ws", [_I, _I, P])
-_lib.register("krrn_map_losses_f32", [P, P, P, P, P, _I, P, P, _I, P, _I, _I, P, P, P])
-_lib.register("krrn_map_losses_crop_f32", [P, _I, _I, P, P])
-_lib.register("krrn_pose_loss_ws", [_I, _I, P])
-_lib.register("krrn_pose_loss_f32", [P, P, P, P, P, P, _I, _I, _I, P, P, P])
-
 
 def _stream(dev) -> P:
     return P(torch.cuda.current_stream(dev).cuda_stream)

@@ -13,13 +13,8 @@ from typing import List, Sequence, Tuple
 import numpy as np
 import torch
 
-import ctypes
-
 from . import _lib
 from .runtime import P, h2d, ptr
-
-_I = ctypes.c_int
-_lib.register("krrn_add_metric_f32", [P, P, P, P, P, P, _I, _I, _I, P, P, P])
 
 
 def add_metric(pred_r: torch.Tensor, pred_t: torch.Tensor, model_points: torch.Tensor, target: torch.Tensor,

@@ -20,49 +20,6 @@ from . import _lib, knobs, ops
 
 P = ctypes.c_void_p
 I = ctypes.c_int
-F = ctypes.c_float
-D = ctypes.c_double
-L = ctypes.c_longlong
-U = ctypes.c_uint
-
-# C-ABI signatures (include/krrn_hip.h); every function returns int status.
-_lib.register("krrn_knn_f32", [P, L, I, I, P, P, L, I, I, I, I, I, I, I, P, P])
-_lib.register("krrn_gcn_conv_f32", [P, I, I, P, L, I, I, P, I, I, P, P, P, I, P, L, I, I, P])
-_lib.register("krrn_pool_max_f32", [P, I, I, P, L, I, I, P, L, I, I, P])
-_lib.register("krrn_resize_bilinear_f32", [P, I, I, I, I, I, I, P, I, I, I, I, P, I, I, I, I, P])
-_lib.register("krrn_add_relu_f32", [P, I, I, P, I, I, P, I, I, L, I, I, P])
-_lib.register("krrn_nchw_to_nhwc_f32", [P, I, I, I, I, P, I, I, P])
-_lib.register("krrn_heads_select_f32", [P, I, I, P, I, P, P, P, I, I, I, P])
-_lib.register("krrn_points_gather_f32", [P, P, P, P, I, I, I, I, P, P])
-_lib.register("krrn_gather_rows_f32", [P, I, L, I, P, L, I, P, L, I, I, I, P])
-_lib.register("krrn_tbase_tail_f32", [P, I, I, I, P, P, P, P, P, P])
-_lib.register("krrn_gather2_add_f32", [P, P, L, I, P, P, L, I, I, I, P, P, P, I, P, L, I, I, P])
-_lib.register("krrn_pnp_ransac_f32", [P, I, P, I, P, I, P, P, P, P, P, P, I, F, D, P, P, P, P, P, I, P])
-_lib.register("krrn_model_points_f32", [P, I, P, I, P, P, P, I, P])
-_lib.register("krrn_umeyama_ransac_f32", [P, P, I, P, I, D, D, D, P, P, P, P, P, P, P, I, P])
-_lib.register("krrn_randperm_i32", [P, U, I, I, I, P, P])
-_lib.register("krrn_ransac_subsets", [P, U, I, I, I, P, P])
-_lib.register("krrn_randperm_multi_i32", [P, I, P, P, P, P, P])
-_lib.register("krrn_rng_advance", [P, P])
-_lib.register("krrn_conv2d_group_f32", [P, I, I, P])
-_lib.register("krrn_conv2d_group_x3_f32", [P, I, I, P])
-_lib.register("krrn_conv2d_x3_f32", [P, I, I, I, I, I, I, I, I, I, I, P, P, P, I, I, P, P, P, I, P, I, I, P, I, I, I, I,
-                                     I, I, I, I, I, I, I, P, P])
-_lib.register("krrn_conv3x3_wino_f32", [P, I, I, I, I, I, I, P, I, I, P, P, P, I, I, P, I, I, I, P])
-_lib.register("krrn_conv3x3_wino_x3_f32", [P, I, I, I, I, I, I, P, I, I, P, P, P, I, I, P, I, I, I, P])
-_lib.register("krrn_conv3x3_wino4_x3_f32", [P, I, I, I, I, I, I, P, I, I, P, P, P, I, I, P, I, I, I, P])
-_lib.register("krrn_convT_s2_x3_f32", [P, I, I, I, I, I, I, P, P, I, P, P, I, P, I, I, I, I, P])
-_lib.register("krrn_conv3x3_wino_x3_head_f32", [P, I, I, I, I, I, I, P, I, P, P, P, I, I, I, P, P, I, P, P, I, P])
-_lib.register("krrn_conv3x3_wino4_x3_head_f32", [P, I, I, I, I, I, I, P, I, P, P, P, I, I, I, P, P, I, P, P, I, P])
-_lib.register("krrn_conv1x1_nchw_f32", [P, I, I, I, I, I, P, I, I, P, P, P, I, I, P])
-_lib.register("krrn_conv1x1_nchw_x3_f32", [P, I, I, I, I, I, P, I, I, P, P, P, I, I, P])
-_lib.register("krrn_conv_small_f32", [P, I, I, I, I, I, I, P, I, I, P, P, P, I, I, P, I, I, I, I, I, I, I, P])
-_lib.register("krrn_blas_gemm_create", [I, I, I, I, I, I, L, L, I, I, I, I, L, L, P, P])
-_lib.register("krrn_blas_gemm_run", [P, P, P, P, P, P, P, L, P])
-_lib.register("krrn_blas_gemm_destroy", [P])
-_lib.register("krrn_gemm_x3_f32", [P, I, I, I, I, P, P, P, I, P, I, I, I, L, L, L, P])
-_lib.register("krrn_gemm_x3_gather_f32", [P, P, L, I, P, P, L, I, I, I, I, I, P, P, P, I, I, P])
-_lib.register("krrn_gemm_panel_x3_f32", [P, I, I, I, I, P, P, P, I, P, I, I, I, P])
 
 
 class ConvDesc(ctypes.Structure):

@@ -8,7 +8,6 @@ import re
 import pytest
 
 from pose_estimation_amd import _lib
-from pose_estimation_amd import bpnp, dataset, fps, loss, metric, runtime  # noqa: F401  (register the signatures)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "krrn_hip.h")
@@ -38,6 +37,51 @@ def test_ctypes_signatures_match_header_arity():
         m = re.search(rf"^int {name}\((.*?)\);", src, re.M | re.S)
         nargs = len([a for a in m.group(1).split(",") if a.strip()])
         assert nargs == len(_lib.SIGNATURES[name]), (name, nargs, len(_lib.SIGNATURES[name]))
+
+
+# the signatures of a few entry points written out by hand, independent of the parser; between them they
+# use every scalar type of the ABI
+_P, _I, _U, _L, _F, _D = (ctypes.c_void_p, ctypes.c_int, ctypes.c_uint, ctypes.c_longlong, ctypes.c_float,
+                          ctypes.c_double)
+EXPECTED = {
+    "krrn_conv2d_f32": [_P] + [_I] * 10 + [_P, _P, _P, _I, _I, _P, _P, _P, _I, _P, _I, _I, _P] + [_I] * 12 + [_P, _P],
+    "krrn_knn_f32": [_P, _L, _I, _I, _P, _P, _L, _I, _I, _I, _I, _I, _I, _I, _P, _P],  # long long strides
+    "krrn_pnp_ransac_f32": [_P, _I, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _I, _F, _D, _P, _P, _P, _P, _P, _I, _P],
+    "krrn_blas_gemm_create": [_I] * 6 + [_L, _L, _I, _I, _I, _I, _L, _L, _P, _P],  # ** and * out-parameters
+    "krrn_randperm_i32": [_P, _U, _I, _I, _I, _P, _P],  # unsigned int
+}
+
+
+def test_ctypes_signatures_match_header_types():
+    assert len(EXPECTED["krrn_conv2d_f32"]) == 38
+    assert {t for sig in EXPECTED.values() for t in sig} == {_P, _I, _U, _L, _F, _D}
+    for name, argtypes in EXPECTED.items():
+        assert _lib.SIGNATURES[name] == argtypes, name
+    lib = _lib.lib()
+    for name in _declared():
+        fn = getattr(lib, name)
+        assert list(fn.argtypes) == _lib.SIGNATURES[name] and fn.restype is ctypes.c_int, name
+
+
+@pytest.mark.parametrize("ctype", ["short", "size_t", "unsigned", "unsigned long long", "int64_t"])
+def test_parser_rejects_unknown_scalar_type(ctype):
+    with pytest.raises(ValueError, match=rf"krrn_thing.*{ctype} n"):
+        _lib.parse_signatures(f"int krrn_thing(const float* a, {ctype} n, void* stream);")
+    ok = _lib.parse_signatures("/* int krrn_no(short n); */\nint krrn_thing(const float* a,\n    long long n); // x")
+    assert ok == {"krrn_thing": [_P, _L]}
+
+
+def test_register_after_load_binds_at_once():
+    lib = _lib.lib()
+    name = "krrn_rng_advance"
+    fn, before = getattr(lib, name), _lib.SIGNATURES[name]
+    try:
+        fn.argtypes = None
+        _lib.register(name, list(before))
+        assert list(fn.argtypes) == before and fn.restype is ctypes.c_int
+    finally:
+        _lib.SIGNATURES[name] = before
+        fn.argtypes = before
 
 
 def test_host_side_errors():

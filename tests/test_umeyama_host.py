@@ -10,7 +10,7 @@ import pytest
 import torch
 
 import umeyama_ref as ur
-from pose_estimation_amd import _lib, runtime  # noqa: F401  (registers the signatures)
+from pose_estimation_amd import _lib
 from pose_estimation_amd.umeyama import estimateSimilarityTransform
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "umeyama_scenes.npz")
