@@ -369,6 +369,25 @@ int krrn_umeyama_ransac_f32(const float* src, const float* dst, int N, const int
                             float* scale, float* R, float* t, int* inliers, int* best_hyp,
                             unsigned char* inlier_mask, int B, void* stream);
 
+/* Point-to-point ICP refinement of a pose against the depth cloud, batched (this project's own
+ * definition: the reference has none). R0 [B][9] row-major, t0 [B][3]: the starting pose, model to
+ * camera (p = R m + t); cloud f32 [B][N][3] (3 <= N <= 4096), model f32 [B][M][3] (1 <= M <= 4096),
+ * max_dist [B] in metres. Pass k = 0 .. max_iter (<= 64): q_i = R^T (p_i - t); the nearest model point
+ * j(i) by d^2 = (dx dx + dy dy) + dz dz (the lowest j among equal distances); pair i kept iff
+ * d_i^2 < max_dist^2; K pairs, err_k = mean kept d^2. Stop, tested in this order: K < min_pairs
+ * (>= 3) -> status 2 STARVED; k >= 1 and |err_{k-1} - err_k| <= tol err_{k-1} -> 0 CONVERGED;
+ * k == max_iter -> 1 MAX_ITER. Otherwise Kabsch on the kept pairs (two-pass covariance, the Jacobi SVD
+ * of krrn_umeyama_ransac_f32) gives the next R, t; if that is not finite the pose from before the
+ * update is returned with 3 DEGENERATE. Outputs (must not alias the inputs): R [B][9], t [B][3],
+ * passes [B] = k + 1, pairs [B] = K and rmse [B] = sqrt(err_k) (+inf for K = 0) of the returned pose,
+ * status [B], nn_idx int32 [B][N] (optional: j(i) of the returned pose, -1 = rejected). A stop in pass
+ * 0 (max_iter 0, no pairs, a non-finite start) returns R0, t0 bit for bit. All arithmetic in f64; one
+ * block per crop and one launch for the whole loop, fixed-order sums, no atomics: a crop's outputs do
+ * not depend on the rest of the batch. */
+int krrn_icp_refine_f32(const float* R0, const float* t0, const float* cloud, int N, const float* model, int M,
+                        const float* max_dist, int max_iter, double tol, int min_pairs, float* R, float* t,
+                        int* passes, int* pairs, float* rmse, int* status, int* nn_idx, int B, void* stream);
+
 /* torch.randperm(n)[:k] per row (gcn3d.py:239, trainer.py:407) from a counter-based generator
  * seeded by *seed_ptr (device memory) and `stream_id`; n <= 4096. out int32 [rows][k]. */
 int krrn_randperm_i32(const unsigned long long* seed_ptr, unsigned int stream_id, int n, int k, int rows, int* out,

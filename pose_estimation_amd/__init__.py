@@ -7,6 +7,7 @@ Drop-in API (the reference's names):
     get_pose(pred, data)                  tools/trainer.py:383-438 (Trainer.get_pose)
     estimateSimilarityTransform(src, dst) lib/transform/umeyama.py:8-98 (Umeyama-RANSAC, batched)
     get_pose_umeyama(pred, data)          tools/script/eval.py:128,151 (the depth-based pose)
+    refine_pose_icp(R, t, data, diameter) ICP polish against the depth cloud (icp.py; this project's own)
     PoseDataset / make_batch              dataset/linemod/batchdataset.py (synthetic frames)
     Metric                                lib/utils/metric.py
     KRRNLoss                              lib/network/loss.py (eval-time terms)
@@ -19,8 +20,9 @@ from .config import CONFIG, Cfg, make_config  # noqa: F401
 from .krrn import KRRN  # noqa: F401
 from . import bpnp, dataset, fps  # noqa: F401
 from .loss import KRRNLoss  # noqa: F401
-from .pose import add_umeyama_ops, get_pose, get_pose_umeyama  # noqa: F401
+from . import icp  # noqa: F401
+from .pose import add_icp_ops, add_umeyama_ops, get_pose, get_pose_umeyama, refine_pose_icp  # noqa: F401
 from .umeyama import estimateSimilarityTransform  # noqa: F401
 
 __all__ = ["KRRN", "KRRNLoss", "get_pose", "get_pose_umeyama", "add_umeyama_ops", "estimateSimilarityTransform",
-           "make_config", "CONFIG", "Cfg"]
+           "icp", "refine_pose_icp", "add_icp_ops", "make_config", "CONFIG", "Cfg"]

@@ -34,7 +34,7 @@ from .dataset import PoseDataset
 from .krrn import KRRN
 from .loss import map_losses
 from .metric import Metric, add_metric, rt_errors
-from .pose import get_pose, get_pose_umeyama
+from .pose import get_pose, get_pose_umeyama, refine_pose_icp
 
 ROT_THR_DEG = 5.0     # trainer.py:156
 TRANS_THR_M = 0.05    # trainer.py:157
@@ -56,7 +56,8 @@ def _batches(buckets: Dict[int, List[int]], bs: int):
 
 @torch.no_grad()
 def eval_records(model: KRRN, dataset: PoseDataset, indices: Dict[int, List[int]], bs: int, device,
-                 opt_pose: bool = True, with_loss: bool = True, pose_solver: str = "pnp") -> torch.Tensor:
+                 opt_pose: bool = True, with_loss: bool = True, pose_solver: str = "pnp",
+                 refine: Optional[str] = None) -> torch.Tensor:
     """Run the eval path over {S: [crop indices]} in batches of <= bs; returns f64 [n, len(REC)]
     (rows in the order evaluated). Every batch's inputs, forward, pose and ADD(-S) are queued on
     the device without a host round trip; the per-crop records are read back once at the end (the
@@ -70,14 +71,22 @@ def eval_records(model: KRRN, dataset: PoseDataset, indices: Dict[int, List[int]
     serial order: forward j's pool perms, then get_pose j's point subsets, then forward j+1's.
 
     pose_solver: "pnp" (get_pose, the reference's test loop) or "umeyama" (get_pose_umeyama: the base
-    R / t from the depth-based Umeyama-RANSAC of tools/script/eval.py:151; everything else unchanged)."""
+    R / t from the depth-based Umeyama-RANSAC of tools/script/eval.py:151; everything else unchanged).
+
+    refine: None (the reference's loop), or "icp": the base pose (base_r, base_t) and, with opt_pose, the
+    final pose (base_r, pred_t) are each polished by pose.refine_pose_icp against the crop's cloud on the
+    pose stream before their ADD(-S) and rotation / translation errors (two more launches per batch; the
+    final pose then carries its own refined R). max_dist = icp.DIST_FRAC x the object's diameter."""
     if pose_solver not in ("pnp", "umeyama"):
         raise ValueError(f"pose_solver must be 'pnp' or 'umeyama', got {pose_solver!r}")
+    if refine not in (None, "icp"):
+        raise ValueError(f"refine must be None or 'icp', got {refine!r}")
     solve_pose = get_pose if pose_solver == "pnp" else get_pose_umeyama
     metric = Metric(dataset.sym_obj)
     pending = []
     batches = list(_batches(indices, bs))
     device = torch.device(device)
+    dia = torch.tensor(dataset.diameter, dtype=torch.float32).to(device) if refine else None  # [classes], metres
     main = torch.cuda.current_stream(device)
     side = torch.cuda.Stream(device)   # inputs
     pstr = torch.cuda.Stream(device)   # pose + metric
@@ -118,20 +127,27 @@ def eval_records(model: KRRN, dataset: PoseDataset, indices: Dict[int, List[int]
                 pred_t.record_stream(pstr)
             with torch.cuda.stream(pstr):
                 base_r, base_t = solve_pose({"xyz": xyz}, data)
+                fin_r = base_r
+                if refine:
+                    d = dia[data["cls_id"].reshape(B)]
+                    r0 = base_r
+                    base_r, base_t = refine_pose_icp(r0, base_t.reshape(B, 3), data, diameter=d)
+                    if opt_pose:
+                        fin_r, pred_t = refine_pose_icp(r0, pred_t, data, diameter=d)
                 add_b = add_metric(base_r, base_t.reshape(B, 3), data["model_points"], data["target"],
                                    data["cls_id"], metric.sys)
                 add_f = None
                 if opt_pose:
                     # reg = final = (PnP R, TBase t) (trainer.py:198-201)
-                    add_f = add_metric(base_r, pred_t, data["model_points"], data["target"], data["cls_id"],
+                    add_f = add_metric(fin_r, pred_t, data["model_points"], data["target"], data["cls_id"],
                                        metric.sys)
             pending.append((idx, data["cls_id"], data["target_r"], data["target_t"], base_r, base_t, pred_t, add_b,
-                            add_f, lc))
+                            add_f, lc, fin_r))
     finally:
         model.return_views = views
     main.wait_stream(pstr)
     for p in pending:  # made on the pose stream, read back on the caller's
-        for t in (p[4], p[5], p[7], p[8]):
+        for t in (p[4], p[5], p[7], p[8]) + ((p[6], p[10]) if refine else ()):
             if t is not None:
                 t.record_stream(main)
     if not pending:
@@ -158,7 +174,7 @@ def eval_records(model: KRRN, dataset: PoseDataset, indices: Dict[int, List[int]
     rec[:, _R["r_b"]], rec[:, _R["t_b"]] = rt_errors(base_r, cat(5, 3), tr, tt)
     if opt_pose:
         rec[:, _R["add_f"]] = cat(8, 1).reshape(n).cpu().numpy()
-        rec[:, _R["r_f"]], rec[:, _R["t_f"]] = rt_errors(base_r, cat(6, 3), tr, tt)
+        rec[:, _R["r_f"]], rec[:, _R["t_f"]] = rt_errors(cat(10, 9) if refine else base_r, cat(6, 3), tr, tt)
     return torch.from_numpy(rec)
 
 
@@ -232,11 +248,11 @@ def gather_epoch_records(local: torch.Tensor, shard_sizes: Sequence[int], device
 @torch.no_grad()
 def test_epoch(model: KRRN, dataset: PoseDataset, bs: int = 64, device=None, opt_pose: bool = True,
                criterion=None, world: Optional[int] = None, rank: Optional[int] = None,
-               group=None, pose_solver: str = "pnp") -> Dict[str, object]:
+               group=None, pose_solver: str = "pnp", refine: Optional[str] = None) -> Dict[str, object]:
     """Trainer.test_epoch over `dataset`. world/rank default to the initialised process group
     (1/0 without one). `criterion` enables the per-crop map-loss terms (dis_xyz / dis_mask /
     dis_normal) when the batches carry GT maps; the reference always evaluates it (:167).
-    `pose_solver` as in eval_records."""
+    `pose_solver` and `refine` as in eval_records."""
     device = torch.device(device) if device is not None else next(model.parameters()).device
     if world is None:
         world = dist.get_world_size(group) if dist.is_initialized() else 1
@@ -247,6 +263,8 @@ def test_epoch(model: KRRN, dataset: PoseDataset, bs: int = 64, device=None, opt
     sizes = [dataset.crop_size(i) for i in range(len(dataset))]
     mine = kd.bucket_shard(sizes, world, rank)
     solver = {} if pose_solver == "pnp" else {"pose_solver": pose_solver}  # the default call is unchanged
+    if refine is not None:
+        solver["refine"] = refine
     local = eval_records(model, dataset, mine, bs, device, opt_pose=opt_pose, with_loss=criterion is not None, **solver)
     shard_sizes = [sum(len(v) for v in kd.bucket_shard(sizes, world, r).values()) for r in range(world)]
     allrec = gather_epoch_records(local, shard_sizes, device, group) if world > 1 else local

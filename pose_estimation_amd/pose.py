@@ -19,7 +19,7 @@ from typing import Dict, Optional
 import torch
 
 from .runtime import P, Plan, h2d, ptr
-from . import _lib, umeyama
+from . import _lib, icp, umeyama
 
 NUM_POINTS = 256
 N_HYP = 100
@@ -143,6 +143,46 @@ def add_umeyama_ops(plan: Plan, xyz: torch.Tensor, choose: torch.Tensor, cloud: 
              umeyama.CONFIDENCE, umeyama.MIN_RATIO, ptr(counts), ptr(scale), ptr(R), ptr(t), ptr(inl), ptr(best),
              ptr(mask), B)
     return R, t, inl, dict(scale=scale, src=src, subsets=subsets, hyp_counts=counts, best_hyp=best, mask=mask)
+
+
+def refine_pose_icp(R: torch.Tensor, t: torch.Tensor, data, diameter=None, max_dist=None,
+                    max_iter: int = icp.MAX_ITER, tol: float = icp.TOL, min_pairs: int = icp.MIN_PAIRS,
+                    return_info: bool = False):
+    """(R [B, 3, 3], t [B, 3]) polished by ICP (icp.refine) of data['model_points'] against data['cloud'].
+    Pairs farther apart than max_dist are rejected: icp.DIST_FRAC x `diameter` per crop (a float or a [B]
+    tensor, metres), or an explicit `max_dist`; one of the two is required. The reference has no such step:
+    the defaults are this project's choices (icp.py)."""
+    if not (isinstance(R, torch.Tensor) and isinstance(t, torch.Tensor) and R.is_cuda and t.is_cuda):
+        raise RuntimeError("refine_pose_icp runs on the HIP path only (R / t must be GPU tensors)")
+    if max_dist is None:
+        if diameter is None:
+            raise ValueError("refine_pose_icp needs `diameter` (max_dist = icp.DIST_FRAC x diameter) or `max_dist`")
+        max_dist = icp.DIST_FRAC * (diameter.to(torch.float32) if isinstance(diameter, torch.Tensor)
+                                    else float(diameter))
+    dev = R.device
+    B = R.shape[0]
+    cloud = _dev(data["cloud"].reshape(B, -1, 3), dev, torch.float32)
+    mp = _dev(data["model_points"].reshape(B, -1, 3), dev, torch.float32)
+    return icp.refine(R, t.reshape(B, 3), cloud, mp, max_dist, max_iter, tol, min_pairs, return_info)
+
+
+def add_icp_ops(plan: Plan, R: torch.Tensor, t: torch.Tensor, cloud: torch.Tensor, model: torch.Tensor,
+                max_dist: torch.Tensor, B: int, N: int, M: int, max_iter: int = icp.MAX_ITER, tol: float = icp.TOL,
+                min_pairs: int = icp.MIN_PAIRS):
+    """Append the ICP refinement to a plan (graph-capturable: one launch, no host decision). R [B, 3, 3],
+    t [B, 3], cloud [B, N, 3], model [B, M, 3], max_dist [B]: f32 contiguous device buffers read at run
+    time. Returns (R, t, info) buffers; info holds passes, pairs, rmse, status, nn_idx."""
+    Ro = plan.buf((B, 3, 3))
+    to = plan.buf((B, 3))
+    passes = plan.buf((B,), torch.int32)
+    pairs = plan.buf((B,), torch.int32)
+    rmse = plan.buf((B,))
+    status = plan.buf((B,), torch.int32)
+    nn_idx = plan.buf((B, N), torch.int32)
+    plan.add("krrn_icp_refine_f32", ptr(R), ptr(t), ptr(cloud), N, ptr(model), M, ptr(max_dist), int(max_iter),
+             float(tol), int(min_pairs), ptr(Ro), ptr(to), ptr(passes), ptr(pairs), ptr(rmse), ptr(status),
+             ptr(nn_idx), B)
+    return Ro, to, dict(passes=passes, pairs=pairs, rmse=rmse, status=status, nn_idx=nn_idx)
 
 
 def add_pose_ops(plan: Plan, xyz: torch.Tensor, choose: torch.Tensor, B: int, N: int, xm: torch.Tensor,

@@ -10,7 +10,8 @@ dataset/linemod/batchdataset.py:603-771 (_load_data).
 Prints one JSON line; also times the forward alone over the same batches (inputs prebuilt) so
 the loader + pose + metric share of the epoch is visible.
 
-usage (GPU box): python3 profiles/eval_epoch.py [--frames 1024] [--bs 64] [--out FILE]"""
+usage (GPU box): python3 profiles/eval_epoch.py [--frames 1024] [--bs 64] [--refine icp] [--out FILE]
+--refine icp: the epoch with the ICP pose refinement (evaluate.test_epoch(refine="icp")) switched on."""
 import argparse
 import json
 import os
@@ -33,8 +34,10 @@ def main():
     ap.add_argument("--frames", type=int, default=1024)
     ap.add_argument("--bs", type=int, default=64)
     ap.add_argument("--out", default="")
+    ap.add_argument("--refine", default=None, choices=["icp"])
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
+    kw = {"refine": args.refine} if args.refine else {}
     t = time.time()
     ds = PoseDataset("test", 1000, False, None, 0.0, 8, cls_type="all", num_frames=args.frames, seed=0)
     print(f"synthetic frames: {args.frames} in {time.time() - t:.1f} s", flush=True)
@@ -44,14 +47,14 @@ def main():
     init_weights(m, 0)
     m = m.to(dev).eval()
     t = time.time()
-    test_epoch(m, ds, bs=args.bs, device=dev)  # warm-up: one launch plan per (B, S)
+    test_epoch(m, ds, bs=args.bs, device=dev, **kw)  # warm-up: one launch plan per (B, S)
     torch.cuda.synchronize()
     print(f"warm-up epoch (plan builds) {time.time() - t:.1f} s", flush=True)
     times = []
     for _ in range(3):
         torch.cuda.synchronize()
         t = time.time()
-        res = test_epoch(m, ds, bs=args.bs, device=dev)
+        res = test_epoch(m, ds, bs=args.bs, device=dev, **kw)
         torch.cuda.synchronize()
         times.append(time.time() - t)
         print(f"epoch {times[-1]:.3f} s", flush=True)
@@ -73,7 +76,7 @@ def main():
             fwds.append(time.time() - t)
         fwd = min(fwds)
     line = {"metric": "eval crops/s, evaluate.test_epoch end to end (f2 inputs + forward + get_pose + ADD(-S))",
-            "value": round(len(ds) / ep, 2), "unit": "crops/s", "epoch_s": round(ep, 4), "crops": len(ds),
+            "refine": args.refine, "value": round(len(ds) / ep, 2), "unit": "crops/s", "epoch_s": round(ep, 4), "crops": len(ds),
             "batches": len(batches), "bs": args.bs, "size_hist": hist, "forward_only_s": round(fwd, 4),
             "forward_only_crops_s": round(len(ds) / fwd, 2), "classes": len(ds.objlist),
             "data": "synthetic LineMOD-all frames (640x480 RGB-D, LM_CROP_HIST sizes), random-init HRNet-W18 KRRN",
