@@ -471,6 +471,53 @@ int krrn_choose_points(const unsigned char* mask, int B, int S, int N, const flo
  * them (f32, sqrt(((dx*dx + dy*dy) + dz*dz)), no FMA). n <= 16384. */
 int krrn_fps_f32(const float* pts, int B, int n, int n_samples, int* out_idx, void* stream);
 
+/* Ground-truth map rendering, batched (this project's own definition: the reference unpickles xyz /
+ * normal / region maps made by an offline renderer that is not in its tree, batchdataset.py:200-210). A
+ * z-buffered triangle rasteriser over B crops of one size S. verts f32 [Vtot][3] (model frame, metres),
+ * faces int32 [Ftot][3] (indices into verts), face_range int32 [B][2] = first face, face count of crop b
+ * (a batch may mix objects; count 0 = all background), R f64 [B][9] row-major and t f64 [B][3] (model to
+ * camera), K4 f32 [B][4] = fx fy cx cy, rc int32 [B][2] = rmin, cmin, region_pts f32 [B][NR][3] (model
+ * frame, metres; NR 1..256). All arithmetic in f64, no FMA contraction:
+ *   c_k = ((r0 x + r1 y) + r2 z) + t per vertex; a face with a vertex index outside [0, Vtot) or any
+ *   c_k.z not > 1e-3 is skipped whole (no clipping); u = fx c.x / c.z + cx, v = fy c.y / c.z + cy;
+ *   E(a, b, p) = (b.u - a.u)(p.v - a.v) - (b.v - a.v)(p.u - a.u); A = E(v0, v1, v2), a face with A == 0 or
+ *   not finite is skipped; both windings are drawn. Pixel (x, y) of the crop is sampled at its integer
+ *   coordinates p = (cmin + x, rmin + y) (the loader's xmap / ymap convention, :712-721; not + 0.5) and
+ *   tested against a face iff p lies in the face's bounding box (inclusive): w0 = E(v1, v2, p) / A,
+ *   w1 = E(v2, v0, p) / A, w2 = E(v0, v1, p) / A, covered iff all three >= 0. q_k = w_k / z_k, depth
+ *   z = 1 / ((q0 + q1) + q2) (perspective-correct); the winner is the covering face with the smallest z,
+ *   the lowest face index among equal z. Model coordinate m = z ((q0 vert_0 + q1 vert_1) + q2 vert_2);
+ *   normal = normalize((c1 - c0) x (c2 - c0)), the face's flat unit normal in the camera frame, negated
+ *   if n . c0 > 0 so that it faces the camera (the offline renderer's normals are unknown: a stated
+ *   departure); region = 1 + argmin_j ((dx dx + dy dy) + dz dz) between m and region_pts[b][j], the lowest
+ *   j on ties.
+ * Outputs (must not alias anything): face int32 [B][S*S] (index local to the crop's range, background
+ * -1), depth f32 [B][S*S] (0), coord f32 [B][3][S*S] (metres, 0), normal f32 [B][3][S*S] (0), region int32
+ * [B][S*S] (0); cover_frame u8 [B][H][W] (optional; H, W unused without it): 1 = covered / 0 written at
+ * (rmin + y, cmin + x) only, the obj_mask krrn_crop_inputs_u8 reads with frame[b] = b; the rest of the
+ * frame is not touched. Host checks: null pointer or overlapping buffers KRRN_EARG; S outside 1..480, NR
+ * outside 1..256, B, Vtot < 1, Ftot < 0, or cover_frame with H < S or W < S KRRN_ESHAPE. face_range and rc
+ * are device memory, so the kernel guards them: a negative first face or count is an empty range, a range
+ * is cut at Ftot, and a cover_frame pixel off the frame is not written. One launch, one block per 16x16
+ * tile, no atomics, no workspace: a crop's maps do not depend on the rest of the batch, bit for bit. */
+int krrn_raster_maps_f32(const float* verts, int Vtot, const int* faces, int Ftot, const int* face_range,
+                         const double* R, const double* t, const float* K4, const int* rc, int S,
+                         const float* region_pts, int NR, int B, int* face, float* depth, float* coord,
+                         float* normal, int* region, unsigned char* cover_frame, int H, int W, void* stream);
+
+/* The pointwise masking of batchdataset.py:663-671, 689-694, 755-759 on the maps above. point_mask u8
+ * [B][HW]: the crop's mask of krrn_crop_inputs_u8 with obj_mask = cover_frame (label * depth * cover);
+ * cls int64 [B]; extent, lfborder f64 [B][3]. xyz f32 [B][3][HW] = float((coord - lfborder) / extent)
+ * where the mask is set, else 0; normal is masked in place; region int64 [B][HW] = region_raw masked;
+ * mask f32 [B][HW]; multi_cls_mask int64 [B][HW] = mask * (cls + 1); mask_obj f32 [B][HW] (optional,
+ * needs face) = face >= 0. Departure from the reference: it zeroes xyz element-wise where a coordinate
+ * component is exactly 0 (xyz_map * (coordinate != [0, 0, 0]), :694); here the mask is coverage, so a
+ * surface point on a model-frame axis plane keeps its normalised coordinate. */
+int krrn_gt_maps_finish_f32(const float* coord, const int* region_raw, const int* face,
+                            const unsigned char* point_mask, const long long* cls, const double* extent,
+                            const double* lfborder, int B, int HW, float* xyz, float* normal, long long* region,
+                            float* mask, long long* multi_cls_mask, float* mask_obj, void* stream);
+
 /* BPnP forward (lib/network/dnn/BPnP.py:43-44, cv2.solvePnP(SOLVEPNP_ITERATIVE,
  * useExtrinsicGuess=True)): Levenberg-Marquardt on sum_i ||pi(z_i; y) - x_i||^2 per crop, f64,
  * from y_init. pts2d [B][n][2] pixels; pts3d [n][3] shared (z_per_crop = 0) or [B][n][3];

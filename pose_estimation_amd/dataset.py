@@ -16,9 +16,13 @@ mode 'eval': `segnet_results/XX_label/NNNN_label.png` == 255, :197-244), and
 `models/obj_XX.ply` (ascii PLY vertices / 1000, ply_vtx :841-852; 2600 random model points at
 test time, :700-704). Only the crop sizes (from gt.yml's boxes) are read up front; each batch
 reads and decodes its frames (a thread pool) and stages them to the GPU. Not read: the per-frame
-GT-map pickles (xyz / normal / region, :202-212) — they feed only the logged loss terms and the
-`mask_obj` factor of the point mask, so here the mask is mask_label * mask_depth (documented
-deviation) and the loss keys are absent.
+GT-map pickles (xyz / normal / region, :202-212) and fps_64.pkl (:105), which come from an offline
+renderer that neither the reference's tree nor a stock Linemod_preprocessed holds. They feed the
+logged loss terms and the `mask_obj` factor of the point mask. By default the mask is therefore
+mask_label * mask_depth (documented deviation) and the loss keys are absent; with `gt_maps=True` the
+maps are rendered on the GPU from the PLY's faces, the GT pose and K (raster.py), the mask is the
+reference's label * obj * depth, and every batch carries xyz, normal, region, mask, multi_cls_mask,
+mask_obj, region_point, coordinate_choosed and depth_render.
 
 `root=None` (the default; no LineMOD data ships with the reference and there is no network)
 serves seeded synthetic 640x480 RGB-D frames built like the real ones (an object mask inside a
@@ -43,6 +47,7 @@ import torch
 
 from . import _lib
 from .config import CONFIG, LM_OBJLIST, OBJ_DICT, SYM_OBJ, models_info
+from .raster import N_REGIONS, finish_maps, region_points, render_maps
 from .runtime import P, h2d, ptr
 from .synthetic import LM_K, rand_rotation
 
@@ -222,6 +227,42 @@ def ply_vtx(path: str) -> np.ndarray:
         return np.array([np.float32(f.readline().split()[:3]) for _ in range(n)], dtype=np.float32)
 
 
+def ply_faces(path: str) -> np.ndarray:
+    """Triangles of an ascii PLY, int32 [n, 3]: the `element face` block's `3 i j k` lines (whatever
+    follows the three indices on a line, e.g. per-face colours, is ignored). A PLY with `element face 0`
+    gives [0, 3]; a face that is not a triangle raises."""
+    with open(path) as f:
+        if f.readline().strip() != "ply":
+            raise ValueError(f"{path}: not a PLY file")
+        fmt, elems = None, []
+        while True:
+            line = f.readline()
+            if not line:
+                raise ValueError(f"{path}: no end_header")
+            tok = line.split()
+            if tok[:1] == ["format"]:
+                fmt = tok[1]
+            if tok[:1] == ["element"]:
+                elems.append((tok[1], int(tok[2])))
+            if line.strip() == "end_header":
+                break
+        if fmt != "ascii":
+            raise ValueError(f"{path}: only ascii PLY is read (format {fmt})")
+        for name, n in elems:  # the elements' lines follow the header in the order declared
+            if name != "face":
+                for _ in range(n):
+                    f.readline()
+                continue
+            out = np.zeros((n, 3), dtype=np.int32)
+            for i in range(n):
+                tok = f.readline().split()
+                if len(tok) < 4 or int(tok[0]) != 3:
+                    raise ValueError(f"{path}: face {i} is not a triangle ('{' '.join(tok)}')")
+                out[i] = [int(tok[1]), int(tok[2]), int(tok[3])]
+            return out
+    return np.zeros((0, 3), dtype=np.int32)
+
+
 def _read_lines(p: str) -> List[str]:
     with open(p) as f:
         return [ln.strip() for ln in f if ln.strip()]
@@ -231,11 +272,15 @@ class _LinemodTree:
     """Index of a LineMOD tree (module doc): one entry per (object, image id) of the split, its GT
     pose and detection box from gt.yml; frames are read on demand."""
 
-    def __init__(self, root: str, mode: str, objlist: Sequence[int], n_model_pts: int, seed: int):
+    def __init__(self, root: str, mode: str, objlist: Sequence[int], n_model_pts: int, seed: int,
+                 meshes: bool = False):
         import yaml
         self.root, self.mode = root, mode
         self.items: List[Dict[str, object]] = []
         self.model_points: Dict[int, np.ndarray] = {}
+        # meshes: per object the full vertex set (metres) and the triangles, for GT-map rendering; apart
+        # from the n_model_pts subsample below, which ADD(-S) uses
+        self.mesh: Dict[int, Tuple[np.ndarray, np.ndarray]] = {}
         rng = np.random.default_rng(seed)
         split = "train.txt" if mode == "train" else "test.txt"
         for obj in objlist:
@@ -251,6 +296,14 @@ class _LinemodTree:
                                    "t": np.array(e["cam_t_m2c"], np.float64) / 1000.0,
                                    "bbox": [float(v) for v in e["obj_bb"]]})
             pts = ply_vtx(os.path.join(root, "models", f"obj_{obj:02d}.ply")) / 1000.0
+            if meshes:
+                tri = ply_faces(os.path.join(root, "models", f"obj_{obj:02d}.ply"))
+                if len(tri) == 0:
+                    raise ValueError(f"gt_maps=True renders the GT maps from the mesh, but obj_{obj:02d}.ply has no "
+                                     "faces (element face 0)")
+                if tri.min() < 0 or tri.max() >= len(pts):
+                    raise ValueError(f"obj_{obj:02d}.ply: a face index lies outside its {len(pts)} vertices")
+                self.mesh[obj] = (pts.astype(np.float32), tri)
             if len(pts) < n_model_pts:
                 # the reference's random.sample(range(len(pts)), len(pts) - num_pt_mesh_large) raises here
                 # too (batchdataset.py:700-704): every crop's ADD(-S) runs over exactly n_model_pts points
@@ -283,13 +336,18 @@ class _LinemodTree:
 class PoseDataset(torch.utils.data.Dataset):
     """The reference's constructor signature (batchdataset.py:34); `root` = a LineMOD tree, or
     None for synthetic frames (module doc). Eval only: add_noise / noise_trans / num_kps are
-    accepted and unused."""
+    accepted and unused. gt_maps=True also serves the per-pixel ground truth, rendered from the tree's
+    meshes (needs a tree whose PLYs have faces; ValueError otherwise); the default changes nothing."""
 
     def __init__(self, mode: str = "test", num_point: int = 1000, add_noise: bool = False, root: Optional[str] = None,
                  noise_trans: float = 0.0, num_kps: int = 8, cls_type: Optional[str] = None, cfg=CONFIG,
                  num_frames: int = 256, seed: int = 0, sizes: Optional[Sequence[int]] = None,
-                 n_model_pts: int = 2600, io_threads: int = 8):
+                 n_model_pts: int = 2600, io_threads: int = 8, gt_maps: bool = False):
         self.mode, self.num_point, self.cfg, self.root = mode, num_point, cfg, root
+        self.gt_maps = bool(gt_maps)
+        if self.gt_maps and root is None:
+            raise ValueError("gt_maps=True renders the GT maps from the objects' meshes and needs a LineMOD tree "
+                             "(root=None serves synthetic frames, which have no mesh)")
         if cls_type in (None, "all"):
             self.objlist = list(LM_OBJLIST)
         else:
@@ -299,7 +357,7 @@ class PoseDataset(torch.utils.data.Dataset):
         self.diameter = [info[o]["diameter"] / 1000.0 for o in self.objlist]
         self.io_threads = io_threads
         if root is not None:
-            self.tree = _LinemodTree(root, mode, self.objlist, n_model_pts, seed)
+            self.tree = _LinemodTree(root, mode, self.objlist, n_model_pts, seed, meshes=self.gt_maps)
             self.frames_np = None
             self.boxes = [get_square_bbox(it["bbox"]) for it in self.tree.items]
         else:
@@ -307,6 +365,7 @@ class PoseDataset(torch.utils.data.Dataset):
             self.frames_np = synthetic_frames(num_frames, seed, self.objlist, sizes=sizes)
             self.boxes = [get_square_bbox([float(v) for v in bb]) for bb in self.frames_np["bbox"]]
         self._dev_frames: Dict[str, Dict[str, torch.Tensor]] = {}
+        self._dev_mesh: Dict[str, Dict[str, object]] = {}
         self._seed: Dict[str, torch.Tensor] = {}
         self._calls = 0
 
@@ -350,8 +409,40 @@ class PoseDataset(torch.utils.data.Dataset):
         return (int(f["obj_id"][i]), f["target_r"][i].astype(np.float64), f["target_t"][i].astype(np.float64),
                 f["model_points"][i])
 
+    def _mesh_for(self, device) -> Dict[str, object]:
+        """The objects' meshes on `device`, concatenated (faces index the concatenated vertices), each
+        object's face range, its 64 FPS region points (metres, from vertex 0: sample_model.py:33-46) and its
+        `region_point` rows (a [0, 0, 0] row, then the normalised points, batchdataset.py:723-728). Built once
+        per device."""
+        key = str(device)
+        if key not in self._dev_mesh:
+            info = models_info()
+            vs, fs, frange, v0, f0 = [], [], {}, 0, 0
+            for obj in self.objlist:
+                v, f = self.tree.mesh[obj]
+                vs.append(v)
+                fs.append(f + v0)
+                frange[obj] = (f0, len(f))
+                v0, f0 = v0 + len(v), f0 + len(f)
+            region, region_point = {}, {}
+            for obj in self.objlist:
+                pts = region_points(h2d(torch.from_numpy(self.tree.mesh[obj][0]), device), N_REGIONS)
+                lf, ext = np.array(info[obj]["min"]) / 1000.0, np.array(info[obj]["size"]) / 1000.0
+                nrm = (pts.cpu().numpy().astype(np.float64) - lf) / ext
+                region[obj] = pts
+                region_point[obj] = h2d(torch.from_numpy(np.concatenate([np.zeros((1, 3)), nrm]).astype(np.float32)),
+                                        device)
+            self._dev_mesh[key] = {"verts": h2d(torch.from_numpy(np.concatenate(vs)), device),
+                                   "faces": h2d(torch.from_numpy(np.concatenate(fs).astype(np.int32)), device),
+                                   "range": frange, "region": region, "region_point": region_point}
+        return self._dev_mesh[key]
+
     def batch(self, indices: Sequence[int], device) -> Dict[str, torch.Tensor]:
-        """The eval keys of batchdataset.py:730-771 for `indices` (one crop size), collated."""
+        """The eval keys of batchdataset.py:730-771 for `indices` (one crop size), collated. With gt_maps
+        also the per-pixel GT of :755-759 (xyz, normal, region, mask, multi_cls_mask), mask_obj,
+        region_point, coordinate_choosed and depth_render: the object's mesh is rendered under the GT pose
+        (raster.render_maps), its coverage is the point mask's `mask_obj` factor (:667-670), and
+        raster.finish_maps applies the loader's masking."""
         device = torch.device(device)
         idx = list(indices)
         if self.tree is not None:
@@ -362,14 +453,22 @@ class PoseDataset(torch.utils.data.Dataset):
             fidx = idx
         K4 = torch.tensor([[LM_K[0, 0], LM_K[1, 1], LM_K[0, 2], LM_K[1, 2]]] * len(idx), dtype=torch.float32)
         self._calls += 1
-        out = build_inputs(fr, fidx, [self.boxes[i] for i in idx], self.num_point, K4, self._seed_for(device),
-                           stream_id=self._calls)
-        info = models_info()
+        boxes = [self.boxes[i] for i in idx]
         metas = [self._meta(i) for i in idx]
-        ext = [np.array(info[m[0]]["size"]) / 1000.0 for m in metas]
-        lfb = [np.array(info[m[0]]["min"]) / 1000.0 for m in metas]
         R64 = torch.from_numpy(np.stack([m[1] for m in metas]))
         t64 = torch.from_numpy(np.stack([m[2] for m in metas]))
+        maps = None
+        if self.gt_maps:
+            mesh = self._mesh_for(device)
+            maps = render_maps(mesh["verts"], mesh["faces"],
+                               torch.tensor([mesh["range"][m[0]] for m in metas], dtype=torch.int32), R64, t64, K4,
+                               boxes, torch.stack([mesh["region"][m[0]] for m in metas]),
+                               frame_hw=tuple(fr["depth"].shape[1:]))
+        out = build_inputs(fr, fidx, boxes, self.num_point, K4, self._seed_for(device), stream_id=self._calls,
+                           obj_mask=maps["cover_frame"] if maps is not None else None)
+        info = models_info()
+        ext = [np.array(info[m[0]]["size"]) / 1000.0 for m in metas]
+        lfb = [np.array(info[m[0]]["min"]) / 1000.0 for m in metas]
         # every object keeps exactly num_pt_mesh_large model points (_LinemodTree / synthetic_frames), so
         # a batch mixing objects stacks them without cutting any crop's ADD(-S) point set
         assert len({len(m[3]) for m in metas}) == 1, [len(m[3]) for m in metas]
@@ -385,6 +484,17 @@ class PoseDataset(torch.utils.data.Dataset):
             "target": (mp.double() @ R64.transpose(1, 2) + t64[:, None]).float(),
         }
         out.update({k: h2d(v, device) for k, v in host.items()})
+        if maps is not None:
+            B, N, S = len(idx), self.num_point, boxes[0][1] - boxes[0][0]
+            out.update(finish_maps(maps, out["point_mask"], out["cls_id"], out["extent"], out["lfborder"]))
+            out["region_point"] = torch.stack([mesh["region_point"][m[0]] for m in metas])
+            out["depth_render"] = maps["depth"]
+            # coordinate_choosed (:688): the rendered model coordinates at `choose`, columns 3..5 of the packed
+            # [cloud | xyz | normal] gather
+            p9 = torch.empty((B, N, 9), dtype=torch.float32, device=device)
+            _lib.call("krrn_points_gather_f32", ptr(out["cloud"]), ptr(maps["coord"]), ptr(out["normal"]),
+                      ptr(out["choose"]), B, N, S, S, ptr(p9), P(torch.cuda.current_stream(device).cuda_stream))
+            out["coordinate_choosed"] = p9[:, :, 3:6]
         return out
 
     def __getitem__(self, i: int) -> Dict[str, torch.Tensor]:

@@ -3,8 +3,9 @@
 ranks.
 
 Per batch of equal-size crops (BucketBatcher): the GPU-built inputs (PoseDataset.batch), one
-KRRN forward, the eval-time KRRNLoss map terms per crop when the batch carries GT maps
-(krrn_map_losses_crop_f32: the reference's batch-size-1 loop adds each crop's own losses,
+KRRN forward, the eval-time KRRNLoss map terms per crop when the batch carries GT maps (a
+PoseDataset(root, gt_maps=True) renders them from the tree's meshes on the input stream;
+krrn_map_losses_crop_f32: the reference's batch-size-1 loop adds each crop's own losses,
 trainer.py:180-182), get_pose (PnP-RANSAC, the "base" R / t), the TBase translation (the "reg" /
 "final" t) and ADD(-S) / rotation / translation errors for the whole batch in one launch
 (metric.cal_dis_batch). Each crop leaves one f64 record (REC fields below).
@@ -251,7 +252,9 @@ def test_epoch(model: KRRN, dataset: PoseDataset, bs: int = 64, device=None, opt
                group=None, pose_solver: str = "pnp", refine: Optional[str] = None) -> Dict[str, object]:
     """Trainer.test_epoch over `dataset`. world/rank default to the initialised process group
     (1/0 without one). `criterion` enables the per-crop map-loss terms (dis_xyz / dis_mask /
-    dis_normal) when the batches carry GT maps; the reference always evaluates it (:167).
+    dis_normal) when the batches carry GT maps, i.e. for a PoseDataset built with gt_maps=True (a
+    stock LineMOD tree is enough: the maps are rendered from its PLYs); without them the columns stay
+    0. The reference always evaluates it (:167).
     `pose_solver` and `refine` as in eval_records."""
     device = torch.device(device) if device is not None else next(model.parameters()).device
     if world is None:
