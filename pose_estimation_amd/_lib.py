@@ -11,9 +11,21 @@ import os
 import re
 import threading
 
-import torch  # noqa: F401  (loads the HIP runtime libamdhip64.so.7 before our library)
+import torch  # loads the HIP runtime libamdhip64.so.7 before our library
 
 from . import knobs
+
+P = ctypes.c_void_p
+
+
+def ptr(t) -> P:
+    return P(t.data_ptr()) if t is not None else P(0)
+
+
+def stream_ptr(device=None) -> P:
+    """The current torch stream of `device` (None: the current device), as the `hipStream_t` argument."""
+    return P(torch.cuda.current_stream(device).cuda_stream)
+
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # KRRN_HIP_LIB: an alternative build of the same library (kernel-variant experiments)

@@ -18,15 +18,11 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .runtime import P, ptr
+from .runtime import ptr, stream_ptr
 
 LM_ITERS = 50
 RANSAC_THR = 3.0  # reprojectionError of the reference's solvePnPRansac (BPnP.py:36-38)
 PNP_MAX_P = 1024  # kPnpMaxP of krrn_pnp_ransac_f32 (csrc/pnp.hip): larger sets are subsampled
-
-
-def _stream(dev):
-    return P(torch.cuda.current_stream(dev).cuda_stream)
 
 
 def _check_inputs(pts2d, pts3d, K):
@@ -77,7 +73,7 @@ def solve(pts2d: torch.Tensor, pts3d: torch.Tensor, K: torch.Tensor, ini_pose: t
     y = torch.empty(bs, 6, dtype=torch.float32, device=dev)
     cost = torch.empty(bs, dtype=torch.float32, device=dev)
     _lib.call("krrn_bpnp_solve_f32", ptr(x), ptr(z), per_crop, ptr(Kc), ptr(y0), ptr(R0), bs, n, iters, ptr(y),
-              ptr(cost), _stream(dev))
+              ptr(cost), stream_ptr(dev))
     return (y, cost) if return_cost else y
 
 
@@ -95,7 +91,7 @@ def backward(pts2d, P_6d, pts3d, K, grad_output):
     gK = torch.empty(3, 3, dtype=torch.float32, device=dev)
     ws = torch.empty(bs * (3 * n + 9), dtype=torch.float64, device=dev)
     _lib.call("krrn_bpnp_backward_f32", ptr(x), ptr(y), ptr(z), per_crop, ptr(Kc), ptr(g), bs, n, ptr(gx), ptr(gz),
-              ptr(gK), ptr(ws), _stream(dev))
+              ptr(gK), ptr(ws), stream_ptr(dev))
     return gx.to(pts2d.dtype), gz.to(pts3d.dtype), gK.to(K.dtype)
 
 

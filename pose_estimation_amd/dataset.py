@@ -48,7 +48,7 @@ import torch
 from . import _lib
 from .config import CONFIG, LM_OBJLIST, OBJ_DICT, SYM_OBJ, models_info
 from .raster import N_REGIONS, finish_maps, region_points, render_maps
-from .runtime import P, h2d, ptr
+from .runtime import h2d, ptr, stream_ptr
 from .synthetic import LM_K, rand_rotation
 
 # batchdataset.py:823
@@ -187,7 +187,7 @@ def build_inputs(frames: Dict[str, torch.Tensor], frame_idx: Sequence[int], boxe
     rc = h2d(torch.tensor([[b[0], b[2]] for b in boxes], dtype=torch.int32), dev)
     img = torch.empty((B, 3, S, S), dtype=torch.float32, device=dev)
     mask = torch.empty((B, S * S), dtype=torch.uint8, device=dev)
-    st = P(torch.cuda.current_stream(dev).cuda_stream)
+    st = stream_ptr(dev)
     _lib.call("krrn_crop_inputs_u8", ptr(rgb), ptr(depth), ptr(ml), ptr(obj_mask), F, H, W, ptr(fi), ptr(rc), B, S,
               ptr(img), ptr(mask), st)
     N = num_point
@@ -493,7 +493,7 @@ class PoseDataset(torch.utils.data.Dataset):
             # [cloud | xyz | normal] gather
             p9 = torch.empty((B, N, 9), dtype=torch.float32, device=device)
             _lib.call("krrn_points_gather_f32", ptr(out["cloud"]), ptr(maps["coord"]), ptr(out["normal"]),
-                      ptr(out["choose"]), B, N, S, S, ptr(p9), P(torch.cuda.current_stream(device).cuda_stream))
+                      ptr(out["choose"]), B, N, S, S, ptr(p9), stream_ptr(device))
             out["coordinate_choosed"] = p9[:, :, 3:6]
         return out
 

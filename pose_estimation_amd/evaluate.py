@@ -24,6 +24,7 @@ the ADD(-S) AUC of Metric.cal_auc (metric.py:38-65) is reported per object and o
 from __future__ import annotations
 
 import copy
+from collections import namedtuple
 from typing import Dict, List, Optional, Sequence
 
 import numpy as np
@@ -46,6 +47,9 @@ _KEYS = ("all_num", "obj_num", "succ_base_rt", "dis_base_rt", "succ_base_r", "di
 # per-crop record (f64)
 REC = ("crop", "cls", "add_b", "r_b", "t_b", "add_f", "r_f", "t_f", "l_xyz", "l_mask", "l_normal", "valid")
 _R = {k: i for i, k in enumerate(REC)}
+# what one evaluated batch leaves on the device until the epoch's single read-back (idx: its crop indices, on
+# the host; pred_t / add_f are None without opt_pose, lc without GT maps)
+_Batch = namedtuple("_Batch", "idx cls_id target_r target_t base_r base_t pred_t fin_r add_b add_f lc")
 
 
 def _batches(buckets: Dict[int, List[int]], bs: int):
@@ -142,13 +146,13 @@ def eval_records(model: KRRN, dataset: PoseDataset, indices: Dict[int, List[int]
                     # reg = final = (PnP R, TBase t) (trainer.py:198-201)
                     add_f = add_metric(fin_r, pred_t, data["model_points"], data["target"], data["cls_id"],
                                        metric.sys)
-            pending.append((idx, data["cls_id"], data["target_r"], data["target_t"], base_r, base_t, pred_t, add_b,
-                            add_f, lc, fin_r))
+            pending.append(_Batch(idx, data["cls_id"], data["target_r"], data["target_t"], base_r, base_t, pred_t,
+                                  fin_r, add_b, add_f, lc))
     finally:
         model.return_views = views
     main.wait_stream(pstr)
     for p in pending:  # made on the pose stream, read back on the caller's
-        for t in (p[4], p[5], p[7], p[8]) + ((p[6], p[10]) if refine else ()):
+        for t in (p.base_r, p.base_t, p.add_b, p.add_f) + ((p.pred_t, p.fin_r) if refine else ()):
             if t is not None:
                 t.record_stream(main)
     if not pending:
@@ -156,26 +160,24 @@ def eval_records(model: KRRN, dataset: PoseDataset, indices: Dict[int, List[int]
     # one read-back and one vectorised host pass for the whole epoch: per batch, the rotation /
     # translation errors' six small copies and ~60 CPU ops ran after the GPU had drained (a serial
     # host tail of ~1 ms per batch); every quantity is per crop, so the values are the same
-    cat = lambda k, w: torch.cat([p[k].reshape(len(p[0]), w) for p in pending])  # noqa: E731
-    n = sum(len(p[0]) for p in pending)
+    cat = lambda k, w: torch.cat([getattr(p, k).reshape(len(p.idx), w) for p in pending])  # noqa: E731
+    n = sum(len(p.idx) for p in pending)
     rec = np.zeros((n, len(REC)), dtype=np.float64)
-    rec[:, _R["crop"]] = np.concatenate([np.asarray(p[0], dtype=np.float64) for p in pending])
-    rec[:, _R["cls"]] = cat(1, 1).reshape(n).cpu().numpy()
+    rec[:, _R["crop"]] = np.concatenate([np.asarray(p.idx, dtype=np.float64) for p in pending])
+    rec[:, _R["cls"]] = cat("cls_id", 1).reshape(n).cpu().numpy()
     rec[:, _R["valid"]] = 1.0
     o = 0
     for p in pending:
-        if p[9] is not None:
-            lcn = p[9].cpu().numpy()
-            rec[o:o + len(p[0]), _R["l_xyz"]] = lcn[:, 0]
-            rec[o:o + len(p[0]), _R["l_normal"]] = lcn[:, 1]
-            rec[o:o + len(p[0]), _R["l_mask"]] = lcn[:, 3]
-        o += len(p[0])
-    base_r, tr, tt = cat(4, 9), cat(2, 9), cat(3, 3)
-    rec[:, _R["add_b"]] = cat(7, 1).reshape(n).cpu().numpy()
-    rec[:, _R["r_b"]], rec[:, _R["t_b"]] = rt_errors(base_r, cat(5, 3), tr, tt)
+        if p.lc is not None:
+            rec[o:o + len(p.idx), [_R["l_xyz"], _R["l_normal"], _R["l_mask"]]] = p.lc.cpu().numpy()[:, [0, 1, 3]]
+        o += len(p.idx)
+    base_r, tr, tt = cat("base_r", 9), cat("target_r", 9), cat("target_t", 3)
+    rec[:, _R["add_b"]] = cat("add_b", 1).reshape(n).cpu().numpy()
+    rec[:, _R["r_b"]], rec[:, _R["t_b"]] = rt_errors(base_r, cat("base_t", 3), tr, tt)
     if opt_pose:
-        rec[:, _R["add_f"]] = cat(8, 1).reshape(n).cpu().numpy()
-        rec[:, _R["r_f"]], rec[:, _R["t_f"]] = rt_errors(cat(10, 9) if refine else base_r, cat(6, 3), tr, tt)
+        rec[:, _R["add_f"]] = cat("add_f", 1).reshape(n).cpu().numpy()
+        fin_r = cat("fin_r", 9) if refine else base_r
+        rec[:, _R["r_f"]], rec[:, _R["t_f"]] = rt_errors(fin_r, cat("pred_t", 3), tr, tt)
     return torch.from_numpy(rec)
 
 
@@ -265,10 +267,8 @@ def test_epoch(model: KRRN, dataset: PoseDataset, bs: int = 64, device=None, opt
         raise ValueError(f"rank {rank} outside world {world}")
     sizes = [dataset.crop_size(i) for i in range(len(dataset))]
     mine = kd.bucket_shard(sizes, world, rank)
-    solver = {} if pose_solver == "pnp" else {"pose_solver": pose_solver}  # the default call is unchanged
-    if refine is not None:
-        solver["refine"] = refine
-    local = eval_records(model, dataset, mine, bs, device, opt_pose=opt_pose, with_loss=criterion is not None, **solver)
+    local = eval_records(model, dataset, mine, bs, device, opt_pose=opt_pose, with_loss=criterion is not None,
+                         pose_solver=pose_solver, refine=refine)
     shard_sizes = [sum(len(v) for v in kd.bucket_shard(sizes, world, r).values()) for r in range(world)]
     allrec = gather_epoch_records(local, shard_sizes, device, group) if world > 1 else local
     metric = Metric(dataset.sym_obj)

@@ -9,7 +9,7 @@ from __future__ import annotations
 import torch
 
 from . import _lib
-from .runtime import P, ptr
+from .runtime import ptr, stream_ptr
 
 
 def farthest_point_sampling(points: torch.Tensor, n_samples: int) -> torch.Tensor:
@@ -19,6 +19,6 @@ def farthest_point_sampling(points: torch.Tensor, n_samples: int) -> torch.Tenso
     pts = (points[None] if single else points).to(torch.float32).contiguous()
     B, n, _ = pts.shape
     out = torch.empty((B, n_samples), dtype=torch.int32, device=pts.device)
-    _lib.call("krrn_fps_f32", ptr(pts), B, n, n_samples, ptr(out), P(torch.cuda.current_stream(pts.device).cuda_stream))
+    _lib.call("krrn_fps_f32", ptr(pts), B, n, n_samples, ptr(out), stream_ptr(pts.device))
     out = out.long()
     return out[0] if single else out

@@ -22,8 +22,7 @@ from typing import Union
 
 import torch
 
-from .runtime import P, ptr
-from . import _lib
+from .runtime import Immediate, ptr
 
 MAX_ITER = 20        # updates at most (max_iter + 1 passes); the kernel allows 0 .. 64
 TOL = 1e-4           # relative change of the mean squared pair distance that counts as converged
@@ -43,26 +42,31 @@ def dist_tensor(max_dist: Union[float, torch.Tensor], B: int, device) -> torch.T
     return torch.full((B,), float(max_dist), dtype=torch.float32, device=device)
 
 
+def refine_step(ctx, R0: torch.Tensor, t0: torch.Tensor, cloud: torch.Tensor, model: torch.Tensor,
+                max_dist: torch.Tensor, B: int, N: int, M: int, max_iter: int = MAX_ITER, tol: float = TOL,
+                min_pairs: int = MIN_PAIRS, with_nn: bool = True):
+    """The krrn_icp_refine_f32 launch, stated once, on `ctx` (a runtime.Plan or runtime.Immediate). R0 [B, 3, 3],
+    t0 [B, 3], cloud [B, N, 3], model [B, M, 3], max_dist [B]: f32 contiguous device tensors. Returns (R, t, info)
+    buffers; without `with_nn` the kernel gets a null nn_idx and info["nn_idx"] is None."""
+    R = ctx.buf((B, 3, 3))
+    t = ctx.buf((B, 3))
+    passes = ctx.buf((B,), torch.int32)
+    pairs = ctx.buf((B,), torch.int32)
+    rmse = ctx.buf((B,))
+    status = ctx.buf((B,), torch.int32)
+    nn_idx = ctx.buf((B, N), torch.int32) if with_nn else None
+    ctx.add("krrn_icp_refine_f32", ptr(R0), ptr(t0), ptr(cloud), N, ptr(model), M, ptr(max_dist), int(max_iter),
+            float(tol), int(min_pairs), ptr(R), ptr(t), ptr(passes), ptr(pairs), ptr(rmse), ptr(status), ptr(nn_idx), B)
+    return R, t, {"passes": passes, "pairs": pairs, "rmse": rmse, "status": status, "nn_idx": nn_idx}
+
+
 def solve(R0: torch.Tensor, t0: torch.Tensor, cloud: torch.Tensor, model: torch.Tensor, max_dist: torch.Tensor,
           max_iter: int = MAX_ITER, tol: float = TOL, min_pairs: int = MIN_PAIRS, with_nn: bool = True):
     """f32 contiguous GPU tensors R0 [B, 3, 3], t0 [B, 3], cloud [B, N, 3], model [B, M, 3], max_dist [B]
     -> (R, t, info) device buffers; info["nn_idx"] is None without `with_nn`."""
-    dev = cloud.device
     B, N, _ = cloud.shape
-    M = model.shape[1]
-    R = torch.empty((B, 3, 3), dtype=torch.float32, device=dev)
-    t = torch.empty((B, 3), dtype=torch.float32, device=dev)
-    passes = torch.empty((B,), dtype=torch.int32, device=dev)
-    pairs = torch.empty((B,), dtype=torch.int32, device=dev)
-    rmse = torch.empty((B,), dtype=torch.float32, device=dev)
-    status = torch.empty((B,), dtype=torch.int32, device=dev)
-    nn_idx = torch.empty((B, N), dtype=torch.int32, device=dev) if with_nn else None
-    stream = P(torch.cuda.current_stream(dev).cuda_stream)
-    _lib.check(_lib.lib().krrn_icp_refine_f32(ptr(R0), ptr(t0), ptr(cloud), N, ptr(model), M, ptr(max_dist),
-                                              int(max_iter), float(tol), int(min_pairs), ptr(R), ptr(t), ptr(passes),
-                                              ptr(pairs), ptr(rmse), ptr(status), ptr(nn_idx), B, stream),
-               "krrn_icp_refine_f32")
-    return R, t, {"passes": passes, "pairs": pairs, "rmse": rmse, "status": status, "nn_idx": nn_idx}
+    return refine_step(Immediate(cloud.device), R0, t0, cloud, model, max_dist, B, N, model.shape[1], max_iter, tol,
+                       min_pairs, with_nn)
 
 
 def refine(R: torch.Tensor, t: torch.Tensor, cloud: torch.Tensor, model_points: torch.Tensor,

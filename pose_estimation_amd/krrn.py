@@ -41,7 +41,7 @@ from .fusion import FEAT_SID, FusionNetLite, build_fusion_plan, emit_fusion_clou
 from .hrnet import _Builder, build_hrnet, build_hrnet_plan
 from .ops import Act, pad4
 from .posenet import PoseNet, build_tbase_plan, emit_tbase_level1
-from .runtime import Late, Plan, add_conv, h2d, ptr
+from .runtime import Late, Plan, RngStream, add_conv, h2d, ptr
 
 # the wide head's final 1x1 conv (xyz_final, K = 128) on split-bf16 operands (f32 accuracy,
 # krrn_conv1x1_nchw_x3_f32) instead of f32 MFMAs
@@ -172,7 +172,7 @@ class KRRNPlan:
             # krrn_randperm_i32(seed, sid, n, m, 1) launch): ~19 us instead of ~95 us of
             # back-to-back single-block sorts at the head of the fusion
             cnt = len(self.perm_sizes)
-            sids = (ctypes.c_uint * cnt)(*range(cnt))
+            sids = (ctypes.c_uint * cnt)(*RngStream.POOL)
             ns = (ctypes.c_int * cnt)(*[n for _, n, _ in self.perm_sizes])
             ms = (ctypes.c_int * cnt)(*[m for _, _, m in self.perm_sizes])
             outs = (ctypes.c_void_p * cnt)(*[self.perms[k].data_ptr() for k, _, _ in self.perm_sizes])

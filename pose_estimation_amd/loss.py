@@ -21,16 +21,12 @@ import torch
 
 from . import _lib
 from .config import CONFIG, SYM_OBJ
-from .runtime import P, ptr
-
-
-def _stream(dev) -> P:
-    return P(torch.cuda.current_stream(dev).cuda_stream)
+from .runtime import ptr, stream_ptr
 
 
 def _ws_size(fn: str, a: int, b: int) -> int:
     n = ctypes.c_longlong(0)
-    _lib.check(getattr(_lib.lib(), fn)(a, b, ctypes.byref(n)), fn)
+    _lib.call(fn, a, b, ctypes.byref(n))
     return int(n.value)
 
 
@@ -59,10 +55,10 @@ def map_losses(pred: Dict[str, torch.Tensor], gt: Dict[str, torch.Tensor], per_c
     out = torch.empty(8, dtype=torch.float64, device=dev)
     _lib.call("krrn_map_losses_f32", ptr(_f32(xyz, dev)), ptr(_f32(gt["xyz"], dev)), ptr(_f32(pred["normal"], dev)),
               ptr(_f32(gt["normal"], dev)), ptr(region), region.shape[1], ptr(region_gt), ptr(mask), mask.shape[1],
-              ptr(mask_gt), B, HW, ptr(ws), ptr(out), _stream(dev))
+              ptr(mask_gt), B, HW, ptr(ws), ptr(out), stream_ptr(dev))
     if per_crop:
         oc = torch.empty((B, 8), dtype=torch.float64, device=dev)
-        _lib.call("krrn_map_losses_crop_f32", ptr(ws), B, HW, ptr(oc), _stream(dev))
+        _lib.call("krrn_map_losses_crop_f32", ptr(ws), B, HW, ptr(oc), stream_ptr(dev))
         return oc
     return out
 
@@ -77,7 +73,7 @@ def pose_loss(target_r: torch.Tensor, pred_t: torch.Tensor, target: torch.Tensor
     out = torch.empty(1, dtype=torch.float64, device=dev)
     _lib.call("krrn_pose_loss_f32", ptr(_f32(target_r, dev)), ptr(_f32(pred_t.reshape(B, 3), dev)),
               ptr(_f32(target, dev)), ptr(_f32(model_points, dev)), ptr(_i64(cls_id.reshape(B), dev)), ptr(sym),
-              len(sym_list), B, Pn, ptr(ws), ptr(out), _stream(dev))
+              len(sym_list), B, Pn, ptr(ws), ptr(out), stream_ptr(dev))
     return out[0]
 
 

@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .runtime import P, h2d, ptr
+from .runtime import h2d, ptr, stream_ptr
 
 
 def add_metric(pred_r: torch.Tensor, pred_t: torch.Tensor, model_points: torch.Tensor, target: torch.Tensor,
@@ -34,7 +34,7 @@ def add_metric(pred_r: torch.Tensor, pred_t: torch.Tensor, model_points: torch.T
     ws = torch.empty((B * ((Pn + 255) // 256),), dtype=torch.float64, device=dev)
     out = torch.empty((B,), dtype=torch.float64, device=dev)
     _lib.call("krrn_add_metric_f32", ptr(r), ptr(t), ptr(mp), ptr(tg), ptr(cls), ptr(symt),
-              len(sym), B, Pn, ptr(ws), ptr(out), P(torch.cuda.current_stream(dev).cuda_stream))
+              len(sym), B, Pn, ptr(ws), ptr(out), stream_ptr(dev))
     return out
 
 

@@ -13,14 +13,7 @@ from typing import List, Optional, Sequence, Tuple
 import torch
 
 from . import _lib, knobs
-
-
-def _ptr(t: Optional[torch.Tensor]):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+from ._lib import ptr, stream_ptr
 
 
 def _int_array(vals: Sequence[int], n: int = 9):
@@ -115,22 +108,22 @@ def conv2d(x: Act, spec: ConvSpec, out: Act, res: Optional[Act] = None, relu: bo
                 spec.wt3 = [conv_weights_x3(w) for w in spec.wt]
             w3 = spec.wt3[cls]
             _lib.call("krrn_conv2d_x3_f32",
-                      _ptr(x.t), x.cs, x.co, x.B, x.H, x.W, spec.cin_p, Hg, Wg, in_s, len(taps), dy, dx,
-                      _ptr(w3), np_, np_, _ptr(spec.scale), _ptr(spec.bias), _ptr(bias2), b2_div,
-                      _ptr(res.t if res is not None else None), res.cs if res is not None else 0,
+                      ptr(x.t), x.cs, x.co, x.B, x.H, x.W, spec.cin_p, Hg, Wg, in_s, len(taps), dy, dx,
+                      ptr(w3), np_, np_, ptr(spec.scale), ptr(spec.bias), ptr(bias2), b2_div,
+                      ptr(res.t if res is not None else None), res.cs if res is not None else 0,
                       res.co if res is not None else 0,
-                      _ptr(out.t), out.cs, out.co, Ho, Wo, osy, osx, ooy, oox, int(relu), t, splits,
-                      _ptr(ws), _stream())
+                      ptr(out.t), out.cs, out.co, Ho, Wo, osy, osx, ooy, oox, int(relu), t, splits,
+                      ptr(ws), stream_ptr())
             continue
         _lib.call("krrn_conv2d_f32",
-                  _ptr(x.t), x.cs, x.co, x.B, x.H, x.W, spec.cin_p,
+                  ptr(x.t), x.cs, x.co, x.B, x.H, x.W, spec.cin_p,
                   Hg, Wg, in_s, len(taps), dy, dx,
-                  _ptr(spec.wt[cls]), np_, np_, _ptr(spec.scale), _ptr(spec.bias),
-                  _ptr(bias2), b2_div,
-                  _ptr(res.t if res is not None else None), res.cs if res is not None else 0,
+                  ptr(spec.wt[cls]), np_, np_, ptr(spec.scale), ptr(spec.bias),
+                  ptr(bias2), b2_div,
+                  ptr(res.t if res is not None else None), res.cs if res is not None else 0,
                   res.co if res is not None else 0,
-                  _ptr(out.t), out.cs, out.co, Ho, Wo, osy, osx, ooy, oox, int(relu), 0, tile, splits,
-                  _ptr(ws), _stream())
+                  ptr(out.t), out.cs, out.co, Ho, Wo, osy, osx, ooy, oox, int(relu), 0, tile, splits,
+                  ptr(ws), stream_ptr())
 
 
 def conv2d_nchw(x: Act, spec: ConvSpec, out: torch.Tensor, n_store: int, relu: bool = False, tile: int = 0):
@@ -143,10 +136,10 @@ def conv2d_nchw(x: Act, spec: ConvSpec, out: torch.Tensor, n_store: int, relu: b
         from .runtime import conv_tile
         tile = conv_tile(B * Ho * Wo, np_, spec.cin_p, nchw=True)
     _lib.call("krrn_conv2d_f32",
-              _ptr(x.t), x.cs, x.co, x.B, x.H, x.W, spec.cin_p,
+              ptr(x.t), x.cs, x.co, x.B, x.H, x.W, spec.cin_p,
               Ho, Wo, spec.stride, len(taps), _int_array([t[0] for t in taps]), _int_array([t[1] for t in taps]),
-              _ptr(spec.wt[0]), np_, n_store, _ptr(spec.scale), _ptr(spec.bias), _ptr(None), 1,
-              _ptr(None), 0, 0, _ptr(out), C, 0, Ho, Wo, 1, 1, 0, 0, int(relu), 1, tile, 1, _ptr(None), _stream())
+              ptr(spec.wt[0]), np_, n_store, ptr(spec.scale), ptr(spec.bias), ptr(None), 1,
+              ptr(None), 0, 0, ptr(out), C, 0, Ho, Wo, 1, 1, 0, 0, int(relu), 1, tile, 1, ptr(None), stream_ptr())
 
 
 def gemm(a: torch.Tensor, a_cs: int, a_co: int, M: int, spec: ConvSpec, out: torch.Tensor, out_cs: int,
@@ -155,10 +148,10 @@ def gemm(a: torch.Tensor, a_cs: int, a_co: int, M: int, spec: ConvSpec, out: tor
     """Row-major GEMM out[M, :N] = act(scale * (A[M, K] @ W^T) + bias [+ bias2]) via the conv kernel."""
     np_ = pad4(spec.cout)
     _lib.call("krrn_conv2d_f32",
-              _ptr(a), a_cs, a_co, 1, 1, M, spec.cin_p, 1, M, 1, 1, _int_array([0]), _int_array([0]),
-              _ptr(spec.wt[0]), np_, np_, _ptr(spec.scale), _ptr(spec.bias), _ptr(bias2), b2_div,
-              _ptr(None), 0, 0, _ptr(out), out_cs, out_co, 1, M, 1, 1, 0, 0, int(relu), 0, tile, splits, _ptr(ws),
-              _stream())
+              ptr(a), a_cs, a_co, 1, 1, M, spec.cin_p, 1, M, 1, 1, _int_array([0]), _int_array([0]),
+              ptr(spec.wt[0]), np_, np_, ptr(spec.scale), ptr(spec.bias), ptr(bias2), b2_div,
+              ptr(None), 0, 0, ptr(out), out_cs, out_co, 1, M, 1, 1, 0, 0, int(relu), 0, tile, splits, ptr(ws),
+              stream_ptr())
 
 
 # ----------------------------------------------------------------------------------------

@@ -18,34 +18,53 @@ from typing import Dict, Optional
 
 import torch
 
-from .runtime import P, Plan, h2d, ptr
-from . import _lib, icp, umeyama
+from .runtime import Immediate, Plan, RngStream, device_seed, h2d, ptr
+from . import icp, umeyama
 
 NUM_POINTS = 256
 N_HYP = 100
 THRESHOLD = 1.0
 CONFIDENCE = 0.9999
-# counter-RNG stream ids (krrn.py's pool draws use 0-4, the PnP step 5-7, umeyama.py's own draws 8)
-UMEYAMA_STREAM = 9
-UMEYAMA_PLAN_STREAM = 10
 
-_seeds: Dict[int, torch.Tensor] = {}
-
-
-def _seed(device) -> torch.Tensor:
-    idx = device.index or 0
-    if idx not in _seeds:
-        _seeds[idx] = torch.zeros(1, dtype=torch.int64, device=device)
-    return _seeds[idx]
-
-
-def _dev(t: torch.Tensor, device, dtype=None) -> torch.Tensor:
-    return h2d(t, device, dtype)
+_seeds: Dict[int, torch.Tensor] = {}  # this module's counters (umeyama.py's own draws keep another table)
 
 
 def draw_sel(B: int, N: int, num_points: int = NUM_POINTS) -> torch.Tensor:
     """torch.randperm(N)[:num_points] per crop on the CPU generator (trainer.py:406-408)."""
     return torch.stack([torch.randperm(N)[:num_points] for _ in range(B)]).to(torch.int32)
+
+
+def pnp_step(ctx, xyz: torch.Tensor, choose: torch.Tensor, B: int, N: int, xm: torch.Tensor, ym: torch.Tensor,
+             K4: torch.Tensor, ext: torch.Tensor, lfb: torch.Tensor, P_: int, n_hyp: int = N_HYP,
+             thr: float = THRESHOLD, sel=None, subsets=None, seed=None, sel_stream=None, subsets_stream=None):
+    """The krrn_pnp_ransac_f32 launch, stated once, on `ctx` (a runtime.Plan or runtime.Immediate). Contiguous
+    device tensors: xyz f32 [B, 3, H, W], choose i64 [B, N], xm / ym f32 [B, N], K4 f32 [B, 4], ext / lfb f64 [B, 3],
+    sel int32 [B, P_], subsets int32 [B, n_hyp, 5]; without `sel` / `subsets` they are drawn through `ctx` from
+    `seed` on counter streams `sel_stream` / `subsets_stream` (the caller advances the seed). Returns buffers."""
+    H, W = xyz.shape[2], xyz.shape[3]
+    if sel is None:
+        sel = ctx.buf((B, P_), torch.int32)
+        ctx.add("krrn_randperm_i32", ptr(seed), int(sel_stream), N, P_, B, ptr(sel))
+    if subsets is None:
+        subsets = ctx.buf((B, n_hyp, 5), torch.int32)
+        ctx.add("krrn_ransac_subsets", ptr(seed), int(subsets_stream), B, n_hyp, P_, ptr(subsets))
+    R = ctx.buf((B, 3, 3))
+    t = ctx.buf((B, 3))
+    inl = ctx.buf((B,), torch.int32)
+    mask = ctx.buf((B, P_), torch.uint8)
+    ws = ctx.buf((B * n_hyp * 13,))
+    ctx.add("krrn_pnp_ransac_f32", ptr(xyz), H * W, ptr(choose), N, ptr(sel), P_, ptr(xm), ptr(ym), ptr(K4), ptr(ext),
+            ptr(lfb), ptr(subsets), n_hyp, float(thr), CONFIDENCE, ptr(ws), ptr(R), ptr(t), ptr(inl), ptr(mask), B)
+    return R, t, inl, dict(sel=sel, subsets=subsets, mask=mask, workspace=ws)
+
+
+def model_points_step(ctx, xyz: torch.Tensor, choose: torch.Tensor, B: int, N: int, ext: torch.Tensor,
+                      lfb: torch.Tensor) -> torch.Tensor:
+    """The krrn_model_points_f32 launch: src f32 [B, N, 3] = xyz * extent + lfborder at the chosen pixels."""
+    src = ctx.buf((B, N, 3))
+    ctx.add("krrn_model_points_f32", ptr(xyz), xyz.shape[2] * xyz.shape[3], ptr(choose), N, ptr(ext), ptr(lfb),
+            ptr(src), B)
+    return src
 
 
 def get_pose(pred, data, num_points: int = NUM_POINTS, n_hyp: int = N_HYP, thr: float = THRESHOLD,
@@ -55,38 +74,27 @@ def get_pose(pred, data, num_points: int = NUM_POINTS, n_hyp: int = N_HYP, thr: 
         raise RuntimeError("get_pose runs on the HIP path only (pred['xyz'] must be a GPU tensor)")
     dev = xyz.device
     xyz = xyz.contiguous()
-    B, _, H, W = xyz.shape
-    choose = _dev(data["choose"].reshape(B, -1), dev, torch.int64)
+    B = xyz.shape[0]
+    choose = h2d(data["choose"].reshape(B, -1), dev, torch.int64)
     N = choose.shape[1]
     P_ = min(num_points, N)
     if sel is None:
         sel = draw_sel(B, N, P_)
-    sel = _dev(sel.reshape(B, P_), dev, torch.int32)
-    xm = _dev(data["x_map_choosed"].reshape(B, N), dev, torch.float32)
-    ym = _dev(data["y_map_choosed"].reshape(B, N), dev, torch.float32)
-    K4 = _dev(data["intrinsic"].reshape(B, 4), dev, torch.float32)
-    ext = _dev(data["extent"].reshape(B, 3), dev, torch.float64)
-    lfb = _dev(data["lfborder"].reshape(B, 3), dev, torch.float64)
-    stream = P(torch.cuda.current_stream(dev).cuda_stream)
-    lib = _lib.lib()
-    if subsets is None:
-        subsets = torch.empty((B, n_hyp, 5), dtype=torch.int32, device=dev)
-        seed = _seed(dev)
-        _lib.check(lib.krrn_ransac_subsets(ptr(seed), 7, B, n_hyp, P_, ptr(subsets), stream), "krrn_ransac_subsets")
-        _lib.check(lib.krrn_rng_advance(ptr(seed), stream), "krrn_rng_advance")
-    else:
-        subsets = _dev(subsets.reshape(B, -1, 5), dev, torch.int32)
+    sel = h2d(sel.reshape(B, P_), dev, torch.int32)
+    xm, ym = (h2d(data[k].reshape(B, N), dev, torch.float32) for k in ("x_map_choosed", "y_map_choosed"))
+    K4 = h2d(data["intrinsic"].reshape(B, 4), dev, torch.float32)
+    ext, lfb = (h2d(data[k].reshape(B, 3), dev, torch.float64) for k in ("extent", "lfborder"))
+    ctx = Immediate(dev)
+    seed = device_seed(_seeds, dev) if subsets is None else None
+    if subsets is not None:
+        subsets = h2d(subsets.reshape(B, -1, 5), dev, torch.int32)
         n_hyp = subsets.shape[1]
-    R = torch.empty((B, 3, 3), dtype=torch.float32, device=dev)
-    t = torch.empty((B, 3), dtype=torch.float32, device=dev)
-    inl = torch.empty((B,), dtype=torch.int32, device=dev)
-    mask = torch.empty((B, P_), dtype=torch.uint8, device=dev)
-    ws = torch.empty((B * n_hyp * 13,), dtype=torch.float32, device=dev)
-    _lib.check(lib.krrn_pnp_ransac_f32(ptr(xyz), H * W, ptr(choose), N, ptr(sel), P_, ptr(xm), ptr(ym), ptr(K4),
-                                       ptr(ext), ptr(lfb), ptr(subsets), n_hyp, float(thr), CONFIDENCE, ptr(ws), ptr(R), ptr(t),
-                                       ptr(inl), ptr(mask), B, stream), "krrn_pnp_ransac_f32")
+    R, t, inl, info = pnp_step(ctx, xyz, choose, B, N, xm, ym, K4, ext, lfb, P_, n_hyp, thr, sel, subsets, seed,
+                               subsets_stream=RngStream.PNP_SUBSETS)
+    if seed is not None:
+        ctx.add("krrn_rng_advance", ptr(seed))
     if return_info:
-        return R, t, {"inliers": inl, "mask": mask, "sel": sel, "subsets": subsets, "workspace": ws}
+        return R, t, dict(info, inliers=inl)
     return R, t
 
 
@@ -105,17 +113,14 @@ def get_pose_umeyama(pred, data, n_hyp: int = umeyama.N_HYP, subsets: Optional[t
         raise RuntimeError("get_pose_umeyama runs on the HIP path only (pred['xyz'] must be a GPU tensor)")
     dev = xyz.device
     xyz = xyz.to(torch.float32).contiguous()
-    B, _, H, W = xyz.shape
-    choose = _dev(data["choose"].reshape(B, -1), dev, torch.int64)
+    B = xyz.shape[0]
+    choose = h2d(data["choose"].reshape(B, -1), dev, torch.int64)
     N = choose.shape[1]
-    cloud = _dev(data["cloud"].reshape(B, N, 3), dev, torch.float32)
-    ext = _dev(data["extent"].reshape(B, 3), dev, torch.float64)
-    lfb = _dev(data["lfborder"].reshape(B, 3), dev, torch.float64)
-    stream = P(torch.cuda.current_stream(dev).cuda_stream)
-    src = torch.empty((B, N, 3), dtype=torch.float32, device=dev)
-    _lib.check(_lib.lib().krrn_model_points_f32(ptr(xyz), H * W, ptr(choose), N, ptr(ext), ptr(lfb), ptr(src), B,
-                                                stream), "krrn_model_points_f32")
-    scale, R, t, info = umeyama.solve(src, cloud, subsets, n_hyp, seed=_seed(dev), stream_id=UMEYAMA_STREAM)
+    cloud = h2d(data["cloud"].reshape(B, N, 3), dev, torch.float32)
+    ext, lfb = (h2d(data[k].reshape(B, 3), dev, torch.float64) for k in ("extent", "lfborder"))
+    src = model_points_step(Immediate(dev), xyz, choose, B, N, ext, lfb)
+    scale, R, t, info = umeyama.solve(src, cloud, subsets, n_hyp, seed=device_seed(_seeds, dev),
+                                      stream_id=RngStream.UMEYAMA_POSE)
     if return_info:
         info.update(scale=scale, src=src)
         return R, t, info
@@ -127,22 +132,11 @@ def add_umeyama_ops(plan: Plan, xyz: torch.Tensor, choose: torch.Tensor, cloud: 
     """Append the Umeyama-RANSAC pose step to a plan (graph-capturable: subsets drawn on the device from
     `seed`; the caller's plan advances the seed). Returns (R, t, inliers, info) buffers; info holds
     scale, src, subsets, hyp_counts, best_hyp, mask."""
-    H, W = xyz.shape[2], xyz.shape[3]
-    src = plan.buf((B, N, 3))
-    subsets = plan.buf((B, n_hyp, 5), torch.int32)
-    counts = plan.buf((B, n_hyp), torch.int32)
-    scale = plan.buf((B,))
-    R = plan.buf((B, 3, 3))
-    t = plan.buf((B, 3))
-    inl = plan.buf((B,), torch.int32)
-    best = plan.buf((B,), torch.int32)
-    mask = plan.buf((B, N), torch.uint8)
-    plan.add("krrn_model_points_f32", ptr(xyz), H * W, ptr(choose), N, ptr(ext), ptr(lfb), ptr(src), B)
-    plan.add("krrn_ransac_subsets", ptr(seed), UMEYAMA_PLAN_STREAM, B, n_hyp, N, ptr(subsets))
-    plan.add("krrn_umeyama_ransac_f32", ptr(src), ptr(cloud), N, ptr(subsets), n_hyp, umeyama.INLIER_FRAC,
-             umeyama.CONFIDENCE, umeyama.MIN_RATIO, ptr(counts), ptr(scale), ptr(R), ptr(t), ptr(inl), ptr(best),
-             ptr(mask), B)
-    return R, t, inl, dict(scale=scale, src=src, subsets=subsets, hyp_counts=counts, best_hyp=best, mask=mask)
+    src = model_points_step(plan, xyz, choose, B, N, ext, lfb)
+    scale, R, t, info = umeyama.ransac_step(plan, src, cloud, B, N, n_hyp, seed=seed,
+                                            stream_id=RngStream.UMEYAMA_PLAN)
+    inl = info.pop("inliers")
+    return R, t, inl, dict(info, scale=scale, src=src)
 
 
 def refine_pose_icp(R: torch.Tensor, t: torch.Tensor, data, diameter=None, max_dist=None,
@@ -161,8 +155,8 @@ def refine_pose_icp(R: torch.Tensor, t: torch.Tensor, data, diameter=None, max_d
                                     else float(diameter))
     dev = R.device
     B = R.shape[0]
-    cloud = _dev(data["cloud"].reshape(B, -1, 3), dev, torch.float32)
-    mp = _dev(data["model_points"].reshape(B, -1, 3), dev, torch.float32)
+    cloud = h2d(data["cloud"].reshape(B, -1, 3), dev, torch.float32)
+    mp = h2d(data["model_points"].reshape(B, -1, 3), dev, torch.float32)
     return icp.refine(R, t.reshape(B, 3), cloud, mp, max_dist, max_iter, tol, min_pairs, return_info)
 
 
@@ -172,35 +166,15 @@ def add_icp_ops(plan: Plan, R: torch.Tensor, t: torch.Tensor, cloud: torch.Tenso
     """Append the ICP refinement to a plan (graph-capturable: one launch, no host decision). R [B, 3, 3],
     t [B, 3], cloud [B, N, 3], model [B, M, 3], max_dist [B]: f32 contiguous device buffers read at run
     time. Returns (R, t, info) buffers; info holds passes, pairs, rmse, status, nn_idx."""
-    Ro = plan.buf((B, 3, 3))
-    to = plan.buf((B, 3))
-    passes = plan.buf((B,), torch.int32)
-    pairs = plan.buf((B,), torch.int32)
-    rmse = plan.buf((B,))
-    status = plan.buf((B,), torch.int32)
-    nn_idx = plan.buf((B, N), torch.int32)
-    plan.add("krrn_icp_refine_f32", ptr(R), ptr(t), ptr(cloud), N, ptr(model), M, ptr(max_dist), int(max_iter),
-             float(tol), int(min_pairs), ptr(Ro), ptr(to), ptr(passes), ptr(pairs), ptr(rmse), ptr(status),
-             ptr(nn_idx), B)
-    return Ro, to, dict(passes=passes, pairs=pairs, rmse=rmse, status=status, nn_idx=nn_idx)
+    return icp.refine_step(plan, R, t, cloud, model, max_dist, B, N, M, max_iter, tol, min_pairs)
 
 
 def add_pose_ops(plan: Plan, xyz: torch.Tensor, choose: torch.Tensor, B: int, N: int, xm: torch.Tensor,
                  ym: torch.Tensor, K4: torch.Tensor, ext: torch.Tensor, lfb: torch.Tensor, seed: torch.Tensor,
                  num_points: int = NUM_POINTS, n_hyp: int = N_HYP, thr: float = THRESHOLD):
     """Append the pose step to a plan (graph-capturable: choose subset and RANSAC subsets drawn
-    on the device). Returns (R, t, inliers) buffers."""
-    H, W = xyz.shape[2], xyz.shape[3]
-    P_ = min(num_points, N)
-    sel = plan.buf((B, P_), torch.int32)
-    subsets = plan.buf((B, n_hyp, 5), torch.int32)
-    R = plan.buf((B, 3, 3))
-    t = plan.buf((B, 3))
-    inl = plan.buf((B,), torch.int32)
-    mask = plan.buf((B, P_), torch.uint8)
-    ws = plan.buf((B * n_hyp * 13,))
-    plan.add("krrn_randperm_i32", ptr(seed), 5, N, P_, B, ptr(sel))
-    plan.add("krrn_ransac_subsets", ptr(seed), 6, B, n_hyp, P_, ptr(subsets))
-    plan.add("krrn_pnp_ransac_f32", ptr(xyz), H * W, ptr(choose), N, ptr(sel), P_, ptr(xm), ptr(ym), ptr(K4), ptr(ext),
-             ptr(lfb), ptr(subsets), n_hyp, float(thr), CONFIDENCE, ptr(ws), ptr(R), ptr(t), ptr(inl), ptr(mask), B)
-    return R, t, inl, dict(sel=sel, subsets=subsets, mask=mask)
+    on the device; the caller's plan advances the seed). Returns (R, t, inliers) buffers."""
+    R, t, inl, info = pnp_step(plan, xyz, choose, B, N, xm, ym, K4, ext, lfb, min(num_points, N), n_hyp, thr,
+                               seed=seed, sel_stream=RngStream.PNP_PLAN_SEL,
+                               subsets_stream=RngStream.PNP_PLAN_SUBSETS)
+    return R, t, inl, dict(sel=info["sel"], subsets=info["subsets"], mask=info["mask"])

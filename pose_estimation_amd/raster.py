@@ -21,15 +21,11 @@ import torch
 
 from . import _lib
 from .fps import farthest_point_sampling
-from .runtime import P, h2d, ptr
+from .runtime import h2d, ptr, stream_ptr
 
 MAX_S = 480          # kRastMaxS of csrc/raster.hip
 MAX_REGIONS = 256    # kRastMaxNR
 N_REGIONS = 64       # the region head's classes (batchdataset.py:105's fps_64)
-
-
-def _stream(dev) -> P:
-    return P(torch.cuda.current_stream(dev).cuda_stream)
 
 
 def region_points(verts: torch.Tensor, n: int = N_REGIONS) -> torch.Tensor:
@@ -86,7 +82,7 @@ def render_maps(verts: torch.Tensor, faces: torch.Tensor, face_range: torch.Tens
         out["cover_frame"] = cover
     _lib.call("krrn_raster_maps_f32", ptr(v), v.shape[0], ptr(f), f.shape[0], ptr(fr), ptr(R64), ptr(t64), ptr(K),
               ptr(rc), S, ptr(rp), NR, B, ptr(out["face"]), ptr(out["depth"]), ptr(out["coord"]), ptr(out["normal"]),
-              ptr(out["region"]), ptr(cover), Hf, Wf, _stream(dev))
+              ptr(out["region"]), ptr(cover), Hf, Wf, stream_ptr(dev))
     return out
 
 
@@ -109,5 +105,5 @@ def finish_maps(maps: Dict[str, torch.Tensor], point_mask: torch.Tensor, cls: to
            "mask_obj": torch.empty((B, 1, S, S), dtype=torch.float32, device=dev)}
     _lib.call("krrn_gt_maps_finish_f32", ptr(coord), ptr(maps["region"]), ptr(maps["face"]), ptr(pm), ptr(c), ptr(ext),
               ptr(lfb), B, S * S, ptr(out["xyz"]), ptr(normal), ptr(out["region"]), ptr(out["mask"]),
-              ptr(out["multi_cls_mask"]), ptr(out["mask_obj"]), _stream(dev))
+              ptr(out["multi_cls_mask"]), ptr(out["mask_obj"]), stream_ptr(dev))
     return out

@@ -17,8 +17,8 @@ from typing import Any, Callable, Dict, List, Optional, Sequence, Tuple
 import torch
 
 from . import _lib, knobs, ops
+from ._lib import P, ptr, stream_ptr  # noqa: F401  (P / ptr / h2d are this module's exports too)
 
-P = ctypes.c_void_p
 I = ctypes.c_int
 
 
@@ -36,10 +36,6 @@ STREAM = "__stream__"
 
 def _skey(sid: int) -> str:
     return STREAM if sid == 0 else f"__stream{sid}__"
-
-
-def ptr(t: Optional[torch.Tensor]) -> P:
-    return P(t.data_ptr()) if t is not None else P(0)
 
 
 def h2d(t: torch.Tensor, device, dtype=None) -> torch.Tensor:
@@ -292,6 +288,41 @@ class Plan:
         return [(op, evs[i].elapsed_time(evs[i + 1])) for i, op in enumerate(kops)]
 
 
+class Immediate:
+    """Plan's two verbs, executed at once: `add` launches on the device's current stream (one ctypes call,
+    no Op, no launch list), so a step written against `ctx.buf` / `ctx.add` (pose.pnp_step, umeyama.ransac_step,
+    icp.refine_step) is stated once for the eager call and the plan op. Unlike Plan.buf, `buf` does NOT zero
+    (torch.empty: an eager call adds no memsets); every buffer those steps allocate is fully written by its kernel."""
+
+    def __init__(self, device):
+        self.device = torch.device(device)
+
+    def buf(self, shape, dtype=torch.float32) -> torch.Tensor:
+        return torch.empty(tuple(shape), dtype=dtype, device=self.device)
+
+    def add(self, name: str, *args):
+        _lib.call(name, *args, stream_ptr(self.device))
+
+
+class RngStream:
+    """Counter-RNG stream ids (krrn_randperm_* / krrn_ransac_subsets): distinct ids, independent draws per seed."""
+    POOL = (0, 1, 2, 3, 4)   # krrn.py: the fusion's five pool permutations
+    PNP_PLAN_SEL = 5         # pose.add_pose_ops: the choose subset
+    PNP_PLAN_SUBSETS = 6     # pose.add_pose_ops: the hypothesis subsets
+    PNP_SUBSETS = 7          # pose.get_pose (its choose subset comes from the CPU generator)
+    UMEYAMA_OWN = 8          # umeyama.estimateSimilarityTransform, on umeyama's own seed table
+    UMEYAMA_POSE = 9         # pose.get_pose_umeyama
+    UMEYAMA_PLAN = 10        # pose.add_umeyama_ops
+
+
+def device_seed(table: Dict[int, torch.Tensor], device) -> torch.Tensor:
+    """The int64 [1] seed counter of `device` in a module's own table (made at 0 on first use)."""
+    idx = device.index or 0
+    if idx not in table:
+        table[idx] = torch.zeros(1, dtype=torch.int64, device=device)
+    return table[idx]
+
+
 def conv_tile(M: int, N: int, K: int = 1024, nchw: bool = False) -> int:
     """Tile choice for krrn_conv2d_f32 from the measured menu (scratch/convbench.py on MI355X,
     graph-replayed, buffer-load staging): 64x64x32 (4-5 waves/SIMD) is best or within 3% on
@@ -334,11 +365,7 @@ CONV_KERNELS = {1: "conv_gemm_f32<128,128,16>", 2: "conv_gemm_f32<128,64,16>", 3
                 7: "conv_gemm_f32<128,64,32>", 8: "conv_gemm_f32<64,64,32>"}
 
 
-def _iarr(vals):
-    arr = (ctypes.c_int * 9)()
-    for i, v in enumerate(vals):
-        arr[i] = int(v)
-    return arr
+_iarr = ops._int_array  # the int[9] tap tables
 
 
 # split-bf16 implicit GEMM (krrn_conv2d_x3_f32): 128x64x16 tiles for N > 32, no split-K
@@ -485,11 +512,12 @@ def add_gemm(plan: Plan, *, a: torch.Tensor, a_off: int, lda: int, M: int, wt: t
 
     def packed(kind: str, fn):
         """The kernel's packed weights, built once per (weights, scale, kind) in a plan: a GEMM
-        repeated over row chunks (the fusion's level-0 crop chunks) shares one copy."""
+        repeated over row chunks (the fusion's level-0 crop chunks) shares one copy. The key is made of
+        wt's and scale's addresses and the launch reads this call's bias: the plan keeps all three."""
         key = wkey + (kind,)
         if key not in plan._packed:
             plan._packed[key] = fn(w)
-            plan.buffers.append([plan._packed[key], bias])
+        plan.buffers.append([plan._packed[key], wt, scale, bias])
         return plan._packed[key]
     flops = 2.0 * (cin or K) * (cout or N) * M * batch
     if GEMM_PANEL and not require_x3 and K in (64, 128) and N % 32 == 0 and N <= 2048 and batch == 1 \

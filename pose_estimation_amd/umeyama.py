@@ -23,53 +23,51 @@ from typing import Dict, Optional
 
 import torch
 
-from .runtime import P, h2d, ptr
-from . import _lib
+from .runtime import Immediate, RngStream, device_seed, h2d, ptr
 
 N_HYP = 128          # maxIter (:21)
 INLIER_FRAC = 0.1    # InlierT = SourceDiameter / 10 (:20)
 CONFIDENCE = 0.99    # (:22)
 MIN_RATIO = 0.1      # (:50)
 MAX_POINTS = 4096    # kUmeMaxN of csrc/umeyama.hip
-SUBSET_STREAM = 8    # counter-RNG stream of this module's draws (krrn.py: 0-4, pose.py: 5-7, 9, 10)
 
-_seeds: Dict[int, torch.Tensor] = {}
+_seeds: Dict[int, torch.Tensor] = {}  # this module's own counters (pose.py keeps another table)
 
 
-def _seed(device) -> torch.Tensor:
-    idx = device.index or 0
-    if idx not in _seeds:
-        _seeds[idx] = torch.zeros(1, dtype=torch.int64, device=device)
-    return _seeds[idx]
+def ransac_step(ctx, src: torch.Tensor, dst: torch.Tensor, B: int, N: int, n_hyp: int = N_HYP,
+                subsets=None, seed=None, stream_id=None):
+    """The krrn_umeyama_ransac_f32 launch, stated once, on `ctx` (a runtime.Plan or runtime.Immediate). src / dst
+    f32 [B, N, 3] and `subsets` int32 [B, n_hyp, 5] are contiguous device tensors; without `subsets` they are drawn
+    through `ctx` from `seed` on counter stream `stream_id` (the caller advances the seed). Returns buffers."""
+    if subsets is None:
+        subsets = ctx.buf((B, n_hyp, 5), torch.int32)
+        ctx.add("krrn_ransac_subsets", ptr(seed), int(stream_id), B, n_hyp, N, ptr(subsets))
+    scale = ctx.buf((B,))
+    R = ctx.buf((B, 3, 3))
+    t = ctx.buf((B, 3))
+    inl = ctx.buf((B,), torch.int32)
+    best = ctx.buf((B,), torch.int32)
+    counts = ctx.buf((B, n_hyp), torch.int32)
+    mask = ctx.buf((B, N), torch.uint8)
+    ctx.add("krrn_umeyama_ransac_f32", ptr(src), ptr(dst), N, ptr(subsets), n_hyp, INLIER_FRAC, CONFIDENCE, MIN_RATIO,
+            ptr(counts), ptr(scale), ptr(R), ptr(t), ptr(inl), ptr(best), ptr(mask), B)
+    return scale, R, t, {"inliers": inl, "best_hyp": best, "hyp_counts": counts, "mask": mask, "subsets": subsets}
 
 
 def solve(src: torch.Tensor, dst: torch.Tensor, subsets: Optional[torch.Tensor] = None, n_hyp: int = N_HYP,
-          seed: Optional[torch.Tensor] = None, stream_id: int = SUBSET_STREAM):
-    """src / dst f32 [B, N, 3] contiguous GPU tensors -> (scale, R, t, info) device buffers."""
+          seed: Optional[torch.Tensor] = None, stream_id: int = RngStream.UMEYAMA_OWN):
+    """src / dst f32 [B, N, 3] contiguous GPU tensors -> (scale, R, t, info) device buffers. Without
+    `subsets` they are drawn from `seed` (default: this module's own counter), which is then advanced."""
     dev = src.device
     B, N, _ = src.shape
-    stream = P(torch.cuda.current_stream(dev).cuda_stream)
-    lib = _lib.lib()
-    if subsets is None:
-        subsets = torch.empty((B, n_hyp, 5), dtype=torch.int32, device=dev)
-        seed = _seed(dev) if seed is None else seed
-        _lib.check(lib.krrn_ransac_subsets(ptr(seed), stream_id, B, n_hyp, N, ptr(subsets), stream),
-                   "krrn_ransac_subsets")
-        _lib.check(lib.krrn_rng_advance(ptr(seed), stream), "krrn_rng_advance")
-    else:
+    ctx = Immediate(dev)
+    if subsets is not None:
         subsets = h2d(subsets.reshape(B, -1, 5), dev, torch.int32)
-        n_hyp = subsets.shape[1]
-    scale = torch.empty((B,), dtype=torch.float32, device=dev)
-    R = torch.empty((B, 3, 3), dtype=torch.float32, device=dev)
-    t = torch.empty((B, 3), dtype=torch.float32, device=dev)
-    inl = torch.empty((B,), dtype=torch.int32, device=dev)
-    best = torch.empty((B,), dtype=torch.int32, device=dev)
-    counts = torch.empty((B, n_hyp), dtype=torch.int32, device=dev)
-    mask = torch.empty((B, N), dtype=torch.uint8, device=dev)
-    _lib.check(lib.krrn_umeyama_ransac_f32(ptr(src), ptr(dst), N, ptr(subsets), n_hyp, INLIER_FRAC, CONFIDENCE,
-                                           MIN_RATIO, ptr(counts), ptr(scale), ptr(R), ptr(t), ptr(inl), ptr(best),
-                                           ptr(mask), B, stream), "krrn_umeyama_ransac_f32")
-    return scale, R, t, {"inliers": inl, "best_hyp": best, "hyp_counts": counts, "mask": mask, "subsets": subsets}
+        return ransac_step(ctx, src, dst, B, N, subsets.shape[1], subsets)
+    seed = device_seed(_seeds, dev) if seed is None else seed
+    out = ransac_step(ctx, src, dst, B, N, n_hyp, None, seed, stream_id)
+    ctx.add("krrn_rng_advance", ptr(seed))
+    return out
 
 
 def estimateSimilarityTransform(source: torch.Tensor, target: torch.Tensor, subsets: Optional[torch.Tensor] = None,

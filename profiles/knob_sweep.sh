@@ -9,7 +9,6 @@ run() {
   python3 -c "import json; d=json.loads(open('gpurun_out/${T}_$name.log').read().strip().splitlines()[-1]); print('$name', d['ms_per_step'], d['value'])"
 }
 run base KRRN_X=0
-run hr_group KRRN_HR_GROUP=1
 run pose_heads KRRN_POSE_AT=heads
 run pose_level2 KRRN_POSE_AT=level2
 run tbase_late KRRN_TBASE_EARLY=0

@@ -84,8 +84,9 @@ class _FakeSet:
         return self.sizes[i]
 
 
-def _fake_records(model, dataset, indices, bs, device, opt_pose=True, with_loss=True):
-    """Deterministic per-crop records (a function of the crop id only), in evaluation order."""
+def _fake_records(model, dataset, indices, bs, device, opt_pose=True, with_loss=True, **solver):
+    """Deterministic per-crop records (a function of the crop id only), in evaluation order; the pose
+    solver's keywords are accepted and ignored."""
     from pose_estimation_amd import evaluate as ev
     rows = []
     for S, idx in ev._batches(indices, bs):

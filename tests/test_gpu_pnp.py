@@ -130,6 +130,38 @@ def test_ransac_failure_identity(dev):
             assert torch.all(t[b].cpu() == 0)
 
 
+def test_eager_and_plan_are_one_launch(dev):
+    """get_pose and a Plan built from the same step function (pose.pnp_step) on the same sel / subsets
+    tensors: one kernel through two host paths, so R, t, inliers and mask are bit-equal. Crop 1 has 30 %
+    outlier correspondences (the adaptive stop and the inlier refit run), crop 0 none."""
+    from pose_estimation_amd.runtime import Plan
+    N, S, P, H = 300, 40, 64, 16
+    parts = [_scene(1, N, S, 11, outlier_frac=0.0), _scene(1, N, S, 12, outlier_frac=0.3)]
+    B = len(parts)
+    xyz = torch.cat([p[0] for p in parts]).to(dev)
+    data = {k: torch.cat([p[1][k] for p in parts]) for k in parts[0][1]}
+    g = torch.Generator().manual_seed(5)
+    sel = torch.stack([torch.randperm(N, generator=g)[:P] for _ in range(B)]).to(torch.int32)
+    subsets = torch.stack([torch.stack([torch.randperm(P, generator=g)[:5] for _ in range(H)])
+                           for _ in range(B)]).to(torch.int32)
+    R, t, info = pose.get_pose({"xyz": xyz}, data, num_points=P, sel=sel, subsets=subsets, return_info=True)
+    assert info["subsets"].shape == (B, H, 5) and info["mask"].shape == (B, P)
+    d = lambda k, shape, dt: data[k].reshape(shape).to(device=dev, dtype=dt).contiguous()  # noqa: E731
+    plan = Plan(dev)
+    Rp, tp, inlp, infop = pose.pnp_step(
+        plan, xyz, d("choose", (B, N), torch.int64), B, N, d("x_map_choosed", (B, N), torch.float32),
+        d("y_map_choosed", (B, N), torch.float32), d("intrinsic", (B, 4), torch.float32),
+        d("extent", (B, 3), torch.float64), d("lfborder", (B, 3), torch.float64), P, H,
+        sel=info["sel"], subsets=info["subsets"])
+    assert [op.name for op in plan.ops] == ["krrn_pnp_ransac_f32"]
+    plan.run({})
+    torch.cuda.synchronize()
+    assert torch.equal(Rp, R) and torch.equal(tp, t)
+    assert torch.equal(inlp, info["inliers"]) and torch.equal(infop["mask"], info["mask"])
+    inl = info["inliers"].cpu()
+    assert int(inl[0]) == P and 5 <= int(inl[1]) < P, inl
+
+
 def test_device_rng(dev):
     from pose_estimation_amd import _lib
     from pose_estimation_amd.runtime import ptr, P

@@ -175,6 +175,27 @@ def test_all_duplicate_sample_counts_zero(dev):
     _compare(_run(dev, src[None], dst[None], sub[None]), 0, ref)
 
 
+def test_eager_and_plan_are_one_launch(dev):
+    """estimateSimilarityTransform and a Plan built from the same step function (umeyama.ransac_step) on
+    the same explicit subsets: one kernel through two host paths, so every output is bit-equal."""
+    from pose_estimation_amd import umeyama
+    B, N, H = 2, 300, 16
+    scenes = [_synth(40, N, out_frac=0.3, noise=1e-3), _synth(41, N)]
+    src = torch.from_numpy(np.stack([s for s, _ in scenes])).to(dev)
+    dst = torch.from_numpy(np.stack([d for _, d in scenes])).to(dev)
+    sub = torch.from_numpy(np.random.default_rng(40).integers(N, size=(B, H, 5)).astype(np.int32))
+    scale, R, t, _, info = estimateSimilarityTransform(src, dst, subsets=sub, return_info=True)
+    plan = Plan(dev)
+    ps, pR, pt, pinfo = umeyama.ransac_step(plan, src, dst, B, N, H, info["subsets"])
+    assert [op.name for op in plan.ops] == ["krrn_umeyama_ransac_f32"]
+    plan.run({})
+    torch.cuda.synchronize()
+    assert torch.equal(ps, scale) and torch.equal(pR, R) and torch.equal(pt, t)
+    for k in ("inliers", "best_hyp", "hyp_counts", "mask"):
+        assert torch.equal(pinfo[k], info[k]), k
+    assert (info["inliers"] > 0).all()
+
+
 def _pose_scene(B, N, S, seed, outlier_frac=0.1):
     """test_gpu_pnp._scene's xyz maps plus the cloud of the same pose: cloud = R obj + t."""
     from test_gpu_pnp import _scene
