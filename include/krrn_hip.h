@@ -518,6 +518,60 @@ int krrn_gt_maps_finish_f32(const float* coord, const int* region_raw, const int
                             const double* lfborder, int B, int HW, float* xyz, float* normal, long long* region,
                             float* mask, long long* multi_cls_mask, float* mask_obj, void* stream);
 
+/* BOP-19 pose errors (Hodan et al., "BOP Challenge 2020 on 6D Object Localization", ECCV-W 2020), written
+ * from the published definition; not compared against the BOP toolkit's output. One stated departure:
+ * pixels are sampled at their integer coordinates (this project's rasteriser convention, above).
+ *
+ * VSD, the visible surface discrepancy, of B estimates. verts / faces / face_range / K4 as
+ * krrn_raster_maps_f32; R_est, R_gt f64 [B][9], t_est, t_gt f64 [B][3]; depth f32 [F][H][W] the observed
+ * frames in raw units, frame int32 [B] the frame of crop b, depth_scale raw units per metre; diameter f64
+ * [B] metres; delta metres (BOP-19: 0.015); taus f64 [T], 1 <= T <= 16, fractions of the diameter (BOP-19:
+ * 0.05, 0.10 .. 0.50). Per crop over the whole H x W frame, in f64 without FMA contraction:
+ *   D_est(p), D_gt(p) = krrn_raster_maps_f32's depth z at the integer pixel p = (col, row) with rmin = cmin
+ *   = 0 under the estimated / the GT pose (the same face test, skip rules, strict < and lowest-face-index
+ *   tie rule: one device function, csrc/krrn_raster.h); 0 where no face covers p.
+ *   D_obs(p) = (double)depth[frame[b]][row][col] / depth_scale; all zero for a frame index outside [0, F).
+ *   xn = (col - cx) / fx, yn = (row - cy) / fy, ray = sqrt((xn xn + yn yn) + 1.0); a depth d > 0 becomes the
+ *   distance from the camera centre d ray, anything else (0, negative, NaN) the distance 0.
+ *   visib(model) = (obs > 0 && model > 0 && (model - obs) <= delta) || (obs == 0 && model > 0)   ("bop19")
+ *   V_gt = visib(dist_gt); V_est = visib(dist_est) || (V_gt && dist_est > 0)
+ *   inter = V_gt && V_est; union = V_gt || V_est; cost = |dist_gt - dist_est| / diameter[b] on inter
+ *   step_k = #{p in inter: cost >= taus[k]};  e_vsd[b][k] = (step_k + (union - inter)) / union, 1.0 if union = 0
+ * Outputs: counts int32 [B][2 + T] = (union, inter, step_0 .. step_{T-1}); e_vsd f64 [B][T] (one f64 division
+ * of the integers). ws: krrn_bop_vsd_ws(B) ints (the two projected bounding boxes per crop; tiles of the
+ * frame outside both do no work). The per-crop counts are summed over the tiles with integer atomicAdd (no
+ * per-tile workspace, no second pass): integer sums do not depend on order, so the result is deterministic
+ * and a crop's does not depend on the rest of the batch, bit for bit. Neither depth image is written to
+ * memory. Host checks: null or overlapping buffers KRRN_EARG; B, Vtot, F, H, W < 1, Ftot < 0, T outside
+ * 1..16, delta or depth_scale not > 0 KRRN_ESHAPE. frame and face_range are device memory and guarded by the
+ * kernel (a bad face range is an empty range). */
+int krrn_bop_vsd_ws(int B, long long* n_ints);
+int krrn_bop_vsd_f32(const float* verts, int Vtot, const int* faces, int Ftot, const int* face_range,
+                     const double* R_est, const double* t_est, const double* R_gt, const double* t_gt,
+                     const float* K4, const float* depth, int F, int H, int W, const int* frame, double depth_scale,
+                     const double* diameter, double delta, const double* taus, int T, int B, int* ws, int* counts,
+                     double* e_vsd, void* stream);
+
+/* MSSD / MSPD, the maximum symmetry-aware surface / projection distance. verts f32 [Vtot][3] (all mesh
+ * vertices), vert_range int32 [B][2] = first vertex, count of crop b; syms f64 [NStot][12] = row-major R
+ * then t (metres, model frame), sym_range int32 [B][2] (each object's set begins with the identity). Per
+ * vertex p = (x, y, z) and symmetry S, in f64 without FMA contraction:
+ *   e = ((Re0 x + Re1 y) + Re2 z) + te;  s = ((S0 x + S1 y) + S2 z) + St;  g = ((Rg0 s.x + Rg1 s.y) + Rg2 s.z) + tg
+ *   d3 = sqrt(((e-g).x^2 + (e-g).y^2) + (e-g).z^2)
+ *   du = (fx e.x / e.z + cx) - (fx g.x / g.z + cx), dv likewise; d2 = sqrt(du du + dv dv); a NaN d counts as +inf
+ *   mssd[b] = min_S max_p d3 (metres), mspd[b] = min_S max_p d2 (pixels)
+ * max and min do not depend on order: any decomposition gives the same bits (here: 16 blocks per crop, each
+ * over a contiguous slice of the symmetries, then the minimum over the slices in order; ws holds the slices'
+ * minima, krrn_bop_mssd_mspd_ws(B) doubles). sym_idx int32 [B][2] (optional) = the lowest index, local to the
+ * crop's range, of a symmetry attaining mssd / mspd (-1 if none is finite). An empty (or bad: guarded like
+ * face_range) vertex or symmetry range gives +inf. Host checks: null or overlapping buffers KRRN_EARG; B,
+ * Vtot, NStot < 1 KRRN_ESHAPE. */
+int krrn_bop_mssd_mspd_ws(int B, long long* n_doubles);
+int krrn_bop_mssd_mspd_f32(const float* verts, int Vtot, const int* vert_range, const double* R_est,
+                           const double* t_est, const double* R_gt, const double* t_gt, const float* K4,
+                           const double* syms, int NStot, const int* sym_range, int B, double* ws, double* mssd,
+                           double* mspd, int* sym_idx, void* stream);
+
 /* BPnP forward (lib/network/dnn/BPnP.py:43-44, cv2.solvePnP(SOLVEPNP_ITERATIVE,
  * useExtrinsicGuess=True)): Levenberg-Marquardt on sum_i ||pi(z_i; y) - x_i||^2 per crop, f64,
  * from y_init. pts2d [B][n][2] pixels; pts3d [n][3] shared (z_per_crop = 0) or [B][n][3];

@@ -16,14 +16,15 @@ Drop-in API (the reference's names):
     fps.farthest_point_sampling           tools/script/sample_model.py:35-48
     bpnp.BPnP / bpnp.BPnPModle            lib/network/dnn/BPnP.py (forward LM + implicit backward)
     raster.render_maps / PoseDataset(gt_maps=True)  the GT xyz / normal / region maps, rendered (this project's own)
+    bop.vsd / bop.mssd_mspd / test_epoch(bop=True)  the BOP-19 pose errors and average recalls (no reference counterpart)
 """
 from .config import CONFIG, Cfg, make_config  # noqa: F401
 from .krrn import KRRN  # noqa: F401
 from . import bpnp, dataset, fps  # noqa: F401
 from .loss import KRRNLoss  # noqa: F401
-from . import icp, raster  # noqa: F401
+from . import bop, icp, raster  # noqa: F401
 from .pose import add_icp_ops, add_umeyama_ops, get_pose, get_pose_umeyama, refine_pose_icp  # noqa: F401
 from .umeyama import estimateSimilarityTransform  # noqa: F401
 
 __all__ = ["KRRN", "KRRNLoss", "get_pose", "get_pose_umeyama", "add_umeyama_ops", "estimateSimilarityTransform",
-           "icp", "raster", "refine_pose_icp", "add_icp_ops", "make_config", "CONFIG", "Cfg"]
+           "bop", "icp", "raster", "refine_pose_icp", "add_icp_ops", "make_config", "CONFIG", "Cfg"]

@@ -1,0 +1,207 @@
+"""The BOP-19 pose errors on the GPU: VSD, MSSD and MSPD (Hodan et al., "BOP Challenge 2020 on 6D Object
+Localization", ECCV-W 2020) and the average recalls AR_VSD / AR_MSSD / AR_MSPD / AR that LineMOD and LM-O
+results are published with. Written from the published definition (include/krrn_hip.h states it,
+tests/bop_ref.py restates it in numpy); it has not been compared against the BOP toolkit's output. One known
+departure: pixels are sampled at their integer coordinates, this project's rasteriser convention.
+
+    e = vsd(verts, faces, face_range, R_est, t_est, R_gt, t_gt, K4, depth, frame, diameter)
+    # -> {"counts": int32 [B, 2 + T] = (union, inter, step_k), "e_vsd": f64 [B, T]}
+    d = mssd_mspd(verts, vert_range, R_est, t_est, R_gt, t_gt, K4, syms, sym_range)
+    # -> {"mssd": f64 [B] metres, "mspd": f64 [B] pixels, "sym_idx": int32 [B, 2]}
+    syms = symmetry_set(discrete=[...], continuous=[{"axis": [0, 0, 1], "offset": [0, 0, 0]}])   # [NS, 12]
+    errs = bop_errors(pred_r, pred_t, data, dataset)      # data = dataset.batch(idx, device, bop=True)
+    res = fold_bop(records, objlist, diameter, width)     # evaluate.test_epoch(..., bop=True)["bop"]
+
+Multi-instance matching is out of scope: LineMOD's eval has one estimate per target, so recall is
+correct / targets.
+"""
+from __future__ import annotations
+
+import math
+from typing import Dict, Optional, Sequence
+
+import numpy as np
+import torch
+
+from . import _lib
+from .runtime import h2d, ptr, stream_ptr
+
+DELTA = 0.015                                           # metres: BOP-19's visibility tolerance
+TAUS = tuple(0.05 * k for k in range(1, 11))            # VSD misalignment tolerances, fractions of the diameter
+THETAS = tuple(0.05 * k for k in range(1, 11))          # correctness thresholds of VSD and (x diameter) MSSD
+THETAS_PX = tuple(5.0 * k for k in range(1, 11))        # MSPD's, pixels at a 640-px-wide image
+MAX_T = 16                                              # kBopMaxT of csrc/bop.hip
+SYM_SPLIT = 16                                          # kBopSymSplit
+FRAME_W = 640                                           # LineMOD's frames (dataset.get_square_bbox)
+# per-crop record of the eval epoch's BOP table (f64), beside evaluate.REC
+BOP_REC = ("crop", "cls") + tuple(f"vsd_{k}" for k in range(len(TAUS))) + ("mssd", "mspd", "valid")
+_B = {k: i for i, k in enumerate(BOP_REC)}
+
+
+def _poses(dev, B, R_est, t_est, R_gt, t_gt):
+    """The four pose operands as f64 [B, 9] / [B, 3] on `dev` (converted there: no host round trip)."""
+    return [h2d(x, dev, torch.float64).reshape(B, w).contiguous()
+            for x, w in ((R_est, 9), (t_est, 3), (R_gt, 9), (t_gt, 3))]
+
+
+def vsd(verts: torch.Tensor, faces: torch.Tensor, face_range: torch.Tensor, R_est: torch.Tensor, t_est: torch.Tensor,
+        R_gt: torch.Tensor, t_gt: torch.Tensor, K4: torch.Tensor, depth: torch.Tensor, frame: torch.Tensor,
+        diameter: torch.Tensor, depth_scale: float = 1.0, delta: float = DELTA,
+        taus: Sequence[float] = TAUS) -> Dict[str, torch.Tensor]:
+    """krrn_bop_vsd_f32 for B crops (module doc). verts [Vtot, 3] / faces [Ftot, 3] / depth [F, H, W] are GPU
+    tensors; face_range [B, 2], the poses, K4 [B, 4], frame [B] and diameter [B] (metres) may be host tensors
+    (staged here). Nothing is read back: the poses may come straight from a solver's launch."""
+    if not (verts.is_cuda and faces.is_cuda and depth.is_cuda):
+        raise RuntimeError("vsd runs on the HIP path only (verts / faces / depth must be GPU tensors)")
+    dev = verts.device
+    B, T = int(face_range.reshape(-1, 2).shape[0]), len(taus)
+    if not 1 <= T <= MAX_T:
+        raise ValueError(f"1 .. {MAX_T} taus, got {T}")
+    if depth.dim() != 3:
+        raise ValueError(f"depth must be [F, H, W], got {tuple(depth.shape)}")
+    # every converted operand stays bound until the launch is enqueued (metric.add_metric's rule)
+    v = verts.to(torch.float32).contiguous()
+    f = faces.to(torch.int32).contiguous()
+    d = depth.to(torch.float32).contiguous()
+    fr = h2d(face_range.reshape(B, 2), dev, torch.int32)
+    Re, te, Rg, tg = _poses(dev, B, R_est, t_est, R_gt, t_gt)
+    K = h2d(K4.reshape(B, 4), dev, torch.float32)
+    fi = h2d(frame.reshape(B), dev, torch.int32)
+    dia = h2d(diameter.reshape(B), dev, torch.float64)
+    tau = h2d(torch.tensor(list(taus), dtype=torch.float64), dev)
+    ws = torch.empty((B, 8), dtype=torch.int32, device=dev)       # krrn_bop_vsd_ws(B)
+    counts = torch.empty((B, 2 + T), dtype=torch.int32, device=dev)
+    e = torch.empty((B, T), dtype=torch.float64, device=dev)
+    F, H, W = d.shape
+    _lib.call("krrn_bop_vsd_f32", ptr(v), v.shape[0], ptr(f), f.shape[0], ptr(fr), ptr(Re), ptr(te), ptr(Rg), ptr(tg),
+              ptr(K), ptr(d), F, H, W, ptr(fi), float(depth_scale), ptr(dia), float(delta), ptr(tau), T, B, ptr(ws),
+              ptr(counts), ptr(e), stream_ptr(dev))
+    return {"counts": counts, "e_vsd": e}
+
+
+def mssd_mspd(verts: torch.Tensor, vert_range: torch.Tensor, R_est: torch.Tensor, t_est: torch.Tensor,
+              R_gt: torch.Tensor, t_gt: torch.Tensor, K4: torch.Tensor, syms: torch.Tensor,
+              sym_range: torch.Tensor) -> Dict[str, torch.Tensor]:
+    """krrn_bop_mssd_mspd_f32 for B crops (module doc). verts [Vtot, 3] is a GPU tensor; syms [NStot, 12]
+    (symmetry_set rows, concatenated over objects), the ranges [B, 2], the poses and K4 may be host tensors."""
+    if not verts.is_cuda:
+        raise RuntimeError("mssd_mspd runs on the HIP path only (verts must be a GPU tensor)")
+    dev = verts.device
+    B = int(vert_range.reshape(-1, 2).shape[0])
+    v = verts.to(torch.float32).contiguous()
+    vr = h2d(vert_range.reshape(B, 2), dev, torch.int32)
+    sr = h2d(sym_range.reshape(B, 2), dev, torch.int32)
+    sy = h2d(syms.reshape(-1, 12), dev, torch.float64)
+    Re, te, Rg, tg = _poses(dev, B, R_est, t_est, R_gt, t_gt)
+    K = h2d(K4.reshape(B, 4), dev, torch.float32)
+    out = {"mssd": torch.empty((B,), dtype=torch.float64, device=dev),
+           "mspd": torch.empty((B,), dtype=torch.float64, device=dev),
+           "sym_idx": torch.empty((B, 2), dtype=torch.int32, device=dev)}
+    ws = torch.empty((3 * B * SYM_SPLIT,), dtype=torch.float64, device=dev)   # krrn_bop_mssd_mspd_ws(B)
+    _lib.call("krrn_bop_mssd_mspd_f32", ptr(v), v.shape[0], ptr(vr), ptr(Re), ptr(te), ptr(Rg), ptr(tg), ptr(K), ptr(sy),
+              sy.shape[0], ptr(sr), B, ptr(ws), ptr(out["mssd"]), ptr(out["mspd"]), ptr(out["sym_idx"]),
+              stream_ptr(dev))
+    return out
+
+
+def _axis_rotation(axis, angle: float) -> np.ndarray:
+    a = np.asarray(axis, np.float64).reshape(3)
+    a = a / np.linalg.norm(a)
+    Kx = np.array([[0.0, -a[2], a[1]], [a[2], 0.0, -a[0]], [-a[1], a[0], 0.0]])
+    return np.eye(3) + math.sin(angle) * Kx + (1.0 - math.cos(angle)) * (Kx @ Kx)   # Rodrigues
+
+
+def symmetry_set(discrete=None, continuous=None, diameter_m: Optional[float] = None,
+                 max_step: float = 0.01) -> np.ndarray:
+    """The symmetry transformations of one object, f64 [NS, 12] = row-major R then t in metres, identity
+    first, without duplicates. Inputs in BOP's models_info convention: `discrete` a list of 4 x 4 row-major
+    matrices (16 numbers each, or [4, 4]) with translations in mm; `continuous` a list of {"axis": [3],
+    "offset": [3] in mm}. Each continuous axis contributes ceil(pi / max_step) equal rotation steps about
+    `axis` through `offset` (the first is the identity), combined with every discrete symmetry. max_step is
+    the fraction of the object's diameter that the point farthest from the axis (at most diameter / 2 away)
+    may travel per step, so the count does not depend on the diameter itself: diameter_m is accepted for the
+    models_info call shape and not used."""
+    eye = np.eye(4)
+    disc = [eye]
+    for m in (discrete or []):
+        T = np.asarray(m, np.float64).reshape(4, 4).copy()
+        T[:3, 3] /= 1000.0
+        disc.append(T)
+    cont = [eye]
+    for c in (continuous or []):
+        off = np.asarray(c.get("offset", (0.0, 0.0, 0.0)), np.float64).reshape(3) / 1000.0
+        n = int(math.ceil(math.pi / max_step))
+        steps = []
+        for base in cont:                                   # several axes: every combination
+            for i in range(n):
+                T = np.eye(4)
+                T[:3, :3] = _axis_rotation(c["axis"], 2.0 * math.pi * i / n)
+                T[:3, 3] = off - T[:3, :3] @ off
+                steps.append(T @ base)
+        cont = steps
+    out = []
+    for d in disc:
+        for c in cont:
+            T = c @ d
+            if not any(np.abs(T - o).max() < 1e-9 for o in out):
+                out.append(T)
+    return np.stack([np.concatenate([T[:3, :3].reshape(9), T[:3, 3]]) for T in out])
+
+
+def bop_errors(pred_r: torch.Tensor, pred_t: torch.Tensor, data: Dict[str, torch.Tensor], dataset,
+               delta: float = DELTA, taus: Sequence[float] = TAUS) -> Dict[str, torch.Tensor]:
+    """The three errors of one batch's estimates (pred_r [B, 3, 3], pred_t [B, 3], GPU) against its GT poses,
+    as device tensors: {"vsd": f64 [B, T], "mssd": f64 [B] metres, "mspd": f64 [B] pixels}. `data` is
+    dataset.batch(indices, device, bop=True): it carries the observed depth frames, each crop's frame index
+    and its object's face / vertex / symmetry ranges; the meshes and symmetry sets are the dataset's, resident
+    on the device. Queued on the current stream, nothing is read back."""
+    if "bop_depth" not in data:
+        raise ValueError("bop_errors needs a batch made with dataset.batch(indices, device, bop=True)")
+    dev = pred_t.device
+    if dev.type != "cuda":
+        raise RuntimeError("bop_errors runs on the HIP path only (GPU tensors)")
+    mesh = dataset._mesh_for(dev)
+    B = pred_t.shape[0]
+    dia = h2d(torch.tensor(dataset.diameter, dtype=torch.float64), dev)[h2d(data["cls_id"].reshape(B), dev)]
+    Rg, tg = data["target_r"], data["target_t"]
+    v = vsd(mesh["verts"], mesh["faces"], data["bop_face_range"], pred_r, pred_t, Rg, tg, data["intrinsic"],
+            data["bop_depth"], data["bop_frame"], dia, 1.0, delta, taus)
+    m = mssd_mspd(mesh["verts"], data["bop_vert_range"], pred_r, pred_t, Rg, tg, data["intrinsic"], mesh["syms"],
+                  data["bop_sym_range"])
+    return {"vsd": v["e_vsd"], "mssd": m["mssd"], "mspd": m["mspd"]}
+
+
+def _recalls(rec: np.ndarray, dia: np.ndarray, width: float) -> Dict[str, float]:
+    n = len(rec)
+    if n == 0:
+        return {"AR_VSD": 0.0, "AR_MSSD": 0.0, "AR_MSPD": 0.0, "AR": 0.0, "count": 0}
+    T = len(TAUS)
+    e = rec[:, _B["vsd_0"]:_B["vsd_0"] + T]
+    th = np.asarray(THETAS)
+    ar_vsd = float(np.mean([(e < t).sum() / (n * T) for t in th]))             # 10 taus x 10 thresholds
+    ar_mssd = float(np.mean([(rec[:, _B["mssd"]] < t * dia).sum() / n for t in th]))
+    ar_mspd = float(np.mean([(rec[:, _B["mspd"]] < t * (width / 640.0)).sum() / n for t in THETAS_PX]))
+    return {"AR_VSD": ar_vsd, "AR_MSSD": ar_mssd, "AR_MSPD": ar_mspd, "AR": (ar_vsd + ar_mssd + ar_mspd) / 3.0,
+            "count": int(n)}
+
+
+def fold_bop(records, objlist: Sequence[int], diameter: Sequence[float], width: float = FRAME_W) -> Dict[str, object]:
+    """The BOP-19 average recalls over per-crop BOP_REC records (any order, pad rows valid = 0), folded in
+    global crop order like evaluate.fold_records. An estimate is correct w.r.t. an error when the error is
+    strictly below the threshold; recall = correct / targets (one estimate per target).
+      AR_VSD   mean over the 10 taus x 10 thresholds 0.05 .. 0.5 of the share of crops with e_vsd < threshold
+      AR_MSSD  mean over thresholds 0.05 .. 0.5 x the object's diameter
+      AR_MSPD  mean over thresholds 5 .. 50 px x (width / 640)
+      AR       the mean of the three
+    Returns {"AR_VSD", "AR_MSSD", "AR_MSPD", "AR", "count"} over all crops pooled, plus "per_obj": {obj id:
+    the same five keys} for the objects that occur."""
+    rec = records.numpy() if isinstance(records, torch.Tensor) else np.asarray(records, np.float64)
+    rec = rec.reshape(-1, len(BOP_REC))
+    rec = rec[rec[:, _B["valid"]] > 0]
+    rec = rec[np.argsort(rec[:, _B["crop"]], kind="stable")]
+    cls = rec[:, _B["cls"]].astype(np.int64)
+    dia = np.asarray(diameter, np.float64)[cls] if len(rec) else np.zeros((0,))
+    out = _recalls(rec, dia, float(width))
+    out["per_obj"] = {objlist[int(c)]: _recalls(rec[cls == c], dia[cls == c], float(width))
+                      for c in dict.fromkeys(cls.tolist())}
+    return out

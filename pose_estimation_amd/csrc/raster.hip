@@ -29,34 +29,14 @@
 // indices are global and a batch mixes objects, so that workspace would be B x Vtot, and the redundant
 // projections (about 6 f64 divisions a face and tile) are cheaper than its traffic. The winner's
 // vertices are projected once more for the normal: the same operations give the same bits.
-#include <math.h>
-
-#include "krrn_common.h"
+// The depth part (camera transform, edge function, face setup, compaction, per-pixel walk) lives in
+// krrn_raster.h, shared with the VSD kernel of bop.hip.
+#include "krrn_raster.h"
 
 namespace {
 
-constexpr int kRastTile = 16;
-constexpr int kRastThreads = kRastTile * kRastTile;  // one thread per pixel of the tile; also the face chunk
-constexpr int kRastWaves = kRastThreads / 64;
-constexpr int kRastSetup = 14;                       // doubles per compacted face
 constexpr int kRastMaxS = 480;
 constexpr int kRastMaxNR = 256;
-constexpr double kRastNear = 1e-3;
-
-struct RastCam {
-  double r[9], t[3], fx, fy, cx, cy;
-};
-
-__device__ __forceinline__ void rast_camera(const RastCam& cam, const float* v, double (&c)[3]) {
-  const double x = (double)v[0], y = (double)v[1], z = (double)v[2];
-  c[0] = ((cam.r[0] * x + cam.r[1] * y) + cam.r[2] * z) + cam.t[0];
-  c[1] = ((cam.r[3] * x + cam.r[4] * y) + cam.r[5] * z) + cam.t[1];
-  c[2] = ((cam.r[6] * x + cam.r[7] * y) + cam.r[8] * z) + cam.t[2];
-}
-
-__device__ __forceinline__ double rast_edge(double au, double av, double bu, double bv, double pu, double pv) {
-  return (bu - au) * (pv - av) - (bv - av) * (pu - au);
-}
 
 __global__ __launch_bounds__(kRastThreads) void raster_maps_kernel(
     const float* __restrict__ verts, int Vtot, const int* __restrict__ faces, int Ftot,
@@ -70,24 +50,17 @@ __global__ __launch_bounds__(kRastThreads) void raster_maps_kernel(
   __shared__ int s_wcnt[kRastWaves];
 
   const int b = blockIdx.z, tid = threadIdx.x;
-  const int lane = tid & 63, wave = tid >> 6;
   const int x = blockIdx.x * kRastTile + (tid & (kRastTile - 1));
   const int y = blockIdx.y * kRastTile + (tid >> 4);
   const bool inside = x < S && y < S;
 
   RastCam cam;
-  for (int i = 0; i < 9; ++i) cam.r[i] = R[9 * b + i];
-  for (int i = 0; i < 3; ++i) cam.t[i] = t[3 * b + i];
-  cam.fx = (double)K4[4 * b + 0];
-  cam.fy = (double)K4[4 * b + 1];
-  cam.cx = (double)K4[4 * b + 2];
-  cam.cy = (double)K4[4 * b + 3];
+  rast_load_cam(cam, R, t, K4, b);
   const int rmin = rc[2 * b], cmin = rc[2 * b + 1];
   // the crop's faces, clamped to the face array (face_range is device memory: nothing on the host saw it)
-  long long f0 = face_range[2 * b], nfl = face_range[2 * b + 1];
-  if (f0 < 0 || nfl < 0 || f0 > Ftot) nfl = 0;
-  if (f0 + nfl > Ftot) nfl = Ftot - f0;
-  const int nf = (int)nfl;
+  long long f0;
+  int nf;
+  rast_range(face_range, b, Ftot, f0, nf);
 
   for (int i = tid; i < NR * 3; i += kRastThreads) s_rp[i] = (double)region_pts[(size_t)b * NR * 3 + i];
 
@@ -97,73 +70,10 @@ __global__ __launch_bounds__(kRastThreads) void raster_maps_kernel(
   const double tu0 = (double)(cmin + lx), tu1 = (double)(cmin + min(lx + kRastTile, S) - 1);
   const double tv0 = (double)(rmin + ly), tv1 = (double)(rmin + min(ly + kRastTile, S) - 1);
 
-  double best_z = INFINITY, bq0 = 0.0, bq1 = 0.0, bq2 = 0.0;
-  int best_f = -1;
-
-  for (int base = 0; base < nf; base += kRastThreads) {  // nf is uniform over the block
-    const int fi = base + tid;
-    bool keep = false;
-    double su[3], sv[3], sz[3], A = 0.0, umin = 0.0, umax = 0.0, vmin = 0.0, vmax = 0.0;
-    if (fi < nf) {
-      const int* fv = faces + (size_t)(f0 + fi) * 3;
-      const int i0 = fv[0], i1 = fv[1], i2 = fv[2];
-      if (i0 >= 0 && i0 < Vtot && i1 >= 0 && i1 < Vtot && i2 >= 0 && i2 < Vtot) {
-        const int iv[3] = {i0, i1, i2};
-        bool front = true;
-        for (int k = 0; k < 3; ++k) {
-          double c[3];
-          rast_camera(cam, verts + (size_t)iv[k] * 3, c);
-          front = front && (c[2] > kRastNear);  // false for NaN too
-          su[k] = cam.fx * c[0] / c[2] + cam.cx;
-          sv[k] = cam.fy * c[1] / c[2] + cam.cy;
-          sz[k] = c[2];
-        }
-        A = rast_edge(su[0], sv[0], su[1], sv[1], su[2], sv[2]);
-        umin = fmin(fmin(su[0], su[1]), su[2]);
-        umax = fmax(fmax(su[0], su[1]), su[2]);
-        vmin = fmin(fmin(sv[0], sv[1]), sv[2]);
-        vmax = fmax(fmax(sv[0], sv[1]), sv[2]);
-        keep = front && A != 0.0 && isfinite(A) && umax >= tu0 && umin <= tu1 && vmax >= tv0 && vmin <= tv1;
-      }
-    }
-    // order-preserving compaction: the wave's ballot gives the rank inside the wave, the waves go in order
-    const unsigned long long bal = __ballot(keep);
-    if (lane == 0) s_wcnt[wave] = __popcll(bal);
-    __syncthreads();
-    int off = 0, total = 0;
-    for (int w = 0; w < kRastWaves; ++w) {
-      const int c = s_wcnt[w];
-      off += w < wave ? c : 0;
-      total += c;
-    }
-    if (keep) {
-      const int slot = off + __popcll(bal & ((1ull << lane) - 1ull));  // < 256
-      double* s = s_setup + slot * kRastSetup;
-      s[0] = su[0], s[1] = sv[0], s[2] = su[1], s[3] = sv[1], s[4] = su[2], s[5] = sv[2];
-      s[6] = sz[0], s[7] = sz[1], s[8] = sz[2], s[9] = A;
-      s[10] = umin, s[11] = umax, s[12] = vmin, s[13] = vmax;
-      s_id[slot] = fi;
-    }
-    __syncthreads();
-    if (inside) {
-      for (int j = 0; j < total; ++j) {
-        const double* s = s_setup + j * kRastSetup;
-        if (!(pu >= s[10] && pu <= s[11] && pv >= s[12] && pv <= s[13])) continue;
-        const double a = s[9];
-        const double w0 = rast_edge(s[2], s[3], s[4], s[5], pu, pv) / a;
-        const double w1 = rast_edge(s[4], s[5], s[0], s[1], pu, pv) / a;
-        const double w2 = rast_edge(s[0], s[1], s[2], s[3], pu, pv) / a;
-        if (!(w0 >= 0.0 && w1 >= 0.0 && w2 >= 0.0)) continue;
-        const double q0 = w0 / s[6], q1 = w1 / s[7], q2 = w2 / s[8];
-        const double z = 1.0 / ((q0 + q1) + q2);
-        if (z < best_z) {
-          best_z = z, best_f = s_id[j];
-          bq0 = q0, bq1 = q1, bq2 = q2;
-        }
-      }
-    }
-    __syncthreads();  // the next chunk rewrites the list
-  }
+  RastHit hit;  // krrn_raster.h: the chunked, order-preserving compaction and the per-pixel walk
+  rast_depth_walk(cam, verts, Vtot, faces, f0, nf, tu0, tu1, tv0, tv1, pu, pv, inside, s_setup, s_id, s_wcnt, hit);
+  const double best_z = hit.z, bq0 = hit.q0, bq1 = hit.q1, bq2 = hit.q2;
+  const int best_f = hit.f;
   __syncthreads();  // s_rp (also when the crop has no face)
   if (!inside) return;
 
@@ -232,27 +142,6 @@ __global__ void gt_maps_finish_kernel(const float* __restrict__ coord, const int
   mask[o1] = on ? 1.f : 0.f;
   multi_cls_mask[o1] = on ? cls[b] + 1 : 0;
   if (mask_obj) mask_obj[o1] = face[o1] >= 0 ? 1.f : 0.f;
-}
-
-struct Span {
-  const void* p;
-  size_t n;
-};
-
-// true when a non-null output span overlaps any other span
-static bool rast_overlap(const Span* outs, int no, const Span* ins, int ni) {
-  auto hit = [](const Span& a, const Span& b) {
-    if (!a.p || !b.p) return false;
-    const uintptr_t a0 = (uintptr_t)a.p, b0 = (uintptr_t)b.p;
-    return a0 < b0 + b.n && b0 < a0 + a.n;
-  };
-  for (int i = 0; i < no; ++i) {
-    for (int j = i + 1; j < no; ++j)
-      if (hit(outs[i], outs[j])) return true;
-    for (int j = 0; j < ni; ++j)
-      if (hit(outs[i], ins[j])) return true;
-  }
-  return false;
 }
 
 }  // namespace

@@ -22,7 +22,8 @@ logged loss terms and the `mask_obj` factor of the point mask. By default the ma
 mask_label * mask_depth (documented deviation) and the loss keys are absent; with `gt_maps=True` the
 maps are rendered on the GPU from the PLY's faces, the GT pose and K (raster.py), the mask is the
 reference's label * obj * depth, and every batch carries xyz, normal, region, mask, multi_cls_mask,
-mask_obj, region_point, coordinate_choosed and depth_render.
+mask_obj, region_point, coordinate_choosed and depth_render. `meshes=True` only loads the meshes
+(faces, all vertices, symmetry sets) for the BOP pose errors (bop.py): `batch(idx, device, bop=True)`.
 
 `root=None` (the default; no LineMOD data ships with the reference and there is no network)
 serves seeded synthetic 640x480 RGB-D frames built like the real ones (an object mask inside a
@@ -46,6 +47,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .bop import symmetry_set
 from .config import CONFIG, LM_OBJLIST, OBJ_DICT, SYM_OBJ, models_info
 from .raster import N_REGIONS, finish_maps, region_points, render_maps
 from .runtime import h2d, ptr, stream_ptr
@@ -278,9 +280,18 @@ class _LinemodTree:
         self.root, self.mode = root, mode
         self.items: List[Dict[str, object]] = []
         self.model_points: Dict[int, np.ndarray] = {}
-        # meshes: per object the full vertex set (metres) and the triangles, for GT-map rendering; apart
-        # from the n_model_pts subsample below, which ADD(-S) uses
+        # meshes: per object the full vertex set (metres) and the triangles, for GT-map rendering and the BOP
+        # errors; apart from the n_model_pts subsample below, which ADD(-S) uses
         self.mesh: Dict[int, Tuple[np.ndarray, np.ndarray]] = {}
+        # per object its symmetry transformations [NS, 12] (bop.symmetry_set), from the optional keys
+        # symmetries_discrete / symmetries_continuous of the tree's models/models_info.yml (BOP's convention);
+        # a stock Linemod_preprocessed tree has none: the identity only
+        self.symmetries: Dict[int, np.ndarray] = {}
+        tree_info = {}
+        ipath = os.path.join(root, "models", "models_info.yml")
+        if meshes and os.path.exists(ipath):
+            with open(ipath) as f:
+                tree_info = {int(k): v for k, v in (yaml.safe_load(f) or {}).items()}
         rng = np.random.default_rng(seed)
         split = "train.txt" if mode == "train" else "test.txt"
         for obj in objlist:
@@ -299,11 +310,13 @@ class _LinemodTree:
             if meshes:
                 tri = ply_faces(os.path.join(root, "models", f"obj_{obj:02d}.ply"))
                 if len(tri) == 0:
-                    raise ValueError(f"gt_maps=True renders the GT maps from the mesh, but obj_{obj:02d}.ply has no "
+                    raise ValueError(f"gt_maps=True / meshes=True render from the mesh, but obj_{obj:02d}.ply has no "
                                      "faces (element face 0)")
                 if tri.min() < 0 or tri.max() >= len(pts):
                     raise ValueError(f"obj_{obj:02d}.ply: a face index lies outside its {len(pts)} vertices")
                 self.mesh[obj] = (pts.astype(np.float32), tri)
+                oi = tree_info.get(obj, {})
+                self.symmetries[obj] = symmetry_set(oi.get("symmetries_discrete"), oi.get("symmetries_continuous"))
             if len(pts) < n_model_pts:
                 # the reference's random.sample(range(len(pts)), len(pts) - num_pt_mesh_large) raises here
                 # too (batchdataset.py:700-704): every crop's ADD(-S) runs over exactly n_model_pts points
@@ -337,16 +350,22 @@ class PoseDataset(torch.utils.data.Dataset):
     """The reference's constructor signature (batchdataset.py:34); `root` = a LineMOD tree, or
     None for synthetic frames (module doc). Eval only: add_noise / noise_trans / num_kps are
     accepted and unused. gt_maps=True also serves the per-pixel ground truth, rendered from the tree's
-    meshes (needs a tree whose PLYs have faces; ValueError otherwise); the default changes nothing."""
+    meshes (needs a tree whose PLYs have faces; ValueError otherwise); the default changes nothing.
+    meshes=True loads the meshes (vertices, faces, symmetry sets) without rendering GT maps, which is what
+    batch(..., bop=True) and bop.bop_errors need; gt_maps=True implies it. The symmetry sets come from the
+    optional keys symmetries_discrete / symmetries_continuous of the tree's models/models_info.yml; a stock
+    Linemod_preprocessed tree has none, so every object, eggbox and glue included, then gets the identity
+    only and MSSD / MSPD are the plain maximum distances."""
 
     def __init__(self, mode: str = "test", num_point: int = 1000, add_noise: bool = False, root: Optional[str] = None,
                  noise_trans: float = 0.0, num_kps: int = 8, cls_type: Optional[str] = None, cfg=CONFIG,
                  num_frames: int = 256, seed: int = 0, sizes: Optional[Sequence[int]] = None,
-                 n_model_pts: int = 2600, io_threads: int = 8, gt_maps: bool = False):
+                 n_model_pts: int = 2600, io_threads: int = 8, gt_maps: bool = False, meshes: bool = False):
         self.mode, self.num_point, self.cfg, self.root = mode, num_point, cfg, root
         self.gt_maps = bool(gt_maps)
-        if self.gt_maps and root is None:
-            raise ValueError("gt_maps=True renders the GT maps from the objects' meshes and needs a LineMOD tree "
+        self.meshes = bool(meshes) or self.gt_maps
+        if self.meshes and root is None:
+            raise ValueError("gt_maps=True / meshes=True render from the objects' meshes and need a LineMOD tree "
                              "(root=None serves synthetic frames, which have no mesh)")
         if cls_type in (None, "all"):
             self.objlist = list(LM_OBJLIST)
@@ -357,7 +376,7 @@ class PoseDataset(torch.utils.data.Dataset):
         self.diameter = [info[o]["diameter"] / 1000.0 for o in self.objlist]
         self.io_threads = io_threads
         if root is not None:
-            self.tree = _LinemodTree(root, mode, self.objlist, n_model_pts, seed, meshes=self.gt_maps)
+            self.tree = _LinemodTree(root, mode, self.objlist, n_model_pts, seed, meshes=self.meshes)
             self.frames_np = None
             self.boxes = [get_square_bbox(it["bbox"]) for it in self.tree.items]
         else:
@@ -411,21 +430,27 @@ class PoseDataset(torch.utils.data.Dataset):
 
     def _mesh_for(self, device) -> Dict[str, object]:
         """The objects' meshes on `device`, concatenated (faces index the concatenated vertices), each
-        object's face range, its 64 FPS region points (metres, from vertex 0: sample_model.py:33-46) and its
-        `region_point` rows (a [0, 0, 0] row, then the normalised points, batchdataset.py:723-728). Built once
-        per device."""
+        object's face range (`range`), vertex range (`vrange`) and symmetry range (`srange`) into the
+        concatenated symmetry sets (`syms` f64 [NStot, 12]), and with gt_maps its 64 FPS region points
+        (metres, from vertex 0: sample_model.py:33-46) and its `region_point` rows (a [0, 0, 0] row, then the
+        normalised points, batchdataset.py:723-728). Built once per device."""
         key = str(device)
         if key not in self._dev_mesh:
             info = models_info()
-            vs, fs, frange, v0, f0 = [], [], {}, 0, 0
+            if self.tree is None or not self.tree.mesh:
+                raise ValueError("this dataset holds no meshes: build it on a LineMOD tree with meshes=True (or "
+                                 "gt_maps=True); root=None serves synthetic frames, which have no mesh")
+            vs, fs, ss, frange, vrange, srange, v0, f0, s0 = [], [], [], {}, {}, {}, 0, 0, 0
             for obj in self.objlist:
                 v, f = self.tree.mesh[obj]
+                sy = self.tree.symmetries[obj]
                 vs.append(v)
                 fs.append(f + v0)
-                frange[obj] = (f0, len(f))
-                v0, f0 = v0 + len(v), f0 + len(f)
+                ss.append(sy)
+                frange[obj], vrange[obj], srange[obj] = (f0, len(f)), (v0, len(v)), (s0, len(sy))
+                v0, f0, s0 = v0 + len(v), f0 + len(f), s0 + len(sy)
             region, region_point = {}, {}
-            for obj in self.objlist:
+            for obj in self.objlist if self.gt_maps else ():
                 pts = region_points(h2d(torch.from_numpy(self.tree.mesh[obj][0]), device), N_REGIONS)
                 lf, ext = np.array(info[obj]["min"]) / 1000.0, np.array(info[obj]["size"]) / 1000.0
                 nrm = (pts.cpu().numpy().astype(np.float64) - lf) / ext
@@ -434,17 +459,25 @@ class PoseDataset(torch.utils.data.Dataset):
                                         device)
             self._dev_mesh[key] = {"verts": h2d(torch.from_numpy(np.concatenate(vs)), device),
                                    "faces": h2d(torch.from_numpy(np.concatenate(fs).astype(np.int32)), device),
-                                   "range": frange, "region": region, "region_point": region_point}
+                                   "syms": h2d(torch.from_numpy(np.concatenate(ss)), device),
+                                   "range": frange, "vrange": vrange, "srange": srange, "region": region,
+                                   "region_point": region_point}
         return self._dev_mesh[key]
 
-    def batch(self, indices: Sequence[int], device) -> Dict[str, torch.Tensor]:
+    def batch(self, indices: Sequence[int], device, bop: bool = False) -> Dict[str, torch.Tensor]:
         """The eval keys of batchdataset.py:730-771 for `indices` (one crop size), collated. With gt_maps
         also the per-pixel GT of :755-759 (xyz, normal, region, mask, multi_cls_mask), mask_obj,
         region_point, coordinate_choosed and depth_render: the object's mesh is rendered under the GT pose
         (raster.render_maps), its coverage is the point mask's `mask_obj` factor (:667-670), and
-        raster.finish_maps applies the loader's masking."""
+        raster.finish_maps applies the loader's masking. bop=True (needs meshes; ValueError otherwise) adds
+        what bop.bop_errors reads: bop_depth [F, H, W] the observed depth frames (metres), bop_frame int32 [B]
+        each crop's frame, bop_face_range / bop_vert_range / bop_sym_range int32 [B, 2] its object's ranges in
+        the dataset's resident meshes and symmetry sets. The other keys are unchanged."""
         device = torch.device(device)
         idx = list(indices)
+        if bop and not self.meshes:
+            raise ValueError("batch(..., bop=True) needs the objects' meshes: build the dataset on a LineMOD tree "
+                             "with meshes=True (or gt_maps=True); root=None serves synthetic frames, which have none")
         if self.tree is not None:
             fr = self._read_frames(idx, device)
             fidx = list(range(len(idx)))
@@ -495,6 +528,12 @@ class PoseDataset(torch.utils.data.Dataset):
             _lib.call("krrn_points_gather_f32", ptr(out["cloud"]), ptr(maps["coord"]), ptr(out["normal"]),
                       ptr(out["choose"]), B, N, S, S, ptr(p9), stream_ptr(device))
             out["coordinate_choosed"] = p9[:, :, 3:6]
+        if bop:
+            mesh = self._mesh_for(device)
+            rng = lambda k: h2d(torch.tensor([mesh[k][m[0]] for m in metas], dtype=torch.int32), device)  # noqa: E731
+            out.update({"bop_depth": fr["depth"], "bop_frame": h2d(torch.tensor(fidx, dtype=torch.int32), device),
+                        "bop_face_range": rng("range"), "bop_vert_range": rng("vrange"),
+                        "bop_sym_range": rng("srange")})
         return out
 
     def __getitem__(self, i: int) -> Dict[str, torch.Tensor]:

@@ -32,6 +32,7 @@ import torch
 import torch.distributed as dist
 
 from . import distributed as kd
+from .bop import BOP_REC, FRAME_W, TAUS, bop_errors, fold_bop
 from .dataset import PoseDataset
 from .krrn import KRRN
 from .loss import map_losses
@@ -62,7 +63,7 @@ def _batches(buckets: Dict[int, List[int]], bs: int):
 @torch.no_grad()
 def eval_records(model: KRRN, dataset: PoseDataset, indices: Dict[int, List[int]], bs: int, device,
                  opt_pose: bool = True, with_loss: bool = True, pose_solver: str = "pnp",
-                 refine: Optional[str] = None) -> torch.Tensor:
+                 refine: Optional[str] = None, bop: bool = False):
     """Run the eval path over {S: [crop indices]} in batches of <= bs; returns f64 [n, len(REC)]
     (rows in the order evaluated). Every batch's inputs, forward, pose and ADD(-S) are queued on
     the device without a host round trip; the per-crop records are read back once at the end (the
@@ -81,7 +82,12 @@ def eval_records(model: KRRN, dataset: PoseDataset, indices: Dict[int, List[int]
     refine: None (the reference's loop), or "icp": the base pose (base_r, base_t) and, with opt_pose, the
     final pose (base_r, pred_t) are each polished by pose.refine_pose_icp against the crop's cloud on the
     pose stream before their ADD(-S) and rotation / translation errors (two more launches per batch; the
-    final pose then carries its own refined R). max_dist = icp.DIST_FRAC x the object's diameter."""
+    final pose then carries its own refined R). max_dist = icp.DIST_FRAC x the object's diameter.
+
+    bop: also the BOP-19 errors (bop.bop_errors: VSD, MSSD, MSPD) of the final pose, i.e. (fin_r, pred_t) with
+    opt_pose and the base pose without, as test_dis chooses; queued on the pose stream after add_metric and
+    read back with everything else at the end. Needs a dataset with meshes. The return value is then the pair
+    (records, f64 [n, len(bop.BOP_REC)] in the same row order); every number of `records` is unchanged."""
     if pose_solver not in ("pnp", "umeyama"):
         raise ValueError(f"pose_solver must be 'pnp' or 'umeyama', got {pose_solver!r}")
     if refine not in (None, "icp"):
@@ -89,6 +95,7 @@ def eval_records(model: KRRN, dataset: PoseDataset, indices: Dict[int, List[int]
     solve_pose = get_pose if pose_solver == "pnp" else get_pose_umeyama
     metric = Metric(dataset.sym_obj)
     pending = []
+    bop_pending = []   # per batch, with bop: bop_errors' dict of device tensors
     batches = list(_batches(indices, bs))
     device = torch.device(device)
     dia = torch.tensor(dataset.diameter, dtype=torch.float32).to(device) if refine else None  # [classes], metres
@@ -99,7 +106,7 @@ def eval_records(model: KRRN, dataset: PoseDataset, indices: Dict[int, List[int]
     def build(j):
         side.wait_stream(main)  # the inputs' pinned staging and allocations follow earlier work
         with torch.cuda.stream(side):
-            d = dataset.batch(batches[j][1], device)
+            d = dataset.batch(batches[j][1], device, bop=True) if bop else dataset.batch(batches[j][1], device)
             ev = torch.cuda.Event()
             ev.record(side)
         return d, ev
@@ -146,6 +153,9 @@ def eval_records(model: KRRN, dataset: PoseDataset, indices: Dict[int, List[int]
                     # reg = final = (PnP R, TBase t) (trainer.py:198-201)
                     add_f = add_metric(fin_r, pred_t, data["model_points"], data["target"], data["cls_id"],
                                        metric.sys)
+                if bop:
+                    bop_pending.append(bop_errors(fin_r, pred_t, data, dataset) if opt_pose else
+                                       bop_errors(base_r, base_t.reshape(B, 3), data, dataset))
             pending.append(_Batch(idx, data["cls_id"], data["target_r"], data["target_t"], base_r, base_t, pred_t,
                                   fin_r, add_b, add_f, lc))
     finally:
@@ -155,8 +165,12 @@ def eval_records(model: KRRN, dataset: PoseDataset, indices: Dict[int, List[int]
         for t in (p.base_r, p.base_t, p.add_b, p.add_f) + ((p.pred_t, p.fin_r) if refine else ()):
             if t is not None:
                 t.record_stream(main)
+    for e in bop_pending:
+        for t in e.values():
+            t.record_stream(main)
     if not pending:
-        return torch.zeros((0, len(REC)), dtype=torch.float64)
+        empty = torch.zeros((0, len(REC)), dtype=torch.float64)
+        return (empty, torch.zeros((0, len(BOP_REC)), dtype=torch.float64)) if bop else empty
     # one read-back and one vectorised host pass for the whole epoch: per batch, the rotation /
     # translation errors' six small copies and ~60 CPU ops ran after the GPU had drained (a serial
     # host tail of ~1 ms per batch); every quantity is per crop, so the values are the same
@@ -178,7 +192,15 @@ def eval_records(model: KRRN, dataset: PoseDataset, indices: Dict[int, List[int]
         rec[:, _R["add_f"]] = cat("add_f", 1).reshape(n).cpu().numpy()
         fin_r = cat("fin_r", 9) if refine else base_r
         rec[:, _R["r_f"]], rec[:, _R["t_f"]] = rt_errors(fin_r, cat("pred_t", 3), tr, tt)
-    return torch.from_numpy(rec)
+    if not bop:
+        return torch.from_numpy(rec)
+    T = len(TAUS)
+    brec = np.zeros((n, len(BOP_REC)), dtype=np.float64)
+    brec[:, 0], brec[:, 1], brec[:, -1] = rec[:, _R["crop"]], rec[:, _R["cls"]], 1.0
+    brec[:, 2:2 + T] = torch.cat([e["vsd"] for e in bop_pending]).cpu().numpy()
+    brec[:, 2 + T] = torch.cat([e["mssd"] for e in bop_pending]).cpu().numpy()
+    brec[:, 3 + T] = torch.cat([e["mspd"] for e in bop_pending]).cpu().numpy()
+    return torch.from_numpy(rec), torch.from_numpy(brec)
 
 
 def fold_records(records: torch.Tensor, objlist: Sequence[int], diameter: Sequence[float], opt_pose: bool,
@@ -234,13 +256,14 @@ def fold_records(records: torch.Tensor, objlist: Sequence[int], diameter: Sequen
 
 
 def gather_epoch_records(local: torch.Tensor, shard_sizes: Sequence[int], device, group=None) -> torch.Tensor:
-    """All-gather every rank's [n_r, len(REC)] records (padded to max(shard_sizes) rows, pad rows
-    have valid = 0) -> all ranks' records, rank-major."""
+    """All-gather every rank's [n_r, width] records (padded to max(shard_sizes) rows, pad rows have
+    valid = 0) -> all ranks' records, rank-major. The width is the table's own: len(REC) for the epoch's
+    records, len(bop.BOP_REC) for its BOP table; `valid` is the last column of both."""
     world = len(shard_sizes)
     if world == 1:
         return local
     m = max(shard_sizes)
-    pad = torch.zeros((max(m, 1), len(REC)), dtype=torch.float64)
+    pad = torch.zeros((max(m, 1), local.shape[1]), dtype=torch.float64)
     pad[:local.shape[0]] = local
     backend = dist.get_backend(group)
     buf = pad.to(device) if backend == "nccl" else pad
@@ -251,13 +274,16 @@ def gather_epoch_records(local: torch.Tensor, shard_sizes: Sequence[int], device
 @torch.no_grad()
 def test_epoch(model: KRRN, dataset: PoseDataset, bs: int = 64, device=None, opt_pose: bool = True,
                criterion=None, world: Optional[int] = None, rank: Optional[int] = None,
-               group=None, pose_solver: str = "pnp", refine: Optional[str] = None) -> Dict[str, object]:
+               group=None, pose_solver: str = "pnp", refine: Optional[str] = None,
+               bop: bool = False) -> Dict[str, object]:
     """Trainer.test_epoch over `dataset`. world/rank default to the initialised process group
     (1/0 without one). `criterion` enables the per-crop map-loss terms (dis_xyz / dis_mask /
     dis_normal) when the batches carry GT maps, i.e. for a PoseDataset built with gt_maps=True (a
     stock LineMOD tree is enough: the maps are rendered from its PLYs); without them the columns stay
     0. The reference always evaluates it (:167).
-    `pose_solver` and `refine` as in eval_records."""
+    `pose_solver` and `refine` as in eval_records. `bop` (off by default; needs a dataset with meshes) adds one
+    key, "bop": bop.fold_bop's BOP-19 average recalls AR_VSD / AR_MSSD / AR_MSPD / AR of the final pose, per
+    object and overall; every other key is unchanged, bit for bit."""
     device = torch.device(device) if device is not None else next(model.parameters()).device
     if world is None:
         world = dist.get_world_size(group) if dist.is_initialized() else 1
@@ -268,11 +294,17 @@ def test_epoch(model: KRRN, dataset: PoseDataset, bs: int = 64, device=None, opt
     sizes = [dataset.crop_size(i) for i in range(len(dataset))]
     mine = kd.bucket_shard(sizes, world, rank)
     local = eval_records(model, dataset, mine, bs, device, opt_pose=opt_pose, with_loss=criterion is not None,
-                         pose_solver=pose_solver, refine=refine)
+                         pose_solver=pose_solver, refine=refine, **({"bop": True} if bop else {}))
+    local_bop = None
+    if bop:
+        local, local_bop = local
     shard_sizes = [sum(len(v) for v in kd.bucket_shard(sizes, world, r).values()) for r in range(world)]
     allrec = gather_epoch_records(local, shard_sizes, device, group) if world > 1 else local
     metric = Metric(dataset.sym_obj)
     out = fold_records(allrec, dataset.objlist, dataset.diameter, opt_pose, metric)
+    if bop:  # a record table of its own, gathered by the same mechanism
+        allbop = gather_epoch_records(local_bop, shard_sizes, device, group) if world > 1 else local_bop
+        out["bop"] = fold_bop(allbop, dataset.objlist, dataset.diameter, FRAME_W)
     if world > 1:
         # the ranks' own crop / success tallies, summed, must equal the gathered table's
         key = "add_f" if opt_pose else "add_b"
