@@ -552,6 +552,34 @@ int krrn_bop_vsd_f32(const float* verts, int Vtot, const int* faces, int Ftot, c
                      const double* diameter, double delta, const double* taus, int T, int B, int* ws, int* counts,
                      double* e_vsd, void* stream);
 
+/* Ground-truth visibility of B object instances: what BOP's calc_gt_masks / calc_gt_info scripts compute on the
+ * CPU, with VSD's render and VSD's visibility rule. verts / faces / face_range / K4 / depth / frame / depth_scale
+ * as krrn_bop_vsd_f32; R f64 [B][9], t f64 [B][3]: one pose per instance. Per instance b over the whole H x W
+ * frame, with D(p), D_obs(p), ray and the depth-to-distance conversion exactly as above (one depth walk under
+ * (R, t); dist = D ray where D > 0, else 0; obs likewise from D_obs):
+ *   mask[b][row][col]       = D(p) > 0
+ *   mask_visib[b][row][col] = visib(dist), the "bop19" rule above (obs == 0 && dist > 0 included)
+ * Both planes u8 [B][H][W] of 0 / 1; either may be NULL (not written). Every byte of a requested plane is defined
+ * after the call: the entry point zeroes the planes (hipMemsetAsync) before the tiles that a face can reach
+ * store theirs. info int32 [B][11] = px_count_all = #mask, px_count_valid = #(mask && obs > 0), px_count_visib =
+ * #mask_visib, bbox_obj (x, y, w, h) of mask, bbox_visib (x, y, w, h) of mask_visib, with BOP's calc_2d_bbox
+ * convention w = x_max - x_min, h = y_max - y_min over the set pixels (a single pixel has w = h = 0); a box with
+ * no pixel is (-1, -1, -1, -1). visib_fract f64 [B] = px_count_visib / px_count_all (one f64 division), 0.0 when
+ * px_count_all == 0. Stated departures from BOP's scripts: bbox_obj is clipped to the frame (BOP renders the
+ * silhouette into a 3 x larger window), and pixels are sampled at their integer coordinates. ws:
+ * krrn_bop_visib_ws(B) ints (per instance the projected bounding box, the three counts and the two boxes' lo /
+ * hi bounds). Counts are integer atomicAdd, bounds integer atomicMin / atomicMax over the tiles: order-free, so
+ * the result is deterministic and an instance's does not depend on the rest of the batch, bit for bit. Host
+ * checks, before any HIP call: null pointer (mask and mask_visib exempt) or overlapping buffers KRRN_EARG; B,
+ * Vtot, F, H, W < 1, Ftot < 0, delta or depth_scale not > 0 KRRN_ESHAPE. frame and face_range are guarded by the
+ * kernel as in VSD: a bad face range is an empty range, a frame index outside [0, F) observes nothing. */
+int krrn_bop_visib_ws(int B, long long* n_ints);
+int krrn_bop_visib_u8(const float* verts, int Vtot, const int* faces, int Ftot, const int* face_range,
+                      const double* R, const double* t, const float* K4, const float* depth, int F, int H, int W,
+                      const int* frame, double depth_scale, double delta, int B, int* ws,
+                      unsigned char* mask, unsigned char* mask_visib, int* info, double* visib_fract,
+                      void* stream);
+
 /* MSSD / MSPD, the maximum symmetry-aware surface / projection distance. verts f32 [Vtot][3] (all mesh
  * vertices), vert_range int32 [B][2] = first vertex, count of crop b; syms f64 [NStot][12] = row-major R
  * then t (metres, model frame), sym_range int32 [B][2] (each object's set begins with the identity). Per

@@ -11,6 +11,12 @@ departure: pixels are sampled at their integer coordinates, this project's raste
     syms = symmetry_set(discrete=[...], continuous=[{"axis": [0, 0, 1], "offset": [0, 0, 0]}])   # [NS, 12]
     errs = bop_errors(pred_r, pred_t, data, dataset)      # data = dataset.batch(idx, device, bop=True)
     res = fold_bop(records, objlist, diameter, width)     # evaluate.test_epoch(..., bop=True)["bop"]
+    gt = visibility(verts, faces, face_range, R, t, K4, depth, frame)   # ground-truth visibility of B instances
+    # -> {"mask", "mask_visib": u8 [B, H, W], "info": int32 [B, 11] (INFO), "visib_fract": f64 [B]}
+
+`visibility` is what BOP's calc_gt_masks / calc_gt_info scripts compute, with VSD's render and VSD's visibility
+rule. Its two stated departures from those scripts: bbox_obj is clipped to the frame (BOP renders the silhouette
+into a 3 x larger window), and pixels are sampled at their integer coordinates, as everywhere in this project.
 
 Multi-instance matching is out of scope: LineMOD's eval has one estimate per target, so recall is
 correct / targets.
@@ -77,6 +83,50 @@ def vsd(verts: torch.Tensor, faces: torch.Tensor, face_range: torch.Tensor, R_es
               ptr(K), ptr(d), F, H, W, ptr(fi), float(depth_scale), ptr(dia), float(delta), ptr(tau), T, B, ptr(ws),
               ptr(counts), ptr(e), stream_ptr(dev))
     return {"counts": counts, "e_vsd": e}
+
+
+VISIB_WS = 16                                           # kVisWs of csrc/bop.hip: ints per instance
+INFO = ("px_count_all", "px_count_valid", "px_count_visib", "bbox_obj_x", "bbox_obj_y", "bbox_obj_w", "bbox_obj_h",
+        "bbox_visib_x", "bbox_visib_y", "bbox_visib_w", "bbox_visib_h")
+
+
+def visibility(verts: torch.Tensor, faces: torch.Tensor, face_range: torch.Tensor, R: torch.Tensor, t: torch.Tensor,
+               K4: torch.Tensor, depth: torch.Tensor, frame: torch.Tensor, depth_scale: float = 1.0,
+               delta: float = DELTA, masks: bool = True) -> Dict[str, torch.Tensor]:
+    """krrn_bop_visib_u8 for B instances (include/krrn_hip.h): the ground truth that BOP's calc_gt_masks /
+    calc_gt_info scripts compute, from VSD's render and VSD's visibility rule. Operands and staging as `vsd`, one
+    pose (R [B, 3, 3], t [B, 3]) per instance. Returns {"mask", "mask_visib": u8 [B, H, W] of 0 / 1 (absent with
+    masks=False), "info": int32 [B, 11] in the order of INFO, "visib_fract": f64 [B]}; a box is (x, y, w, h) with
+    BOP's w = x_max - x_min, h = y_max - y_min, or four -1 without a pixel. Two stated departures from BOP's
+    scripts: bbox_obj is clipped to the frame (BOP renders the silhouette into a 3 x larger window), and pixels
+    are sampled at their integer coordinates. Nothing is read back."""
+    if not (verts.is_cuda and faces.is_cuda and depth.is_cuda):
+        raise RuntimeError("visibility runs on the HIP path only (verts / faces / depth must be GPU tensors)")
+    dev = verts.device
+    B = int(face_range.reshape(-1, 2).shape[0])
+    if depth.dim() != 3:
+        raise ValueError(f"depth must be [F, H, W], got {tuple(depth.shape)}")
+    # every converted operand stays bound until the launch is enqueued (metric.add_metric's rule)
+    v = verts.to(torch.float32).contiguous()
+    f = faces.to(torch.int32).contiguous()
+    d = depth.to(torch.float32).contiguous()
+    fr = h2d(face_range.reshape(B, 2), dev, torch.int32)
+    Rd = h2d(R, dev, torch.float64).reshape(B, 9).contiguous()
+    td = h2d(t, dev, torch.float64).reshape(B, 3).contiguous()
+    K = h2d(K4.reshape(B, 4), dev, torch.float32)
+    fi = h2d(frame.reshape(B), dev, torch.int32)
+    F, H, W = d.shape
+    ws = torch.empty((B, VISIB_WS), dtype=torch.int32, device=dev)    # krrn_bop_visib_ws(B)
+    out = {}
+    if masks:
+        out["mask"] = torch.empty((B, H, W), dtype=torch.uint8, device=dev)
+        out["mask_visib"] = torch.empty((B, H, W), dtype=torch.uint8, device=dev)
+    out["info"] = torch.empty((B, 11), dtype=torch.int32, device=dev)
+    out["visib_fract"] = torch.empty((B,), dtype=torch.float64, device=dev)
+    _lib.call("krrn_bop_visib_u8", ptr(v), v.shape[0], ptr(f), f.shape[0], ptr(fr), ptr(Rd), ptr(td), ptr(K), ptr(d), F,
+              H, W, ptr(fi), float(depth_scale), float(delta), B, ptr(ws), ptr(out.get("mask")),
+              ptr(out.get("mask_visib")), ptr(out["info"]), ptr(out["visib_fract"]), stream_ptr(dev))
+    return out
 
 
 def mssd_mspd(verts: torch.Tensor, vert_range: torch.Tensor, R_est: torch.Tensor, t_est: torch.Tensor,

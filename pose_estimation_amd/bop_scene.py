@@ -1,0 +1,281 @@
+"""Datasets in BOP's own layout (Hodan et al., "BOP: Benchmark for 6D Object Pose Estimation", ECCV 2018; the
+format of LM-O, YCB-V, T-LESS ... as published): the index of a tree, the GPU counterpart of BOP's
+calc_gt_masks / calc_gt_info scripts, and BOP's result CSV.
+
+    tree = BopTree("/data/lmo", split="test", targets="/data/lmo/test_targets_bop19.json", meshes=True)
+    write_gt_info("/data/mine", "test", device, masks=True)      # for a tree that ships no scene_gt_info.json
+    write_results("krrn_lmo-test.csv", rows); rows = read_results("krrn_lmo-test.csv")
+
+A tree is read as follows. `models/models_info.json` (millimetres): per object `diameter`, `min_x/y/z`,
+`size_x/y/z` and the optional `symmetries_discrete` / `symmetries_continuous`, which are already in the
+convention bop.symmetry_set takes. `models/obj_%06d.ply`: read with dataset.ply_vtx / ply_faces, which read ASCII
+PLY only; a binary PLY (what some BOP datasets ship) keeps raising their ValueError: convert it first. Per scene
+`<split>/%06d/scene_gt.json` (per image a list of {obj_id, cam_R_m2c, cam_t_m2c in mm}), `scene_camera.json`
+(per image `cam_K` row-major and `depth_scale`: raw depth x depth_scale = millimetres) and `scene_gt_info.json`
+(per instance `visib_fract`, `px_count_visib`, `bbox_visib`, ...); images `rgb/%06d.png` (or .jpg),
+`depth/%06d.png` (uint16) and the per-instance `mask_visib/%06d_%06d.png` (image id, GT index).
+
+Out of scope: matching several estimates to several instances of one object in an image (a target's
+`inst_count` > 1: every kept GT instance is one item with one estimate), binary PLY, and detector boxes / masks
+in BOP's detection format (the crops come from `bbox_visib`)."""
+from __future__ import annotations
+
+import json
+import os
+from typing import Dict, List, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import bop
+
+INFO_KEYS = ("bbox_obj", "bbox_visib", "px_count_all", "px_count_valid", "px_count_visib", "visib_fract")  # BOP's six
+
+
+def _load_json(path: str) -> Dict[int, object]:
+    with open(path) as f:
+        return {int(k): v for k, v in json.load(f).items()}
+
+
+def scene_ids(root: str, split: str) -> List[int]:
+    d = os.path.join(root, split)
+    return sorted(int(n) for n in os.listdir(d) if n.isdigit() and os.path.isdir(os.path.join(d, n)))
+
+
+def _image_path(sdir: str, sub: str, im: int) -> str:
+    for ext in (".png", ".jpg"):
+        p = os.path.join(sdir, sub, f"{im:06d}{ext}")
+        if os.path.exists(p):
+            return p
+    raise FileNotFoundError(os.path.join(sdir, sub, f"{im:06d}.png (or .jpg)"))
+
+
+def read_depth(sdir: str, im: int, depth_scale: float) -> np.ndarray:
+    """depth/%06d.png in metres, f32 [H, W]: (raw as f64 x depth_scale / 1000) rounded to f32 once."""
+    from PIL import Image
+    with Image.open(os.path.join(sdir, "depth", f"{im:06d}.png")) as di:
+        return (np.asarray(di).astype(np.float64) * float(depth_scale) / 1000.0).astype(np.float32)
+
+
+def load_models(root: str, objs: Sequence[int], faces: bool = True):
+    """({obj: its models_info.json entry}, {obj: (verts f32 [V, 3] metres, faces int32 [F, 3])}) of a tree."""
+    from .dataset import ply_faces, ply_vtx
+    info = _load_json(os.path.join(root, "models", "models_info.json"))
+    mesh = {}
+    for obj in objs:
+        p = os.path.join(root, "models", f"obj_{obj:06d}.ply")
+        pts = (ply_vtx(p) / 1000.0).astype(np.float32)
+        tri = ply_faces(p) if faces else np.zeros((0, 3), np.int32)
+        if faces and len(tri) == 0:
+            raise ValueError(f"obj_{obj:06d}.ply has no faces (element face 0): nothing to render")
+        if len(tri) and (tri.min() < 0 or tri.max() >= len(pts)):
+            raise ValueError(f"obj_{obj:06d}.ply: a face index lies outside its {len(pts)} vertices")
+        mesh[obj] = (pts, tri)
+    return info, mesh
+
+
+class BopTree:
+    """Index of a BOP tree (module doc) with the interface PoseDataset uses of its LineMOD index: `items`,
+    `model_points`, `mesh`, `symmetries`, `read(i)`; also `info` = the tree's models_info.json entries and
+    `frame_hw`. One item per GT instance: {"scene", "im", "gt" (index in the image's scene_gt list), "obj", "R" f64
+    [3, 3], "t" f64 [3] metres, "K4" (fx, fy, cx, cy), "depth_scale", "bbox" = bbox_visib}.
+
+    targets: the path of a test_targets_bop19.json-style list ({scene_id, im_id, obj_id, inst_count}); only its
+    (scene, image, object) triples are kept. Instances with visib_fract < min_visib or px_count_visib == 0 are
+    dropped: BOP-19's rule for which GT instances count. objlist: the objects to keep; default the sorted ids
+    that remain. A scene without scene_gt_info.json raises FileNotFoundError naming write_gt_info."""
+
+    def __init__(self, root: str, split: str = "test", targets: Optional[str] = None,
+                 objlist: Optional[Sequence[int]] = None, n_model_pts: int = 2600, seed: int = 0, meshes: bool = False,
+                 min_visib: float = 0.1):
+        self.root, self.split = root, split
+        want = None
+        if targets is not None:
+            with open(targets) as f:
+                want = {(int(e["scene_id"]), int(e["im_id"]), int(e["obj_id"])) for e in json.load(f)}
+        keep_obj = None if objlist is None else {int(o) for o in objlist}
+        self.items: List[Dict[str, object]] = []
+        self.frame_hw: Optional[Tuple[int, int]] = None
+        for sc in scene_ids(root, split):
+            sdir = os.path.join(root, split, f"{sc:06d}")
+            gt = _load_json(os.path.join(sdir, "scene_gt.json"))
+            cam = _load_json(os.path.join(sdir, "scene_camera.json"))
+            ipath = os.path.join(sdir, "scene_gt_info.json")
+            if not os.path.exists(ipath):
+                raise FileNotFoundError(f"{ipath} is missing: a tree without it (recorded or rendered by the user) "
+                                        "gets one from bop_scene.write_gt_info(root, split, device)")
+            ginfo = _load_json(ipath)
+            for im in sorted(gt):
+                K = [float(k) for k in cam[im]["cam_K"]]
+                for g, (e, gi) in enumerate(zip(gt[im], ginfo[im])):
+                    obj = int(e["obj_id"])
+                    if want is not None and (sc, im, obj) not in want:
+                        continue
+                    if keep_obj is not None and obj not in keep_obj:
+                        continue
+                    if float(gi["visib_fract"]) < min_visib or int(gi["px_count_visib"]) == 0:
+                        continue
+                    self.items.append({"scene": sc, "im": im, "gt": g, "obj": obj,
+                                       "R": np.array(e["cam_R_m2c"], np.float64).reshape(3, 3),
+                                       "t": np.array(e["cam_t_m2c"], np.float64) / 1000.0,
+                                       "K4": (K[0], K[4], K[2], K[5]),
+                                       "depth_scale": float(cam[im].get("depth_scale", 1.0)),
+                                       "bbox": [float(v) for v in gi["bbox_visib"]]})
+        self.objlist = sorted({int(it["obj"]) for it in self.items}) if objlist is None else [int(o) for o in objlist]
+        if self.items:
+            it = self.items[0]
+            from PIL import Image
+            with Image.open(os.path.join(root, split, f"{int(it['scene']):06d}", "depth", f"{int(it['im']):06d}.png")) as di:
+                self.frame_hw = (di.size[1], di.size[0])
+        self.info, mesh = load_models(root, self.objlist, faces=meshes)
+        self.mesh: Dict[int, Tuple[np.ndarray, np.ndarray]] = mesh if meshes else {}
+        self.symmetries: Dict[int, np.ndarray] = {}
+        self.model_points: Dict[int, np.ndarray] = {}
+        rng = np.random.default_rng(seed)
+        for obj in self.objlist:  # the LineMOD index's subsampling, draw for draw
+            pts = mesh[obj][0]
+            oi = self.info.get(obj, {})
+            if meshes:
+                self.symmetries[obj] = bop.symmetry_set(oi.get("symmetries_discrete"), oi.get("symmetries_continuous"))
+            if len(pts) < n_model_pts:
+                raise ValueError(f"obj_{obj:06d}.ply has {len(pts)} vertices < num_pt_mesh_large = {n_model_pts}")
+            if len(pts) > n_model_pts:
+                pts = pts[np.sort(rng.choice(len(pts), n_model_pts, replace=False))]
+            self.model_points[obj] = pts.astype(np.float32)
+
+    def has_symmetry(self, obj: int) -> bool:
+        oi = self.info.get(obj, {})
+        return bool(oi.get("symmetries_discrete")) or bool(oi.get("symmetries_continuous"))
+
+    def _sdir(self, it) -> str:
+        return os.path.join(self.root, self.split, f"{int(it['scene']):06d}")
+
+    def read_image(self, scene: int, im: int, depth_scale: float):
+        """(rgb u8 [H, W, 3], depth f32 [H, W] metres) of one image."""
+        from PIL import Image
+        sdir = os.path.join(self.root, self.split, f"{scene:06d}")
+        with Image.open(_image_path(sdir, "rgb", im)) as ri:
+            rgb = np.array(ri.convert("RGB"))
+        return rgb, read_depth(sdir, im, depth_scale)
+
+    def read_mask(self, i: int) -> np.ndarray:
+        from PIL import Image
+        it = self.items[i]
+        with Image.open(os.path.join(self._sdir(it), "mask_visib", f"{int(it['im']):06d}_{int(it['gt']):06d}.png")) as li:
+            label = np.array(li)
+        return ((label[:, :, 0] if label.ndim == 3 else label) != 0).astype(np.uint8)
+
+    def read(self, i: int):
+        it = self.items[i]
+        rgb, depth = self.read_image(int(it["scene"]), int(it["im"]), float(it["depth_scale"]))
+        return rgb, depth, self.read_mask(i)
+
+
+def _save_json(path: str, content: Dict[int, object]) -> None:
+    with open(path, "w") as f:
+        json.dump({str(k): v for k, v in sorted(content.items())}, f, indent=1)
+
+
+def write_gt_info(root: str, split: str, device, masks: bool = False, delta: float = bop.DELTA, batch: int = 64,
+                  overwrite: bool = False) -> Dict[int, Dict[int, List[Dict[str, object]]]]:
+    """The GPU counterpart of BOP's calc_gt_info / calc_gt_masks for every scene of `root`/`split`:
+    bop.visibility over the scene's GT instances in batches of `batch` (each batch decodes its distinct images
+    once), written as scene_gt_info.json with BOP's six keys (INFO_KEYS) and, with masks=True, the
+    mask/%06d_%06d.png and mask_visib/%06d_%06d.png images (0 / 255). Refuses to overwrite an existing
+    scene_gt_info.json or mask file unless overwrite=True (FileExistsError, before anything is computed for that
+    scene). Returns {scene: {image: [entry per instance]}}. The two departures from BOP's scripts that
+    bop.visibility states apply: bbox_obj is clipped to the frame, and pixels are sampled at integer coordinates."""
+    from PIL import Image
+    from .runtime import h2d
+    device = torch.device(device)
+    out = {}
+    scenes = scene_ids(root, split)
+    objs = set()
+    gts = {}
+    for sc in scenes:
+        gts[sc] = _load_json(os.path.join(root, split, f"{sc:06d}", "scene_gt.json"))
+        objs |= {int(e["obj_id"]) for v in gts[sc].values() for e in v}
+    objs = sorted(objs)
+    _, mesh = load_models(root, objs)
+    v0 = f0 = 0
+    frange, vs, fs = {}, [], []
+    for obj in objs:
+        v, f = mesh[obj]
+        vs.append(v)
+        fs.append(f + v0)
+        frange[obj] = (f0, len(f))
+        v0, f0 = v0 + len(v), f0 + len(f)
+    verts = h2d(torch.from_numpy(np.concatenate(vs)), device)
+    faces = h2d(torch.from_numpy(np.concatenate(fs).astype(np.int32)), device)
+    for sc in scenes:
+        sdir = os.path.join(root, split, f"{sc:06d}")
+        ipath = os.path.join(sdir, "scene_gt_info.json")
+        if os.path.exists(ipath) and not overwrite:
+            raise FileExistsError(f"{ipath} exists (overwrite=True replaces it)")
+        cam = _load_json(os.path.join(sdir, "scene_camera.json"))
+        inst = [(im, g, e) for im in sorted(gts[sc]) for g, e in enumerate(gts[sc][im])]
+        if masks:
+            for sub in ("mask", "mask_visib"):
+                os.makedirs(os.path.join(sdir, sub), exist_ok=True)
+                for im, g, _ in inst:
+                    p = os.path.join(sdir, sub, f"{im:06d}_{g:06d}.png")
+                    if os.path.exists(p) and not overwrite:
+                        raise FileExistsError(f"{p} exists (overwrite=True replaces it)")
+        entries = {im: [None] * len(gts[sc][im]) for im in gts[sc]}
+        for lo in range(0, len(inst), max(1, int(batch))):
+            part = inst[lo:lo + max(1, int(batch))]
+            ims = list(dict.fromkeys(im for im, _, _ in part))
+            depth = np.stack([read_depth(sdir, im, float(cam[im].get("depth_scale", 1.0))) for im in ims])
+            K = [[float(k) for k in cam[im]["cam_K"]] for im, _, _ in part]
+            res = bop.visibility(
+                verts, faces, torch.tensor([frange[int(e["obj_id"])] for _, _, e in part], dtype=torch.int32),
+                torch.tensor(np.stack([np.array(e["cam_R_m2c"], np.float64).reshape(3, 3) for _, _, e in part])),
+                torch.tensor(np.stack([np.array(e["cam_t_m2c"], np.float64) / 1000.0 for _, _, e in part])),
+                torch.tensor([[k[0], k[4], k[2], k[5]] for k in K], dtype=torch.float32),
+                h2d(torch.from_numpy(depth), device), torch.tensor([ims.index(im) for im, _, _ in part], dtype=torch.int32),
+                1.0, delta, masks=masks)
+            info, fract = res["info"].cpu().numpy(), res["visib_fract"].cpu().numpy()   # one read-back per batch
+            planes = {k: res[k].cpu().numpy() for k in ("mask", "mask_visib")} if masks else {}
+            for j, (im, g, _) in enumerate(part):
+                q = [int(x) for x in info[j]]
+                entries[im][g] = {"bbox_obj": q[3:7], "bbox_visib": q[7:11], "px_count_all": q[0], "px_count_valid": q[1],
+                                  "px_count_visib": q[2], "visib_fract": float(fract[j])}
+                for sub, pl in planes.items():
+                    Image.fromarray(pl[j] * np.uint8(255)).save(os.path.join(sdir, sub, f"{im:06d}_{g:06d}.png"))
+        _save_json(ipath, entries)
+        out[sc] = entries
+    return out
+
+
+RESULT_HEADER = "scene_id,im_id,obj_id,score,R,t,time"
+
+
+def write_results(path: str, rows) -> None:
+    """BOP's result CSV, one estimate per row: `rows` = dicts with scene_id, im_id, obj_id, score, R (9 numbers,
+    row-major), t (3 numbers, millimetres) and time (seconds, -1 = not measured). Floats are written with repr,
+    so read_results returns them bit for bit."""
+    with open(path, "w") as f:
+        f.write(RESULT_HEADER + "\n")
+        for r in rows:
+            R = " ".join(repr(float(x)) for x in np.asarray(r["R"], np.float64).reshape(9))
+            t = " ".join(repr(float(x)) for x in np.asarray(r["t"], np.float64).reshape(3))
+            f.write(f"{int(r['scene_id'])},{int(r['im_id'])},{int(r['obj_id'])},{float(r['score'])!r},{R},{t},"
+                    f"{float(r['time'])!r}\n")
+
+
+def read_results(path: str) -> List[Dict[str, object]]:
+    with open(path) as f:
+        lines = [ln.strip() for ln in f if ln.strip()]
+    if not lines or lines[0] != RESULT_HEADER:
+        raise ValueError(f"{path}: the first line must be '{RESULT_HEADER}'")
+    rows = []
+    for n, ln in enumerate(lines[1:], 2):
+        tok = ln.split(",")
+        if len(tok) != 7:
+            raise ValueError(f"{path}:{n}: 7 comma-separated fields expected, got {len(tok)}")
+        R, t = np.array(tok[4].split(), np.float64), np.array(tok[5].split(), np.float64)
+        if R.size != 9 or t.size != 3:
+            raise ValueError(f"{path}:{n}: R holds 9 and t 3 numbers")
+        rows.append({"scene_id": int(tok[0]), "im_id": int(tok[1]), "obj_id": int(tok[2]), "score": float(tok[3]),
+                     "R": R.reshape(3, 3), "t": t, "time": float(tok[6])})
+    return rows

@@ -1,7 +1,9 @@
 // The BOP-19 pose errors (Hodan et al., ECCV-W 2020) of a batch of estimates against their GT poses:
 // VSD (krrn_bop_vsd_f32) and MSSD / MSPD (krrn_bop_mssd_mspd_f32). Written from the published definition;
 // include/krrn_hip.h states it, tests/bop_ref.py restates it in numpy f64 with the same operation order.
-// Everything is f64 without FMA contraction (FLAGS_bop).
+// Everything is f64 without FMA contraction (FLAGS_bop). krrn_bop_visib_u8, at the end of the VSD part, writes
+// out the ground-truth visibility of B instances (silhouette, visible mask, pixel counts, boxes) with the same
+// walk and the same visibility rule (bop_visible below: stated once for both).
 //
 // VSD renders the mesh twice per crop, under the estimated and the GT pose, over the whole H x W frame with
 // the GT-map rasteriser's depth walk (krrn_raster.h: the same face test, skip rules, strict < and
@@ -46,18 +48,32 @@ __device__ __forceinline__ double bop_wave_max(double v) {
   return v;
 }
 
-// ws int32 [B][2][4] = (u lo, u hi, v lo, v hi) of pose 0 (estimate) and 1 (GT); lo > hi = no vertex
-__global__ __launch_bounds__(kRastThreads) void bop_box_kernel(
-    const float* __restrict__ verts, int Vtot, const int* __restrict__ faces, int Ftot,
-    const int* __restrict__ face_range, const double* __restrict__ R_est, const double* __restrict__ t_est,
-    const double* __restrict__ R_gt, const double* __restrict__ t_gt, const float* __restrict__ K4, int NC,
-    int* __restrict__ ws, int* __restrict__ counts) {
-  __shared__ double s_box[kRastWaves][4];
-  const int b = blockIdx.x, pose = blockIdx.y, tid = threadIdx.x;
-  const int lane = tid & 63, wave = tid >> 6;
-  if (pose == 0 && tid < NC) counts[(size_t)b * NC + tid] = 0;
-  RastCam cam;
-  rast_load_cam(cam, pose ? R_gt : R_est, pose ? t_gt : t_est, K4, b);
+// the "bop19" visibility rule of include/krrn_hip.h for one pixel: obs and model are distances from the camera
+// centre, 0 = nothing observed / nothing rendered
+__device__ __forceinline__ bool bop_visible(double obs, double model, double delta) {
+  return (obs > 0.0 && model > 0.0 && (model - obs) <= delta) || (obs == 0.0 && model > 0.0);
+}
+
+// ray = the distance per unit depth of pixel (pu, pv); obs = the observed distance there (0 for a frame index
+// outside [0, F), and for a zero, negative or NaN sample)
+__device__ __forceinline__ void bop_observe(const RastCam& cam, double pu, double pv, const float* __restrict__ depth,
+                                            int F, int H, int W, int fr, int x, int y, double depth_scale,
+                                            double& ray, double& obs) {
+  const double xn = (pu - cam.cx) / cam.fx, yn = (pv - cam.cy) / cam.fy;
+  ray = sqrt((xn * xn + yn * yn) + 1.0);
+  double d_obs = 0.0;
+  if (fr >= 0 && fr < F) d_obs = (double)depth[((size_t)fr * H + y) * W + x] / depth_scale;
+  obs = d_obs > 0.0 ? d_obs * ray : 0.0;
+}
+
+// the bounding box of the projected vertices of crop b's faces under `cam` (vertices with z > 1e-3 only), as 4
+// ints rounded outwards in o[0..3] = (u lo, u hi, v lo, v hi), lo > hi = no vertex. All threads of the block
+// call it; thread 0 writes.
+__device__ __forceinline__ void bop_project_box(const RastCam& cam, const float* __restrict__ verts, int Vtot,
+                                                const int* __restrict__ faces, int Ftot,
+                                                const int* __restrict__ face_range, int b, double (*s_box)[4],
+                                                int* __restrict__ o) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   long long f0;
   int nf;
   rast_range(face_range, b, Ftot, f0, nf);
@@ -85,13 +101,26 @@ __global__ __launch_bounds__(kRastThreads) void bop_box_kernel(
       umin = fmin(umin, s_box[w][0]), umax = fmax(umax, s_box[w][1]);
       vmin = fmin(vmin, s_box[w][2]), vmax = fmax(vmax, s_box[w][3]);
     }
-    int* o = ws + ((size_t)b * 2 + pose) * 4;
     const bool any = umin <= umax && vmin <= vmax;
     auto lo = [](double x) { return (int)fmax(fmin(floor(x), kBopBoxClamp), -kBopBoxClamp); };
     auto hi = [](double x) { return (int)fmax(fmin(ceil(x), kBopBoxClamp), -kBopBoxClamp); };
     o[0] = any ? lo(umin) : kBopBoxEmptyLo, o[1] = any ? hi(umax) : kBopBoxEmptyHi;
     o[2] = any ? lo(vmin) : kBopBoxEmptyLo, o[3] = any ? hi(vmax) : kBopBoxEmptyHi;
   }
+}
+
+// ws int32 [B][2][4] = (u lo, u hi, v lo, v hi) of pose 0 (estimate) and 1 (GT); lo > hi = no vertex
+__global__ __launch_bounds__(kRastThreads) void bop_box_kernel(
+    const float* __restrict__ verts, int Vtot, const int* __restrict__ faces, int Ftot,
+    const int* __restrict__ face_range, const double* __restrict__ R_est, const double* __restrict__ t_est,
+    const double* __restrict__ R_gt, const double* __restrict__ t_gt, const float* __restrict__ K4, int NC,
+    int* __restrict__ ws, int* __restrict__ counts) {
+  __shared__ double s_box[kRastWaves][4];
+  const int b = blockIdx.x, pose = blockIdx.y, tid = threadIdx.x;
+  if (pose == 0 && tid < NC) counts[(size_t)b * NC + tid] = 0;
+  RastCam cam;
+  rast_load_cam(cam, pose ? R_gt : R_est, pose ? t_gt : t_est, K4, b);
+  bop_project_box(cam, verts, Vtot, faces, Ftot, face_range, b, s_box, ws + ((size_t)b * 2 + pose) * 4);
 }
 
 __global__ __launch_bounds__(kRastThreads) void bop_vsd_kernel(
@@ -142,17 +171,12 @@ __global__ __launch_bounds__(kRastThreads) void bop_vsd_kernel(
   bool in_union = false, in_inter = false;
   double cost = 0.0;
   if (inside) {
-    const double xn = (pu - cam.cx) / cam.fx, yn = (pv - cam.cy) / cam.fy;  // K4 is the same for both poses
-    const double ray = sqrt((xn * xn + yn * yn) + 1.0);
-    const int fr = frame[b];
-    double d_obs = 0.0;
-    if (fr >= 0 && fr < F) d_obs = (double)depth[((size_t)fr * H + y) * W + x] / depth_scale;
-    const double obs = d_obs > 0.0 ? d_obs * ray : 0.0;  // also for a negative or NaN sample
+    double ray, obs;  // K4 is the same for both poses
+    bop_observe(cam, pu, pv, depth, F, H, W, frame[b], x, y, depth_scale, ray, obs);
     const double dist_est = z_est > 0.0 ? z_est * ray : 0.0;
     const double dist_gt = z_gt > 0.0 ? z_gt * ray : 0.0;
-    const bool v_gt = (obs > 0.0 && dist_gt > 0.0 && (dist_gt - obs) <= delta) || (obs == 0.0 && dist_gt > 0.0);
-    const bool v_est = (obs > 0.0 && dist_est > 0.0 && (dist_est - obs) <= delta) ||
-                       (obs == 0.0 && dist_est > 0.0) || (v_gt && dist_est > 0.0);
+    const bool v_gt = bop_visible(obs, dist_gt, delta);
+    const bool v_est = bop_visible(obs, dist_est, delta) || (v_gt && dist_est > 0.0);
     in_inter = v_gt && v_est;
     in_union = v_gt || v_est;
     cost = fabs(dist_gt - dist_est) / diameter[b];
@@ -173,6 +197,154 @@ __global__ void bop_vsd_finish_kernel(const int* __restrict__ counts, int B, int
   const int* c = counts + (size_t)b * (2 + T);
   const int un = c[0], in = c[1], step = c[2 + k];
   e_vsd[i] = un > 0 ? (double)(step + (un - in)) / (double)un : 1.0;
+}
+
+// ------------------------------------------------------------------------------------------ GT visibility
+// krrn_bop_visib_u8: VSD's structure with one pose per instance, and the result written out.
+//   0. the entry point zeroes the requested planes with hipMemsetAsync, so the tiles that return early (and the
+//      pixels of a walked tile that no face covers, which store their own zeros again) leave every byte defined.
+//   1. bop_visib_box_kernel, one block per instance: its projected bounding box (bop_project_box) and the reset
+//      of its counters and box bounds.
+//   2. bop_visib_kernel, one block per 16 x 16 tile and instance: a tile outside the box returns after reading
+//      4 ints; otherwise one depth walk, the observed depth, the two flags per pixel. A wave holds 4 rows of 16
+//      pixels, so its 64-bit ballot of a flag is 4 rows of 16 bits: the lane at the head of each row expands its
+//      16 bits to 16 bytes and stores the row with one 16-byte store (a row cut by the frame's right border, or
+//      a plane whose rows are not 16-byte aligned, takes per-pixel byte stores instead). The same ballots give
+//      the counts (popcount) and the wave's box bounds (first / last set column and row), which go through LDS
+//      and then one integer atomicAdd / atomicMin / atomicMax per block and quantity: all order-independent.
+//   3. bop_visib_finish_kernel: (lo, hi) bounds to (x, y, w, h), and visib_fract.
+// ws int32 [B][16] = box (u lo, u hi, v lo, v hi), counts (all, valid, visib), one unused, the bounds of mask
+// (x lo, x hi, y lo, y hi), the bounds of mask_visib.
+constexpr int kVisWs = 16;
+constexpr int kVisLoInit = 0x7fffffff, kVisHiInit = -1;
+
+__global__ __launch_bounds__(kRastThreads) void bop_visib_box_kernel(
+    const float* __restrict__ verts, int Vtot, const int* __restrict__ faces, int Ftot,
+    const int* __restrict__ face_range, const double* __restrict__ R, const double* __restrict__ t,
+    const float* __restrict__ K4, int* __restrict__ ws) {
+  __shared__ double s_box[kRastWaves][4];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  int* o = ws + (size_t)b * kVisWs;
+  if (tid >= 4 && tid < 8) o[tid] = 0;
+  if (tid >= 8 && tid < kVisWs) o[tid] = (tid & 1) ? kVisHiInit : kVisLoInit;
+  RastCam cam;
+  rast_load_cam(cam, R, t, K4, b);
+  bop_project_box(cam, verts, Vtot, faces, Ftot, face_range, b, s_box, o);
+}
+
+// 16 flag bits -> 16 bytes of 0 / 1 (bit i to byte i)
+__device__ __forceinline__ uint4 bop_row_bytes(unsigned bits) {
+  auto four = [](unsigned n) { return ((n & 0xfu) * 0x00204081u) & 0x01010101u; };  // the shifted copies do not overlap
+  return make_uint4(four(bits), four(bits >> 4), four(bits >> 8), four(bits >> 12));
+}
+
+// one plane's stores and one box's bounds for one wave: bal = the wave's ballot of the pixel flag
+__device__ __forceinline__ void bop_visib_emit(unsigned long long bal, bool flag, bool inside, bool row_fast,
+                                               unsigned char* __restrict__ plane, size_t pix, int lane, int lx,
+                                               int wy, int* s_bounds) {
+  if (plane) {
+    if (row_fast) {
+      if ((lane & 15) == 0 && inside)
+        *reinterpret_cast<uint4*>(plane + pix) = bop_row_bytes((unsigned)(bal >> lane) & 0xffffu);
+    } else if (inside) {
+      plane[pix] = flag ? 1 : 0;
+    }
+  }
+  if (lane == 0 && bal) {
+    const unsigned cols = (unsigned)((bal | (bal >> 16) | (bal >> 32) | (bal >> 48)) & 0xffffull);
+    int r0 = 0, r1 = 3;
+    while (!((bal >> (16 * r0)) & 0xffffull)) ++r0;
+    while (!((bal >> (16 * r1)) & 0xffffull)) --r1;
+    atomicMin(&s_bounds[0], lx + (__ffs(cols) - 1));
+    atomicMax(&s_bounds[1], lx + (31 - __clz(cols)));
+    atomicMin(&s_bounds[2], wy + r0);
+    atomicMax(&s_bounds[3], wy + r1);
+  }
+}
+
+__global__ __launch_bounds__(kRastThreads) void bop_visib_kernel(
+    const float* __restrict__ verts, int Vtot, const int* __restrict__ faces, int Ftot,
+    const int* __restrict__ face_range, const double* __restrict__ R, const double* __restrict__ t,
+    const float* __restrict__ K4, const float* __restrict__ depth, int F, int H, int W, const int* __restrict__ frame,
+    double depth_scale, double delta, int* __restrict__ ws, unsigned char* __restrict__ mask,
+    unsigned char* __restrict__ mask_visib) {
+  __shared__ double s_setup[kRastThreads * kRastSetup];
+  __shared__ int s_id[kRastThreads];
+  __shared__ int s_wcnt[kRastWaves];
+  __shared__ int s_out[11];  // 3 counts, 2 x 4 bounds
+
+  const int b = blockIdx.z, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int lx = blockIdx.x * kRastTile, ly = blockIdx.y * kRastTile;
+  const int tx1 = min(lx + kRastTile, W) - 1, ty1 = min(ly + kRastTile, H) - 1;
+  int* o = ws + (size_t)b * kVisWs;
+  if (!(o[0] <= tx1 && o[1] >= lx && o[2] <= ty1 && o[3] >= ly)) return;  // uniform: the planes are zero already
+
+  const int x = lx + (tid & (kRastTile - 1)), y = ly + (tid >> 4);
+  const bool inside = x < W && y < H;
+  long long f0;
+  int nf;
+  rast_range(face_range, b, Ftot, f0, nf);
+  const double pu = (double)x, pv = (double)y;
+  RastCam cam;
+  RastHit hit;
+  rast_load_cam(cam, R, t, K4, b);
+  rast_depth_walk(cam, verts, Vtot, faces, f0, nf, (double)lx, (double)tx1, (double)ly, (double)ty1, pu, pv, inside,
+                  s_setup, s_id, s_wcnt, hit);
+  if (tid < 11) s_out[tid] = tid < 3 ? 0 : (((tid - 3) & 1) ? kVisHiInit : kVisLoInit);
+  __syncthreads();
+
+  bool in_mask = false, in_valid = false, in_visib = false;
+  if (inside) {
+    double ray, obs;
+    bop_observe(cam, pu, pv, depth, F, H, W, frame[b], x, y, depth_scale, ray, obs);
+    const double z = hit.f >= 0 ? hit.z : 0.0;
+    const double dist = z > 0.0 ? z * ray : 0.0;
+    in_mask = z > 0.0;
+    in_valid = in_mask && obs > 0.0;
+    in_visib = bop_visible(obs, dist, delta);
+  }
+  const size_t pix = ((size_t)b * H + y) * W + x;  // used only where `inside`
+  // a whole 16-pixel row of the tile lies in the frame and starts on a 16-byte boundary (uniform over the row)
+  const bool full = lx + kRastTile <= W;
+  const size_t row0 = ((size_t)b * H + y) * W + lx;
+  const bool fast_m = full && mask && ((reinterpret_cast<uintptr_t>(mask) + row0) & 15) == 0;
+  const bool fast_v = full && mask_visib && ((reinterpret_cast<uintptr_t>(mask_visib) + row0) & 15) == 0;
+  const unsigned long long bal_m = __ballot(in_mask), bal_val = __ballot(in_valid), bal_v = __ballot(in_visib);
+  const int wy = ly + 4 * wave;
+  bop_visib_emit(bal_m, in_mask, inside, fast_m, mask, pix, lane, lx, wy, s_out + 3);
+  bop_visib_emit(bal_v, in_visib, inside, fast_v, mask_visib, pix, lane, lx, wy, s_out + 7);
+  if (lane == 0) {
+    if (bal_m) atomicAdd(&s_out[0], __popcll(bal_m));
+    if (bal_val) atomicAdd(&s_out[1], __popcll(bal_val));
+    if (bal_v) atomicAdd(&s_out[2], __popcll(bal_v));
+  }
+  __syncthreads();
+  if (tid < 3) {
+    if (s_out[tid]) atomicAdd(&o[4 + tid], s_out[tid]);
+  } else if (tid < 11) {
+    const int v = s_out[tid];
+    if ((tid - 3) & 1) {
+      if (v != kVisHiInit) atomicMax(&o[8 + (tid - 3)], v);
+    } else {
+      if (v != kVisLoInit) atomicMin(&o[8 + (tid - 3)], v);
+    }
+  }
+}
+
+__global__ void bop_visib_finish_kernel(const int* __restrict__ ws, int B, int* __restrict__ info,
+                                        double* __restrict__ visib_fract) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  const int* o = ws + (size_t)b * kVisWs;
+  int* q = info + (size_t)b * 11;
+  q[0] = o[4], q[1] = o[5], q[2] = o[6];
+  for (int k = 0; k < 2; ++k) {
+    const int* e = o + 8 + 4 * k;
+    const bool any = o[k ? 6 : 4] > 0;
+    q[3 + 4 * k] = any ? e[0] : -1, q[4 + 4 * k] = any ? e[2] : -1;
+    q[5 + 4 * k] = any ? e[1] - e[0] : -1, q[6 + 4 * k] = any ? e[3] - e[2] : -1;
+  }
+  visib_fract[b] = o[4] > 0 ? (double)o[6] / (double)o[4] : 0.0;
 }
 
 __global__ __launch_bounds__(kRastThreads) void bop_mssd_mspd_kernel(
@@ -285,6 +457,44 @@ KRRN_API int krrn_bop_vsd_f32(const float* verts, int Vtot, const int* faces, in
                      st, verts, Vtot, faces, Ftot, face_range, R_est, t_est, R_gt, t_gt, K4, depth, F, H, W, frame,
                      depth_scale, diameter, delta, taus, T, ws, counts);
   hipLaunchKernelGGL(bop_vsd_finish_kernel, dim3(krrn_cdiv(B * T, 256)), dim3(256), 0, st, counts, B, T, e_vsd);
+  return krrn_launch_status();
+}
+
+KRRN_API int krrn_bop_visib_ws(int B, long long* n_ints) {
+  if (!n_ints) return KRRN_EARG;
+  if (B < 1 || B > 65535) return KRRN_ESHAPE;
+  *n_ints = (long long)kVisWs * B;
+  return KRRN_OK;
+}
+
+KRRN_API int krrn_bop_visib_u8(const float* verts, int Vtot, const int* faces, int Ftot, const int* face_range,
+                               const double* R, const double* t, const float* K4, const float* depth, int F, int H,
+                               int W, const int* frame, double depth_scale, double delta, int B, int* ws,
+                               unsigned char* mask, unsigned char* mask_visib, int* info, double* visib_fract,
+                               void* stream) {
+  if (!verts || !faces || !face_range || !R || !t || !K4 || !depth || !frame || !ws || !info || !visib_fract)
+    return KRRN_EARG;
+  if (B < 1 || B > 65535 || Vtot < 1 || Ftot < 0 || F < 1 || H < 1 || W < 1 || H > 65535 * kRastTile ||
+      W > 65535 * kRastTile || !(delta > 0.0) || !(depth_scale > 0.0))
+    return KRRN_ESHAPE;
+  const size_t b = (size_t)B, plane = b * H * W;
+  const Span outs[5] = {{ws, 4 * b * kVisWs}, {mask, mask ? plane : 0}, {mask_visib, mask_visib ? plane : 0},
+                        {info, 44 * b},       {visib_fract, 8 * b}};
+  const Span ins[8] = {{verts, 12 * (size_t)Vtot}, {faces, 12 * (size_t)Ftot}, {face_range, 8 * b}, {R, 72 * b},
+                       {t, 24 * b},                {K4, 16 * b},               {depth, 4 * (size_t)F * H * W},
+                       {frame, 4 * b}};
+  if (rast_overlap(outs, 5, ins, 8)) return KRRN_EARG;
+  hipStream_t st = (hipStream_t)stream;
+  for (unsigned char* p : {mask, mask_visib}) {
+    const hipError_t e = p ? hipMemsetAsync(p, 0, plane, st) : hipSuccess;
+    if (e != hipSuccess) return (int)e;
+  }
+  hipLaunchKernelGGL(bop_visib_box_kernel, dim3(B), dim3(kRastThreads), 0, st, verts, Vtot, faces, Ftot, face_range, R,
+                     t, K4, ws);
+  hipLaunchKernelGGL(bop_visib_kernel, dim3(krrn_cdiv(W, kRastTile), krrn_cdiv(H, kRastTile), B), dim3(kRastThreads), 0,
+                     st, verts, Vtot, faces, Ftot, face_range, R, t, K4, depth, F, H, W, frame, depth_scale, delta, ws,
+                     mask, mask_visib);
+  hipLaunchKernelGGL(bop_visib_finish_kernel, dim3(krrn_cdiv(B, 256)), dim3(256), 0, st, ws, B, info, visib_fract);
   return krrn_launch_status();
 }
 

@@ -25,6 +25,10 @@ reference's label * obj * depth, and every batch carries xyz, normal, region, ma
 mask_obj, region_point, coordinate_choosed and depth_render. `meshes=True` only loads the meshes
 (faces, all vertices, symmetry sets) for the BOP pose errors (bop.py): `batch(idx, device, bop=True)`.
 
+`layout="bop"` reads `root` as a tree in BOP's own layout instead (bop_scene.py: several instances per image, a
+camera matrix and a depth scale per image, models_info.json; LM-O and its kin) and feeds the same kernels:
+see PoseDataset.
+
 `root=None` (the default; no LineMOD data ships with the reference and there is no network)
 serves seeded synthetic 640x480 RGB-D frames built like the real ones (an object mask inside a
 YOLO-like detection box whose snapped sizes follow the LineMOD test histogram, a depth plane
@@ -47,7 +51,9 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import bop as _bop
 from .bop import symmetry_set
+from .bop_scene import BopTree
 from .config import CONFIG, LM_OBJLIST, OBJ_DICT, SYM_OBJ, models_info
 from .raster import N_REGIONS, finish_maps, region_points, render_maps
 from .runtime import h2d, ptr, stream_ptr
@@ -65,12 +71,12 @@ def get_square_bbox(bbox, height_px: int = 480, width_px: int = 640) -> Tuple[in
     bbx = [bbox[1], bbox[1] + bbox[3], bbox[0], bbox[0] + bbox[2]]
     if bbx[0] < 0:
         bbx[0] = 0
-    if bbx[1] >= 480:
-        bbx[1] = 479
+    if bbx[1] >= height_px:
+        bbx[1] = height_px - 1
     if bbx[2] < 0:
         bbx[2] = 0
-    if bbx[3] >= 640:
-        bbx[3] = 639
+    if bbx[3] >= width_px:
+        bbx[3] = width_px - 1
     rmin, rmax, cmin, cmax = bbx
     rmax += 1
     cmax += 1
@@ -355,27 +361,61 @@ class PoseDataset(torch.utils.data.Dataset):
     batch(..., bop=True) and bop.bop_errors need; gt_maps=True implies it. The symmetry sets come from the
     optional keys symmetries_discrete / symmetries_continuous of the tree's models/models_info.yml; a stock
     Linemod_preprocessed tree has none, so every object, eggbox and glue included, then gets the identity
-    only and MSSD / MSPD are the plain maximum distances."""
+    only and MSSD / MSPD are the plain maximum distances.
+
+    layout="bop" reads `root` as a tree in BOP's own layout (bop_scene.BopTree: one item per GT instance of
+    `split`, filtered by the `targets` list and BOP-19's `min_visib` rule; several instances per image, a camera
+    matrix and a depth scale per image). Then each crop's K4 is its image's, `objlist` is the tree's (cls_type
+    None / "all": the sorted object ids that remain; a name: that object), extent, lfborder, diameter and the
+    region points' normalisation come from the tree's models/models_info.json (BOP's models are not in
+    Linemod_preprocessed's coordinates), sym_obj holds the classes whose entry there has a symmetry key, and the
+    crop boxes are snapped inside the tree's own frame size. masks="png" (default) takes mask_label from the
+    tree's mask_visib PNGs; masks="render" (needs meshes=True) takes it from bop.visibility of the GT pose
+    against the observed depth, for trees that ship none. layout="linemod" (default) changes nothing."""
 
     def __init__(self, mode: str = "test", num_point: int = 1000, add_noise: bool = False, root: Optional[str] = None,
                  noise_trans: float = 0.0, num_kps: int = 8, cls_type: Optional[str] = None, cfg=CONFIG,
                  num_frames: int = 256, seed: int = 0, sizes: Optional[Sequence[int]] = None,
-                 n_model_pts: int = 2600, io_threads: int = 8, gt_maps: bool = False, meshes: bool = False):
+                 n_model_pts: int = 2600, io_threads: int = 8, gt_maps: bool = False, meshes: bool = False,
+                 layout: str = "linemod", split: str = "test", targets: Optional[str] = None, min_visib: float = 0.1,
+                 masks: str = "png"):
+        if layout not in ("linemod", "bop"):
+            raise ValueError(f"layout must be 'linemod' or 'bop', got {layout!r}")
+        if masks not in ("png", "render"):
+            raise ValueError(f"masks must be 'png' or 'render', got {masks!r}")
+        self.layout, self.masks = layout, masks
         self.mode, self.num_point, self.cfg, self.root = mode, num_point, cfg, root
         self.gt_maps = bool(gt_maps)
         self.meshes = bool(meshes) or self.gt_maps
         if self.meshes and root is None:
             raise ValueError("gt_maps=True / meshes=True render from the objects' meshes and need a LineMOD tree "
                              "(root=None serves synthetic frames, which have no mesh)")
+        if masks == "render" and not (layout == "bop" and self.meshes):
+            raise ValueError("masks='render' renders mask_label from the objects' meshes: it needs layout='bop' and "
+                             "meshes=True (or gt_maps=True)")
+        if layout == "bop" and root is None:
+            raise ValueError("layout='bop' reads a tree in BOP's layout and needs root")
         if cls_type in (None, "all"):
             self.objlist = list(LM_OBJLIST)
         else:
             self.objlist = [OBJ_DICT[cls_type]]
         self.sym_obj = [i for i in SYM_OBJ if i < len(self.objlist)] if len(self.objlist) > 1 else []
-        info = models_info()
-        self.diameter = [info[o]["diameter"] / 1000.0 for o in self.objlist]
+        # per object {"min", "size" (mm, [3]), "diameter" (mm)}: the packaged yaml, or a BOP tree's models_info.json
+        self.obj_info = models_info()
         self.io_threads = io_threads
-        if root is not None:
+        self.frame_hw = (480, 640)
+        if layout == "bop":
+            self.tree = BopTree(root, split=split, targets=targets,
+                                objlist=None if cls_type in (None, "all") else self.objlist, n_model_pts=n_model_pts,
+                                seed=seed, meshes=self.meshes, min_visib=min_visib)
+            self.objlist = list(self.tree.objlist)
+            self.obj_info = {o: {"min": [e["min_x"], e["min_y"], e["min_z"]], "size": [e["size_x"], e["size_y"], e["size_z"]],
+                                 "diameter": e["diameter"]} for o, e in ((o, self.tree.info[o]) for o in self.objlist)}
+            self.sym_obj = [i for i, o in enumerate(self.objlist) if self.tree.has_symmetry(o)]
+            self.frame_hw = self.tree.frame_hw or self.frame_hw
+            self.frames_np = None
+            self.boxes = [get_square_bbox(it["bbox"], *self.frame_hw) for it in self.tree.items]
+        elif root is not None:
             self.tree = _LinemodTree(root, mode, self.objlist, n_model_pts, seed, meshes=self.meshes)
             self.frames_np = None
             self.boxes = [get_square_bbox(it["bbox"]) for it in self.tree.items]
@@ -383,6 +423,7 @@ class PoseDataset(torch.utils.data.Dataset):
             self.tree = None
             self.frames_np = synthetic_frames(num_frames, seed, self.objlist, sizes=sizes)
             self.boxes = [get_square_bbox([float(v) for v in bb]) for bb in self.frames_np["bbox"]]
+        self.diameter = [self.obj_info[o]["diameter"] / 1000.0 for o in self.objlist]
         self._dev_frames: Dict[str, Dict[str, torch.Tensor]] = {}
         self._dev_mesh: Dict[str, Dict[str, object]] = {}
         self._seed: Dict[str, torch.Tensor] = {}
@@ -413,10 +454,24 @@ class PoseDataset(torch.utils.data.Dataset):
     def _read_frames(self, idx: Sequence[int], device) -> Dict[str, torch.Tensor]:
         """Decode the batch's frames from the tree (thread pool) and stage them on `device`."""
         with ThreadPoolExecutor(max_workers=max(1, min(self.io_threads, len(idx)))) as ex:
-            fr = list(ex.map(self.tree.read, idx))
-        return {"rgb": h2d(torch.from_numpy(np.stack([f[0] for f in fr])), device),
-                "depth": h2d(torch.from_numpy(np.stack([f[1] for f in fr])), device),
-                "mask_label": h2d(torch.from_numpy(np.stack([f[2] for f in fr])), device)}
+            if self.layout == "bop":
+                # each distinct image is decoded once and stacked per item: the input kernels index the rgb, depth
+                # and mask planes by one frame[b] (the cover_frame convention), so per-item frames are what is fed
+                its = [self.tree.items[i] for i in idx]
+                keys = list(dict.fromkeys((int(it["scene"]), int(it["im"]), float(it["depth_scale"])) for it in its))
+                img = dict(zip(keys, ex.map(lambda k: self.tree.read_image(*k), keys)))
+                if self.masks == "render":
+                    ml = [None] * len(idx)
+                else:
+                    ml = list(ex.map(self.tree.read_mask, idx))
+                fr = [img[(int(it["scene"]), int(it["im"]), float(it["depth_scale"]))] + (m,) for it, m in zip(its, ml)]
+            else:
+                fr = list(ex.map(self.tree.read, idx))
+        out = {"rgb": h2d(torch.from_numpy(np.stack([f[0] for f in fr])), device),
+               "depth": h2d(torch.from_numpy(np.stack([f[1] for f in fr])), device)}
+        if fr[0][2] is not None:  # masks="render": batch() renders mask_label on the device
+            out["mask_label"] = h2d(torch.from_numpy(np.stack([f[2] for f in fr])), device)
+        return out
 
     def _meta(self, i: int):
         """(obj id, R [3,3] f64, t [3] f64, model points [P,3] f32) of crop i."""
@@ -436,7 +491,7 @@ class PoseDataset(torch.utils.data.Dataset):
         normalised points, batchdataset.py:723-728). Built once per device."""
         key = str(device)
         if key not in self._dev_mesh:
-            info = models_info()
+            info = self.obj_info
             if self.tree is None or not self.tree.mesh:
                 raise ValueError("this dataset holds no meshes: build it on a LineMOD tree with meshes=True (or "
                                  "gt_maps=True); root=None serves synthetic frames, which have no mesh")
@@ -484,12 +539,20 @@ class PoseDataset(torch.utils.data.Dataset):
         else:
             fr = self.frames(device)
             fidx = idx
-        K4 = torch.tensor([[LM_K[0, 0], LM_K[1, 1], LM_K[0, 2], LM_K[1, 2]]] * len(idx), dtype=torch.float32)
+        if self.layout == "bop":
+            K4 = torch.tensor([self.tree.items[i]["K4"] for i in idx], dtype=torch.float32)
+        else:
+            K4 = torch.tensor([[LM_K[0, 0], LM_K[1, 1], LM_K[0, 2], LM_K[1, 2]]] * len(idx), dtype=torch.float32)
         self._calls += 1
         boxes = [self.boxes[i] for i in idx]
         metas = [self._meta(i) for i in idx]
         R64 = torch.from_numpy(np.stack([m[1] for m in metas]))
         t64 = torch.from_numpy(np.stack([m[2] for m in metas]))
+        if "mask_label" not in fr:  # masks="render": the visible mask of the GT pose against the observed depth
+            mesh = self._mesh_for(device)
+            fr["mask_label"] = _bop.visibility(
+                mesh["verts"], mesh["faces"], torch.tensor([mesh["range"][m[0]] for m in metas], dtype=torch.int32),
+                R64, t64, K4, fr["depth"], torch.tensor(fidx, dtype=torch.int32))["mask_visib"]
         maps = None
         if self.gt_maps:
             mesh = self._mesh_for(device)
@@ -499,7 +562,7 @@ class PoseDataset(torch.utils.data.Dataset):
                                frame_hw=tuple(fr["depth"].shape[1:]))
         out = build_inputs(fr, fidx, boxes, self.num_point, K4, self._seed_for(device), stream_id=self._calls,
                            obj_mask=maps["cover_frame"] if maps is not None else None)
-        info = models_info()
+        info = self.obj_info
         ext = [np.array(info[m[0]]["size"]) / 1000.0 for m in metas]
         lfb = [np.array(info[m[0]]["min"]) / 1000.0 for m in metas]
         # every object keeps exactly num_pt_mesh_large model points (_LinemodTree / synthetic_frames), so

@@ -33,6 +33,7 @@ import torch.distributed as dist
 
 from . import distributed as kd
 from .bop import BOP_REC, FRAME_W, TAUS, bop_errors, fold_bop
+from .bop_scene import write_results
 from .dataset import PoseDataset
 from .krrn import KRRN
 from .loss import map_losses
@@ -48,6 +49,8 @@ _KEYS = ("all_num", "obj_num", "succ_base_rt", "dis_base_rt", "succ_base_r", "di
 # per-crop record (f64)
 REC = ("crop", "cls", "add_b", "r_b", "t_b", "add_f", "r_f", "t_f", "l_xyz", "l_mask", "l_normal", "valid")
 _R = {k: i for i, k in enumerate(REC)}
+# per-crop record of eval_records(poses=True) (f64): the scored pose, R row-major, t in metres
+POSE_REC = ("crop",) + tuple(f"r{k}" for k in range(9)) + ("tx", "ty", "tz")
 # what one evaluated batch leaves on the device until the epoch's single read-back (idx: its crop indices, on
 # the host; pred_t / add_f are None without opt_pose, lc without GT maps)
 _Batch = namedtuple("_Batch", "idx cls_id target_r target_t base_r base_t pred_t fin_r add_b add_f lc")
@@ -63,7 +66,7 @@ def _batches(buckets: Dict[int, List[int]], bs: int):
 @torch.no_grad()
 def eval_records(model: KRRN, dataset: PoseDataset, indices: Dict[int, List[int]], bs: int, device,
                  opt_pose: bool = True, with_loss: bool = True, pose_solver: str = "pnp",
-                 refine: Optional[str] = None, bop: bool = False):
+                 refine: Optional[str] = None, bop: bool = False, poses: bool = False):
     """Run the eval path over {S: [crop indices]} in batches of <= bs; returns f64 [n, len(REC)]
     (rows in the order evaluated). Every batch's inputs, forward, pose and ADD(-S) are queued on
     the device without a host round trip; the per-crop records are read back once at the end (the
@@ -87,7 +90,12 @@ def eval_records(model: KRRN, dataset: PoseDataset, indices: Dict[int, List[int]
     bop: also the BOP-19 errors (bop.bop_errors: VSD, MSSD, MSPD) of the final pose, i.e. (fin_r, pred_t) with
     opt_pose and the base pose without, as test_dis chooses; queued on the pose stream after add_metric and
     read back with everything else at the end. Needs a dataset with meshes. The return value is then the pair
-    (records, f64 [n, len(bop.BOP_REC)] in the same row order); every number of `records` is unchanged."""
+    (records, f64 [n, len(bop.BOP_REC)] in the same row order); every number of `records` is unchanged.
+
+    poses: also return an f64 [n, len(POSE_REC)] table in the same row order: crop, R row-major and t in metres of
+    the pose that test_dis scores (the final pose with opt_pose, else the base pose). It is read back
+    in the epoch's single read-back (the tensors are the ones the records are made from). The return value then
+    ends with it: (records, poses) or (records, bop table, poses)."""
     if pose_solver not in ("pnp", "umeyama"):
         raise ValueError(f"pose_solver must be 'pnp' or 'umeyama', got {pose_solver!r}")
     if refine not in (None, "icp"):
@@ -169,8 +177,10 @@ def eval_records(model: KRRN, dataset: PoseDataset, indices: Dict[int, List[int]
         for t in e.values():
             t.record_stream(main)
     if not pending:
-        empty = torch.zeros((0, len(REC)), dtype=torch.float64)
-        return (empty, torch.zeros((0, len(BOP_REC)), dtype=torch.float64)) if bop else empty
+        empty = (torch.zeros((0, len(REC)), dtype=torch.float64),)
+        empty += (torch.zeros((0, len(BOP_REC)), dtype=torch.float64),) if bop else ()
+        empty += (torch.zeros((0, len(POSE_REC)), dtype=torch.float64),) if poses else ()
+        return empty if len(empty) > 1 else empty[0]
     # one read-back and one vectorised host pass for the whole epoch: per batch, the rotation /
     # translation errors' six small copies and ~60 CPU ops ran after the GPU had drained (a serial
     # host tail of ~1 ms per batch); every quantity is per crop, so the values are the same
@@ -192,15 +202,25 @@ def eval_records(model: KRRN, dataset: PoseDataset, indices: Dict[int, List[int]
         rec[:, _R["add_f"]] = cat("add_f", 1).reshape(n).cpu().numpy()
         fin_r = cat("fin_r", 9) if refine else base_r
         rec[:, _R["r_f"]], rec[:, _R["t_f"]] = rt_errors(fin_r, cat("pred_t", 3), tr, tt)
+    prec = None
+    if poses:
+        prec = np.zeros((n, len(POSE_REC)), dtype=np.float64)
+        prec[:, 0] = rec[:, _R["crop"]]
+        if opt_pose:
+            prec[:, 1:10] = (cat("fin_r", 9) if refine else base_r).double().cpu().numpy()
+            prec[:, 10:13] = cat("pred_t", 3).double().cpu().numpy()
+        else:
+            prec[:, 1:10] = base_r.double().cpu().numpy()
+            prec[:, 10:13] = cat("base_t", 3).double().cpu().numpy()
     if not bop:
-        return torch.from_numpy(rec)
+        return (torch.from_numpy(rec), torch.from_numpy(prec)) if poses else torch.from_numpy(rec)
     T = len(TAUS)
     brec = np.zeros((n, len(BOP_REC)), dtype=np.float64)
     brec[:, 0], brec[:, 1], brec[:, -1] = rec[:, _R["crop"]], rec[:, _R["cls"]], 1.0
     brec[:, 2:2 + T] = torch.cat([e["vsd"] for e in bop_pending]).cpu().numpy()
     brec[:, 2 + T] = torch.cat([e["mssd"] for e in bop_pending]).cpu().numpy()
     brec[:, 3 + T] = torch.cat([e["mspd"] for e in bop_pending]).cpu().numpy()
-    return torch.from_numpy(rec), torch.from_numpy(brec)
+    return (torch.from_numpy(rec), torch.from_numpy(brec)) + ((torch.from_numpy(prec),) if poses else ())
 
 
 def fold_records(records: torch.Tensor, objlist: Sequence[int], diameter: Sequence[float], opt_pose: bool,
@@ -275,7 +295,7 @@ def gather_epoch_records(local: torch.Tensor, shard_sizes: Sequence[int], device
 def test_epoch(model: KRRN, dataset: PoseDataset, bs: int = 64, device=None, opt_pose: bool = True,
                criterion=None, world: Optional[int] = None, rank: Optional[int] = None,
                group=None, pose_solver: str = "pnp", refine: Optional[str] = None,
-               bop: bool = False) -> Dict[str, object]:
+               bop: bool = False, bop_csv: Optional[str] = None) -> Dict[str, object]:
     """Trainer.test_epoch over `dataset`. world/rank default to the initialised process group
     (1/0 without one). `criterion` enables the per-crop map-loss terms (dis_xyz / dis_mask /
     dis_normal) when the batches carry GT maps, i.e. for a PoseDataset built with gt_maps=True (a
@@ -283,7 +303,11 @@ def test_epoch(model: KRRN, dataset: PoseDataset, bs: int = 64, device=None, opt
     0. The reference always evaluates it (:167).
     `pose_solver` and `refine` as in eval_records. `bop` (off by default; needs a dataset with meshes) adds one
     key, "bop": bop.fold_bop's BOP-19 average recalls AR_VSD / AR_MSSD / AR_MSPD / AR of the final pose, per
-    object and overall; every other key is unchanged, bit for bit."""
+    object and overall; every other key is unchanged, bit for bit.
+    `bop_csv` (needs a dataset with layout="bop": the rows carry its scene and image ids) writes every crop's scored
+    pose as BOP's result CSV (bop_scene.write_results; t in millimetres) in crop order. The pose table is gathered
+    like the records and only rank 0 writes. score is 1.0 for every row: there is one estimate per target, so
+    nothing ranks on it; time is -1 (not measured per image). The returned dict is unchanged."""
     device = torch.device(device) if device is not None else next(model.parameters()).device
     if world is None:
         world = dist.get_world_size(group) if dist.is_initialized() else 1
@@ -293,9 +317,16 @@ def test_epoch(model: KRRN, dataset: PoseDataset, bs: int = 64, device=None, opt
         raise ValueError(f"rank {rank} outside world {world}")
     sizes = [dataset.crop_size(i) for i in range(len(dataset))]
     mine = kd.bucket_shard(sizes, world, rank)
+    if bop_csv and getattr(dataset, "layout", "linemod") != "bop":
+        raise ValueError("bop_csv writes BOP's scene / image ids: it needs a PoseDataset with layout='bop'")
     local = eval_records(model, dataset, mine, bs, device, opt_pose=opt_pose, with_loss=criterion is not None,
-                         pose_solver=pose_solver, refine=refine, **({"bop": True} if bop else {}))
-    local_bop = None
+                         pose_solver=pose_solver, refine=refine, **({"bop": True} if bop else {}),
+                         **({"poses": True} if bop_csv else {}))
+    local_bop = local_pose = None
+    if bop_csv:
+        local, local_pose = local[:-1] if bop else local[0], local[-1]
+        # gather_epoch_records marks pad rows by a last column `valid` = 0
+        local_pose = torch.cat([local_pose, torch.ones((local_pose.shape[0], 1), dtype=torch.float64)], 1)
     if bop:
         local, local_bop = local
     shard_sizes = [sum(len(v) for v in kd.bucket_shard(sizes, world, r).values()) for r in range(world)]
@@ -304,7 +335,19 @@ def test_epoch(model: KRRN, dataset: PoseDataset, bs: int = 64, device=None, opt
     out = fold_records(allrec, dataset.objlist, dataset.diameter, opt_pose, metric)
     if bop:  # a record table of its own, gathered by the same mechanism
         allbop = gather_epoch_records(local_bop, shard_sizes, device, group) if world > 1 else local_bop
-        out["bop"] = fold_bop(allbop, dataset.objlist, dataset.diameter, FRAME_W)
+        out["bop"] = fold_bop(allbop, dataset.objlist, dataset.diameter, getattr(dataset, "frame_hw", (0, FRAME_W))[1])
+    if bop_csv:
+        allpose = gather_epoch_records(local_pose, shard_sizes, device, group) if world > 1 else local_pose
+        if rank == 0:
+            tab = allpose.numpy()
+            tab = tab[tab[:, -1] > 0]
+            tab = tab[np.argsort(tab[:, 0], kind="stable")]
+            rows = []
+            for row in tab:
+                it = dataset.tree.items[int(row[0])]
+                rows.append({"scene_id": it["scene"], "im_id": it["im"], "obj_id": it["obj"], "score": 1.0,
+                             "R": row[1:10], "t": row[10:13] * 1000.0, "time": -1.0})
+            write_results(bop_csv, rows)
     if world > 1:
         # the ranks' own crop / success tallies, summed, must equal the gathered table's
         key = "add_f" if opt_pose else "add_b"
