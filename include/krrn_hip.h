@@ -287,7 +287,8 @@ int krrn_resize_bilinear_f32(const float* in, int B, int Hi, int Wi, int in_cs, 
                              int align_corners, int relu, void* stream);
 
 /* out = relu?(a + b) on NHWC channel slices (HRNet fuse identity term, myhrnet.py:237-238;
- * b == NULL copies a, the concat of myhrnet.py:516). */
+ * b == NULL copies a, the concat of myhrnet.py:516). C, strides and offsets multiples of 4, a / b /
+ * out 16-byte aligned (float4; KRRN_EALIGN otherwise). out may be a itself (same stride and offset). */
 int krrn_add_relu_f32(const float* a, int a_cs, int a_co, const float* b, int b_cs, int b_co, float* out,
                       int o_cs, int o_co, long long npix, int C, int relu, void* stream);
 

@@ -351,6 +351,7 @@ KRRN_API int krrn_add_relu_f32(const float* a, int a_cs, int a_co, const float* 
   if (npix < 1 || C < 1) return KRRN_ESHAPE;
   if ((C & 3) || (a_cs & 3) || (a_co & 3) || (o_cs & 3) || (o_co & 3) || (b && ((b_cs & 3) || (b_co & 3))))
     return KRRN_EALIGN;
+  if (!krrn_aligned16(a) || !krrn_aligned16(out) || (b && !krrn_aligned16(b))) return KRRN_EALIGN;
   const long long total = npix * (C / 4);
   if (total < 0x7fffffffLL)
     hipLaunchKernelGGL(add_relu_kernel<int>, grid1(total), dim3(256), 0, (hipStream_t)stream, a, a_cs, a_co, b, b_cs,

@@ -1,13 +1,16 @@
 """krrn_resize_bilinear_f32 (HRNet fuse / final upsample, myhrnet.py:242-245, 511-516; the heads'
 UpsamplingBilinear2d, krrn.py:56, 78) against torch's F.interpolate in f32, both conventions,
 with the fused residual add + ReLU, on NHWC channel slices; upsampling (2x2 outputs per thread,
-odd output sizes) and downsampling (one output per thread)."""
+odd output sizes) and downsampling (one output per thread). The 2x2 kernel is also run at a 1-pixel
+source, odd and identity sizes into a slice of a sentinel-filled buffer, and compared bit for bit with
+the one-output kernel on the same crop."""
 import pytest
 import torch
 import torch.nn.functional as F
 
 from pose_estimation_amd import _lib
 from pose_estimation_amd.runtime import P, ptr
+from tests.points_ref import EPS32, Guarded, resize_ref
 
 
 @pytest.mark.gpu
@@ -36,3 +39,73 @@ def test_resize_matches_torch(dev, B, C, Hi, Wi, Ho, Wo, align, fused):
               ptr(add), C + pad, pad, int(align), int(fused), P(torch.cuda.current_stream().cuda_stream))
     got = od.cpu()[..., pad:].permute(0, 3, 1, 2)
     torch.testing.assert_close(got, ref, rtol=1e-5, atol=1e-5)
+
+
+def _resize(dev, x, Ho, Wo, align, base):
+    """krrn_resize_bilinear_f32 of NCHW x (fused with + base and ReLU if base is given) into a C-wide slice
+    at column 4 of pixel rows C + 8 wide in a sentinel-filled buffer with guard rows; returns NCHW."""
+    B, C, Hi, Wi = x.shape
+    pad = 4
+    xin = torch.full((B, Hi, Wi, C + 2 * pad), float("nan"))
+    xin[..., pad:pad + C] = x.permute(0, 2, 3, 1)
+    out = Guarded(1, B * Ho * Wo, C, stride=C + 8, off=4, device=dev)
+    if base is not None:
+        out.fill(base.permute(0, 2, 3, 1).reshape(1, B * Ho * Wo, C))
+    xd = xin.to(dev)
+    obase = P(out.buf.data_ptr() + 4 * out.stride)  # base pointer + channel offset, as the ABI takes them
+    _lib.call("krrn_resize_bilinear_f32", ptr(xd), B, Hi, Wi, C + 2 * pad, pad, C, obase, Ho, Wo, out.stride, out.off,
+              obase if base is not None else P(0), out.stride, out.off, int(align), int(base is not None),
+              P(torch.cuda.current_stream().cuda_stream))
+    torch.cuda.synchronize()
+    return out.result().view(B, Ho, Wo, C).permute(0, 3, 1, 2)
+
+
+def _quads2x2(B, C, Ho, Wo):
+    return B * ((Ho + 1) // 2) * ((Wo + 1) // 2) * (C // 4)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("fused", [False, True], ids=["plain", "add-relu"])
+@pytest.mark.parametrize("align", [False, True], ids=["half-pixel", "align-corners"])
+@pytest.mark.parametrize("Hi,Wi,Ho,Wo", [(1, 1, 128, 128), (2, 3, 127, 129), (128, 128, 128, 128)],
+                         ids=["up2x2-1x1-source", "up2x2-2x3-to-odd-127x129", "up2x2-identity-128"])
+def test_resize_up2x2_kernel(dev, Hi, Wi, Ho, Wo, align, fused):
+    """resize_up2x2_kernel needs B * ceil(Ho / 2) * ceil(Wo / 2) * C / 4 >= 2^21 output quads: C = 1024,
+    B = 2. A 1-pixel source (every clamp at once), odd output sizes (the last 2x2 group is cut on both
+    axes) and the identity size (source windows move by exactly one pixel per output)."""
+    B, C = 2, 1024
+    assert Ho >= Hi and Wo >= Wi and _quads2x2(B, C, Ho, Wo) >= 1 << 21
+    g = torch.Generator().manual_seed(Hi * 1000 + Wo)
+    x = torch.randn(B, C, Hi, Wi, generator=g)
+    ref = F.interpolate(x, size=(Ho, Wo), mode="bilinear", align_corners=align)
+    base = None
+    if fused:
+        base = torch.randn(B, C, Ho, Wo, generator=g)
+        ref = torch.relu(ref + base)
+    got = _resize(dev, x, Ho, Wo, align, base)
+    torch.testing.assert_close(got, ref, rtol=1e-5, atol=1e-5)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("fused", [False, True], ids=["plain", "add-relu"])
+@pytest.mark.parametrize("align", [False, True], ids=["half-pixel", "align-corners"])
+def test_resize_up2x2_is_bit_identical_to_one_output_kernel(dev, align, fused):
+    """The 2x2 kernel's comment promises the one-output kernel's bits: the same crop once in a batch of two
+    (2^21 quads or more: the 2x2 kernel) and once alone (under 2^21: the one-output kernel)."""
+    B, C, Hi, Wi, Ho, Wo = 2, 1024, 50, 37, 127, 129
+    assert _quads2x2(B, C, Ho, Wo) >= 1 << 21 > _quads2x2(1, C, Ho, Wo)
+    g = torch.Generator().manual_seed(7 + int(align))
+    x = torch.randn(B, C, Hi, Wi, generator=g)
+    base = torch.randn(B, C, Ho, Wo, generator=g) if fused else None
+    both = _resize(dev, x, Ho, Wo, align, base)
+    b = B - 1
+    alone = _resize(dev, x[b:b + 1], Ho, Wo, align, base[b:b + 1] if fused else None)
+    assert torch.equal(alone[0], both[b])
+    # and both are the float64 interpolation up to the f32 source coordinate: scale, product and - 0.5 are
+    # three roundings of a coordinate <= Hi (Wi), each moving the sample by at most the largest step
+    # between neighbours (<= 2 max|x|); the blend's six operations and the add round once each
+    ref = resize_ref(x[:1], Ho, Wo, align)
+    if fused:
+        ref = torch.relu(ref + base[:1].double())
+    bound = EPS32 * (float(x[:1].abs().max()) * (6 * (Hi + Wi) + 6) + 2 * ref.abs())
+    assert ((both[:1].double() - ref).abs() <= bound).all()
