@@ -159,6 +159,21 @@ int krrn_gemm_x3_gather_f32(const int* ia, const float* A, long long a_bs, int a
                             long long a2_bs, int a2_st, int npts, int B, int K, int N, const void* w3f,
                             const float* bias, float* out, int ldo, int relu, void* stream);
 
+/* Live-row forms of the two GEMMs above, for TBase on a crop's distinct rows (posenet.py:51-96 with
+ * pred_t of krrn.py:150-153: a point's h1 row depends only on its (nearest_pool_1, nearest_pool_2)
+ * pair, krrn_pair_compact_i32): live int32 [batch] / [B] = rows in use per group. Row tiles (128
+ * rows) are per group (the gathered form tiles each crop's npts rows, out[(b*npts + j)*ldo + n]); a
+ * tile that starts at or past live[g] is skipped and writes nothing, a partly live tile is computed
+ * whole (its reads and stores stay inside the group's rows). Live rows equal the rows of the forms
+ * above bit for bit. live must not be NULL (KRRN_EARG); other arguments and limits as above. */
+int krrn_gemm_x3_live_f32(const float* a, int lda, int M, int K, int N, const void* w3f, const float* bias,
+                          const float* res, int ldr, float* out, int ldo, int relu, int batch, long long a_grp,
+                          long long o_grp, long long r_grp, const int* live, void* stream);
+int krrn_gemm_x3_gather_live_f32(const int* ia, const float* A, long long a_bs, int a_st, const int* ib,
+                                 const float* A2, long long a2_bs, int a2_st, int npts, int B, int K, int N,
+                                 const void* w3f, const float* bias, float* out, int ldo, int relu, const int* live,
+                                 void* stream);
+
 /* Short-K GEMM streaming its output (gemm_panel.hip): the fusion's level-0 / level-1 GCN
  * `feature_map @ weights + bias` of Conv_layer (lib/network/point/gcn3d.py:136-164, K = 128,
  * N = 8 * 128) and layer1's 64 -> 256 1x1 convs (myhrnet.py:65-103, K = 64):
@@ -328,6 +343,20 @@ int krrn_gather2_add_f32(const int* ia, const float* A, long long a_bs, int a_st
  * C multiple of 4, h and w4 16-byte aligned (KRRN_EALIGN otherwise). */
 int krrn_tbase_tail_f32(const float* h, int B, int n, int C, const float* w4, const float* b4, const float* cloud,
                         float* pred_t, float* t_res, void* stream);
+
+/* The same tail reading point i's row at h[b][slot[b][i]] (slot int32 [B][n], values < n): TBase on
+ * the crop's distinct rows (posenet.py:51-96, krrn.py:150-153). Same loop, lane mapping and reduction
+ * tree, so pred_t / t_res equal krrn_tbase_tail_f32's on the expanded h bit for bit. */
+int krrn_tbase_tail_slot_f32(const float* h, const int* slot, int B, int n, int C, const float* w4, const float* b4,
+                             const float* cloud, float* pred_t, float* t_res, void* stream);
+
+/* Distinct (ia, ib) pairs per crop (posenet.py:51-96, krrn.py:150-153: TBase's row of a point depends
+ * only on its two nearest indices). ia / ib int32 [B][npts] with values < n1 / < n2; keys ia*n2 + ib.
+ * cnt[b] = number of distinct keys; (pa, pb)[b][j], j < cnt[b], = the distinct pairs in ascending key
+ * order, entries j >= cnt[b] repeat entry 0; slot[b][i] = the rank of point i's key. One block per
+ * crop, deterministic. n1 * n2 <= 2^18 and npts <= 65535 (KRRN_ESHAPE otherwise). */
+int krrn_pair_compact_i32(const int* ia, const int* ib, int B, int npts, int n1, int n2, int* cnt, int* pa, int* pb,
+                          int* slot, void* stream);
 
 /* Batched PnP-RANSAC: Trainer.get_pose (tools/trainer.py:383-438), cv2.solvePnPRansac(EPNP,
  * reprojectionError = thr, confidence = conf (0.9999 there), iterationsCount = H) restated.

@@ -31,6 +31,13 @@
 // staged, A[m, k] = relu(P[b, ia[b, i], k] + Q[b, ib[b, i], k]), from two small per-crop row tables —
 // TBase conv1 by linearity (posenet.py: the fusion's level rows times W1, BN / bias / one-hot
 // column folded into them) feeding conv2 directly, so the 1024-wide h1 is never written to HBM.
+//
+// Live-row forms (krrn_gemm_x3_live_f32, krrn_gemm_x3_gather_live_f32): live[g] of group g's rows are
+// in use (TBase on the distinct (nn1, nn2) rows of a crop, krrn_pair_compact_i32). Row tiles are per
+// group; a block whose tile starts at or past live[g] returns before its first load and barrier (the
+// condition is uniform over the block) and writes nothing. A partly live tile is computed whole:
+// its reads and stores stay inside the group's rows. A row's result depends on that row and the
+// weights only (same k order, no cross-row term), so live rows equal the plain forms' bit for bit.
 #include "krrn_common.h"
 #include "krrn_split.h"
 
@@ -43,12 +50,15 @@ constexpr int PX = 3 * KC + 4;  // dwords per LDS row: 12 per 4 k + 4 pad (odd n
 
 struct GemmArgs {
   const float* a;
-  // GA: A[m] = relu(a[b * a_grp + ia[m] * lda] + a2[b * a2_grp + ib[m] * lda2]), b = m / npts
+  // GA: A[m] = relu(a[b * a_grp + ia[m] * lda] + a2[b * a2_grp + ib[m] * lda2]), b = m / npts over
+  // the flat B * npts rows (i_grp = 0), or one group of M = npts rows per crop (i_grp = npts: crop
+  // b = the group, its indices at ia + b * i_grp)
   const float* a2;
   const int* ia;
   const int* ib;
   long long a2_grp;
-  int lda2, npts;
+  int lda2, npts, nb, i_grp;  // nb: crops in the row tables
+  const int* live;            // rows in use per group (null: all M)
   const unsigned* w;  // wave fragments [N/32][K/8][2][64][4]
   const float* bias;
   const float* res;
@@ -75,6 +85,7 @@ __global__ __launch_bounds__(256, 2) void gemm_x3_kernel(const GemmArgs g) {
   const int grp = bid / tpg, rem = bid - grp * tpg;
   const int tm = rem / g.nt, tn = rem - tm * g.nt;
   const int m0 = tm * BM, n0 = tn * BN;
+  if (g.live && m0 >= g.live[grp]) return;  // no live row in this tile (uniform over the block)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int frow = lane & 31, fh = lane >> 5;
 
@@ -85,19 +96,20 @@ __global__ __launch_bounds__(256, 2) void gemm_x3_kernel(const GemmArgs g) {
   // GA: the two row tables are whole buffer resources (bounds checked on the host); rows past M
   // read 0 through an out-of-range offset
   const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)abase, (short)0, GA ? (int)(g.a_grp * (g.M / g.npts) * 4) : ((rows - 1) * g.lda + g.K) * 4, 0x00020000);
+      (void*)abase, (short)0, GA ? (int)(g.a_grp * g.nb * 4) : ((rows - 1) * g.lda + g.K) * 4, 0x00020000);
   __amdgpu_buffer_rsrc_t rsA2;
   unsigned aoff[2], aoff2[2];
   if constexpr (GA) {
-    rsA2 = __builtin_amdgcn_make_buffer_rsrc((void*)g.a2, (short)0, (int)(g.a2_grp * (g.M / g.npts) * 4),
+    rsA2 = __builtin_amdgcn_make_buffer_rsrc((void*)g.a2, (short)0, (int)(g.a2_grp * g.nb * 4),
                                              0x00020000);
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       const int m = m0 + srow + 64 * i;
       if (m < g.M) {
-        const int b = m / g.npts;
-        aoff[i] = (unsigned)((b * g.a_grp + (long long)g.ia[m] * g.lda + kq) * 4);
-        aoff2[i] = (unsigned)((b * g.a2_grp + (long long)g.ib[m] * g.lda2 + kq) * 4);
+        const int b = g.i_grp ? grp : m / g.npts;
+        const long long ii = (long long)grp * g.i_grp + m;
+        aoff[i] = (unsigned)((b * g.a_grp + (long long)g.ia[ii] * g.lda + kq) * 4);
+        aoff2[i] = (unsigned)((b * g.a2_grp + (long long)g.ib[ii] * g.lda2 + kq) * 4);
       } else {
         aoff[i] = aoff2[i] = 0x80000000u;
       }
@@ -267,9 +279,11 @@ __global__ __launch_bounds__(256, 2) void gemm_x3_kernel(const GemmArgs g) {
 
 }  // namespace
 
-KRRN_API int krrn_gemm_x3_f32(const float* a, int lda, int M, int K, int N, const void* w3f, const float* bias,
-                              const float* res, int ldr, float* out, int ldo, int relu, int batch, long long a_grp,
-                              long long o_grp, long long r_grp, void* stream) {
+namespace {
+
+int launch_plain(const float* a, int lda, int M, int K, int N, const void* w3f, const float* bias, const float* res,
+                 int ldr, float* out, int ldo, int relu, int batch, long long a_grp, long long o_grp,
+                 long long r_grp, const int* live, void* stream) {
   if (!a || !w3f || !out) return KRRN_EARG;
   if (M < 1 || K < KC || N < BN || batch < 1) return KRRN_ESHAPE;
   if ((K % (2 * KC)) || (N % BN) || lda < K || ldo < N) return KRRN_ESHAPE;
@@ -280,7 +294,8 @@ KRRN_API int krrn_gemm_x3_f32(const float* a, int lda, int M, int K, int N, cons
   const long long tiles = (long long)krrn_cdiv(M, BM) * (N / BN) * batch;
   if (tiles > 0x7FFFFFFFLL) return KRRN_ESHAPE;
   GemmArgs g;
-  g.a = a; g.a2 = nullptr; g.ia = g.ib = nullptr; g.a2_grp = 0; g.lda2 = 0; g.npts = 1;
+  g.a = a; g.a2 = nullptr; g.ia = g.ib = nullptr; g.a2_grp = 0; g.lda2 = 0; g.npts = 1; g.nb = 1; g.i_grp = 0;
+  g.live = live;
   g.w = reinterpret_cast<const unsigned*>(w3f); g.bias = bias; g.res = res; g.out = out;
   g.lda = lda; g.M = M; g.K = K; g.N = N; g.ldr = ldr; g.ldo = ldo; g.relu = relu;
   g.a_grp = a_grp; g.o_grp = o_grp; g.r_grp = r_grp;
@@ -289,10 +304,10 @@ KRRN_API int krrn_gemm_x3_f32(const float* a, int lda, int M, int K, int N, cons
   return krrn_launch_status();
 }
 
-KRRN_API int krrn_gemm_x3_gather_f32(const int* ia, const float* A, long long a_bs, int a_st, const int* ib,
-                                     const float* A2, long long a2_bs, int a2_st, int npts, int B, int K, int N,
-                                     const void* w3f, const float* bias, float* out, int ldo, int relu,
-                                     void* stream) {
+// live null: the flat B * npts rows in one group; else one group of npts rows per crop
+int launch_gather(const int* ia, const float* A, long long a_bs, int a_st, const int* ib, const float* A2,
+                  long long a2_bs, int a2_st, int npts, int B, int K, int N, const void* w3f, const float* bias,
+                  float* out, int ldo, int relu, const int* live, void* stream) {
   if (!ia || !A || !ib || !A2 || !w3f || !out) return KRRN_EARG;
   if (npts < 1 || B < 1 || K < KC || N < BN) return KRRN_ESHAPE;
   if ((K % (2 * KC)) || (N % BN) || a_st < K || a2_st < K || ldo < N) return KRRN_ESHAPE;
@@ -302,15 +317,48 @@ KRRN_API int krrn_gemm_x3_gather_f32(const int* ia, const float* A, long long a_
   // their crop's table (a_bs / a_st floats), as krrn_gather2_add_f32 does
   if ((long long)B * a_bs * 4 >= 0x7FFFFFFFLL || (long long)B * a2_bs * 4 >= 0x7FFFFFFFLL) return KRRN_ESHAPE;
   const long long M = (long long)B * npts;
-  const long long tiles = (long long)krrn_cdiv(M, BM) * (N / BN);
+  const long long tiles = live ? (long long)krrn_cdiv(npts, BM) * (N / BN) * B : (long long)krrn_cdiv(M, BM) * (N / BN);
   if (M > 0x7FFFFFFFLL || tiles > 0x7FFFFFFFLL) return KRRN_ESHAPE;
   GemmArgs g;
   g.a = A; g.a2 = A2; g.ia = ia; g.ib = ib; g.a_grp = a_bs; g.a2_grp = a2_bs; g.lda = a_st; g.lda2 = a2_st;
-  g.npts = npts;
+  g.npts = npts; g.nb = B; g.i_grp = live ? npts : 0; g.live = live;
   g.w = reinterpret_cast<const unsigned*>(w3f); g.bias = bias; g.res = nullptr; g.out = out;
-  g.M = (int)M; g.K = K; g.N = N; g.ldr = 0; g.ldo = ldo; g.relu = relu;
-  g.o_grp = 0; g.r_grp = 0;
+  g.M = live ? npts : (int)M; g.K = K; g.N = N; g.ldr = 0; g.ldo = ldo; g.relu = relu;
+  g.o_grp = live ? (long long)npts * ldo : 0; g.r_grp = 0;
   g.mt = krrn_cdiv(g.M, BM); g.nt = N / BN; g.total = (int)tiles;
   hipLaunchKernelGGL(gemm_x3_kernel<true>, dim3((unsigned)tiles), dim3(256), 0, (hipStream_t)stream, g);
   return krrn_launch_status();
+}
+
+}  // namespace
+
+KRRN_API int krrn_gemm_x3_f32(const float* a, int lda, int M, int K, int N, const void* w3f, const float* bias,
+                              const float* res, int ldr, float* out, int ldo, int relu, int batch, long long a_grp,
+                              long long o_grp, long long r_grp, void* stream) {
+  return launch_plain(a, lda, M, K, N, w3f, bias, res, ldr, out, ldo, relu, batch, a_grp, o_grp, r_grp, nullptr,
+                      stream);
+}
+
+KRRN_API int krrn_gemm_x3_live_f32(const float* a, int lda, int M, int K, int N, const void* w3f, const float* bias,
+                                   const float* res, int ldr, float* out, int ldo, int relu, int batch,
+                                   long long a_grp, long long o_grp, long long r_grp, const int* live, void* stream) {
+  if (!live) return KRRN_EARG;
+  return launch_plain(a, lda, M, K, N, w3f, bias, res, ldr, out, ldo, relu, batch, a_grp, o_grp, r_grp, live, stream);
+}
+
+KRRN_API int krrn_gemm_x3_gather_f32(const int* ia, const float* A, long long a_bs, int a_st, const int* ib,
+                                     const float* A2, long long a2_bs, int a2_st, int npts, int B, int K, int N,
+                                     const void* w3f, const float* bias, float* out, int ldo, int relu,
+                                     void* stream) {
+  return launch_gather(ia, A, a_bs, a_st, ib, A2, a2_bs, a2_st, npts, B, K, N, w3f, bias, out, ldo, relu, nullptr,
+                       stream);
+}
+
+KRRN_API int krrn_gemm_x3_gather_live_f32(const int* ia, const float* A, long long a_bs, int a_st, const int* ib,
+                                          const float* A2, long long a2_bs, int a2_st, int npts, int B, int K, int N,
+                                          const void* w3f, const float* bias, float* out, int ldo, int relu,
+                                          const int* live, void* stream) {
+  if (!live) return KRRN_EARG;
+  return launch_gather(ia, A, a_bs, a_st, ib, A2, a2_bs, a2_st, npts, B, K, N, w3f, bias, out, ldo, relu, live,
+                       stream);
 }

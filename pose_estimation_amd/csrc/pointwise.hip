@@ -212,6 +212,7 @@ __global__ __launch_bounds__(64 * kTailWaves) void tbase_tail_kernel(const float
                                                          const float* __restrict__ w4,
                                                          const float* __restrict__ b4,
                                                          const float* __restrict__ cloud,
+                                                         const int* __restrict__ slot,
                                                          float* __restrict__ pred_t, float* __restrict__ t_res) {
   __shared__ float red[kTailWaves][3];
   const int b = blockIdx.x;
@@ -223,7 +224,10 @@ __global__ __launch_bounds__(64 * kTailWaves) void tbase_tail_kernel(const float
   for (int i0 = 0; i0 < n; i0 += 16 * kTailWaves) {
     const int i = i0 + wave * 16 + pl;
     if (i < n) {
-      const f32x4* hr = reinterpret_cast<const f32x4*>(h + ((long long)b * n + i) * C);
+      // slot: point i's row is h[b, slot[b, i]] (TBase on the crop's distinct rows); same loop,
+      // lane mapping and reduction tree either way
+      const int r = slot ? slot[(long long)b * n + i] : i;
+      const f32x4* hr = reinterpret_cast<const f32x4*>(h + ((long long)b * n + r) * C);
       float a0 = 0.f, a1 = 0.f, a2 = 0.f;
       for (int c4 = q; c4 < C4; c4 += 4) {
         const f32x4 x = hr[c4];
@@ -299,6 +303,82 @@ __global__ void gather2_add_kernel(const int* __restrict__ ia, const float* __re
     v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
   }
   *reinterpret_cast<f32x4*>(out + b * o_bs + (long long)i * o_st + 4 * c4) = v;
+}
+
+// The distinct (ia, ib) pairs of a crop's points, in ascending key order (key = ia * n2 + ib), and each
+// point's rank among them: TBase's h1 row of a point (posenet.py:51-96 on the concat of
+// fusion.py:234-238) is a function of its (nearest_pool_1, nearest_pool_2) pair only, so conv2 / conv3
+// run once per distinct pair and krrn_tbase_tail_slot_f32 reads row slot[i] (krrn.py:150-153).
+// One block per crop, nothing shared between blocks: the keys set bits of an LDS bitmap (an OR, so
+// the order of the points does not matter), a key's rank is the number of set bits below it (a block
+// scan of the words' popcounts), entries past cnt repeat entry 0 so every index stays in range.
+// A point's key; the indices are clamped into their tables, so a bad index can not leave the bitmap.
+__device__ __forceinline__ int pair_key(int a, int b, int n1, int n2) {
+  return min(max(a, 0), n1 - 1) * n2 + min(max(b, 0), n2 - 1);
+}
+constexpr int kPairThreads = 256;
+constexpr int kPairWords = 8192;  // 2^18 keys: n1 * n2 of the largest plan (1024 x 256)
+__global__ __launch_bounds__(kPairThreads) void pair_compact_kernel(const int* __restrict__ ia,
+                                                                    const int* __restrict__ ib, int npts, int n1,
+                                                                    int n2, int words, int* __restrict__ cnt,
+                                                                    int* __restrict__ pa, int* __restrict__ pb,
+                                                                    int* __restrict__ slot) {
+  __shared__ unsigned bits[kPairWords];
+  __shared__ unsigned short pre[kPairWords];  // set bits below word w (<= npts <= 65535)
+  __shared__ int part[kPairThreads];
+  __shared__ int first_key;
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int* ka = ia + (long long)b * npts;
+  const int* kb = ib + (long long)b * npts;
+  for (int w = tid; w < words; w += kPairThreads) bits[w] = 0u;
+  __syncthreads();
+  for (int i = tid; i < npts; i += kPairThreads) {
+    const int key = pair_key(ka[i], kb[i], n1, n2);
+    atomicOr(&bits[key >> 5], 1u << (key & 31));
+  }
+  __syncthreads();
+  // thread t owns the words [t * per, t * per + per)
+  const int per = (words + kPairThreads - 1) / kPairThreads;
+  const int w0 = min(tid * per, words), w1 = min(w0 + per, words);
+  int mine = 0;
+  for (int w = w0; w < w1; ++w) mine += __popc(bits[w]);
+  part[tid] = mine;
+  __syncthreads();
+  for (int off = 1; off < kPairThreads; off <<= 1) {  // inclusive scan of the threads' totals
+    const int v = tid >= off ? part[tid - off] : 0;
+    __syncthreads();
+    part[tid] += v;
+    __syncthreads();
+  }
+  const int total = part[kPairThreads - 1];
+  int rank = part[tid] - mine;
+  int* qa = pa + (long long)b * npts;
+  int* qb = pb + (long long)b * npts;
+  for (int w = w0; w < w1; ++w) {
+    pre[w] = (unsigned short)rank;
+    unsigned m = bits[w];
+    while (m) {
+      const int key = 32 * w + __ffs(m) - 1;
+      m &= m - 1;
+      if (rank == 0) first_key = key;
+      qa[rank] = key / n2;
+      qb[rank] = key - (key / n2) * n2;
+      ++rank;
+    }
+  }
+  __syncthreads();
+  if (tid == 0) cnt[b] = total;
+  const int a0 = first_key / n2, b0 = first_key - a0 * n2;
+  for (int j = total + tid; j < npts; j += kPairThreads) {
+    qa[j] = a0;
+    qb[j] = b0;
+  }
+  int* sl = slot + (long long)b * npts;
+  for (int i = tid; i < npts; i += kPairThreads) {
+    const int key = pair_key(ka[i], kb[i], n1, n2);
+    const int w = key >> 5;
+    sl[i] = (int)pre[w] + __popc(bits[w] & ((1u << (key & 31)) - 1u));
+  }
 }
 
 inline dim3 grid1(long long total) { return dim3((unsigned)((total + 255) / 256)); }
@@ -419,8 +499,30 @@ KRRN_API int krrn_tbase_tail_f32(const float* h, int B, int n, int C, const floa
   if (!h || !w4 || !b4 || !cloud || !pred_t) return KRRN_EARG;
   if (B < 1 || n < 1 || C < 1) return KRRN_ESHAPE;
   if ((C & 3) || !krrn_aligned16(h) || !krrn_aligned16(w4)) return KRRN_EALIGN;
-  hipLaunchKernelGGL(tbase_tail_kernel, dim3(B), dim3(64 * kTailWaves), 0, (hipStream_t)stream, h, n, C, w4, b4, cloud, pred_t,
-                     t_res);
+  hipLaunchKernelGGL(tbase_tail_kernel, dim3(B), dim3(64 * kTailWaves), 0, (hipStream_t)stream, h, n, C, w4, b4, cloud,
+                     (const int*)nullptr, pred_t, t_res);
+  return krrn_launch_status();
+}
+
+KRRN_API int krrn_tbase_tail_slot_f32(const float* h, const int* slot, int B, int n, int C, const float* w4,
+                                      const float* b4, const float* cloud, float* pred_t, float* t_res,
+                                      void* stream) {
+  if (!h || !slot || !w4 || !b4 || !cloud || !pred_t) return KRRN_EARG;
+  if (B < 1 || n < 1 || C < 1) return KRRN_ESHAPE;
+  if ((C & 3) || !krrn_aligned16(h) || !krrn_aligned16(w4)) return KRRN_EALIGN;
+  hipLaunchKernelGGL(tbase_tail_kernel, dim3(B), dim3(64 * kTailWaves), 0, (hipStream_t)stream, h, n, C, w4, b4, cloud,
+                     slot, pred_t, t_res);
+  return krrn_launch_status();
+}
+
+KRRN_API int krrn_pair_compact_i32(const int* ia, const int* ib, int B, int npts, int n1, int n2, int* cnt, int* pa,
+                                   int* pb, int* slot, void* stream) {
+  if (!ia || !ib || !cnt || !pa || !pb || !slot) return KRRN_EARG;
+  if (B < 1 || npts < 1 || n1 < 1 || n2 < 1) return KRRN_ESHAPE;
+  // the key bitmap and its 16-bit rank table live in LDS
+  if ((long long)n1 * n2 > 32LL * kPairWords || npts > 0xFFFF) return KRRN_ESHAPE;
+  hipLaunchKernelGGL(pair_compact_kernel, dim3(B), dim3(kPairThreads), 0, (hipStream_t)stream, ia, ib, npts, n1, n2,
+                     (n1 * n2 + 31) / 32, cnt, pa, pb, slot);
   return krrn_launch_status();
 }
 

@@ -40,7 +40,7 @@ from .config import CONFIG
 from .fusion import FEAT_SID, FusionNetLite, build_fusion_plan, emit_fusion_cloud_part, level_sizes
 from .hrnet import _Builder, build_hrnet, build_hrnet_plan
 from .ops import Act, pad4
-from .posenet import PoseNet, build_tbase_plan, emit_tbase_level1
+from .posenet import PoseNet, build_tbase_plan, emit_pair_compact, emit_tbase_level1
 from .runtime import Late, Plan, RngStream, add_conv, h2d, ptr
 
 # the wide head's final 1x1 conv (xyz_final, K = 128) on split-bf16 operands (f32 accuracy,
@@ -202,6 +202,11 @@ class KRRNPlan:
 
             if TBASE_EARLY:
                 hooks["level1"].append(tracked(emit_tb_l1))
+            # TBase's distinct (nn1, nn2) pairs per crop (posenet.emit_pair_compact): right behind nn2 on
+            # its stream, beside the level-2 convs (nothing emitted with KRRN_TBASE_DISTINCT=0)
+            tb_pairs = {}
+            hooks["pairs"] = [tracked(lambda fb: tb_pairs.update(
+                emit_pair_compact(plan, B, N, N1, N2, fb["nn1"], fb["nn2"]) or {}))]
             f0 = len(plan.ops)
             feat, self.fusion_bufs = build_fusion_plan(model.fusion, plan, B, N, self.p9, self.perms, hooks=hooks,
                                                        materialize=model.keep_fusion_feat, early=early)
@@ -214,7 +219,8 @@ class KRRNPlan:
                           N2=N2)
             self.pred_t, self.tbase_bufs = build_tbase_plan(model.pose.t_net, plan, B, N, feat, "cls", "cloud",
                                                             cfg.Module.POSENet.INC_R, C, levels=levels,
-                                                            pre=tb_pre or None, pre_sid=tb_sid)
+                                                            pre=tb_pre or None, pre_sid=tb_sid,
+                                                            pairs=tb_pairs or None)
             if feat is not None:
                 plan.join([FEAT_SID])
         if pose_hook is not None:

@@ -24,6 +24,10 @@ from .runtime import Late, Plan, add_conv, add_gemm, ptr
 # conv2 gathers h1 = ReLU(P1[nn1] + P2[nn2]) inside its operand staging (krrn_gemm_x3_gather_f32)
 # instead of a separate gather-add launch writing the 262 MB h1 (KRRN_TBASE_GATHER=0: the old form)
 TBASE_GATHER = knobs.flag("KRRN_TBASE_GATHER")
+# with TBASE_GATHER: conv2 / conv3 once per distinct (nn1, nn2) pair of a crop (h1's row is a function
+# of the pair only; ~36 % of the points at config 2), the tail reads each point's row by its slot
+TBASE_DISTINCT = knobs.flag("KRRN_TBASE_DISTINCT")
+PAIR_MAX_KEYS = 1 << 18  # krrn_pair_compact_i32's LDS key bitmap (N1 * N2 of config 5: 1024 x 256)
 
 
 class TBase(nn.Module):
@@ -112,8 +116,25 @@ def emit_tbase_level1(tb: TBase, plan: Plan, B: int, N: int, N1: int, feat1: tor
     return dict(P1=P1, Q=Q)
 
 
+def emit_pair_compact(plan: Plan, B: int, N: int, N1: int, N2: int, nn1: torch.Tensor,
+                      nn2: torch.Tensor) -> Optional[dict]:
+    """The distinct (nn1, nn2) pairs of every crop, on the plan's current stream: cnt [B], the pairs
+    pa / pb [B, N] in ascending key order (entries past cnt repeat entry 0) and each point's slot
+    [B, N] (krrn_pair_compact_i32). It needs only the two nearest-index buffers, so the fusion emits
+    it right behind them. None when TBase runs per point: the knobs, or a shape past the kernel's
+    limits (it would return KRRN_ESHAPE)."""
+    if not (TBASE_GATHER and TBASE_DISTINCT) or N1 * N2 > PAIR_MAX_KEYS or N > 0xFFFF:
+        return None
+    i32 = torch.int32
+    pr = dict(cnt=plan.buf((B,), i32), pa=plan.buf((B, N), i32), pb=plan.buf((B, N), i32), slot=plan.buf((B, N), i32))
+    plan.add("krrn_pair_compact_i32", ptr(nn1), ptr(nn2), B, N, N1, N2, ptr(pr["cnt"]), ptr(pr["pa"]), ptr(pr["pb"]),
+             ptr(pr["slot"]))
+    return pr
+
+
 def build_tbase_plan(tb: TBase, plan: Plan, B: int, N: int, feat: torch.Tensor, cls_key: str, cloud_key: str,
-                     inc_r: int, num_cls: int, levels=None, pre: Optional[dict] = None, pre_sid: int = 0):
+                     inc_r: int, num_cls: int, levels=None, pre: Optional[dict] = None, pre_sid: int = 0,
+                     pairs: Optional[dict] = None):
     """Emit TBase + pred_t. `feat` is [B, N, inc_r]; cls ([B, 1] int64) and cloud ([B, N, 3])
     are late-bound env tensors. Returns the [B, 3] pred_t buffer.
 
@@ -123,7 +144,15 @@ def build_tbase_plan(tb: TBase, plan: Plan, B: int, N: int, feat: torch.Tensor, 
     P1 = feat1[:N1] W1[:, 512:896]^T + feat2 W1[:, 896:1280]^T (N1 rows; the reference indexes
     feat_1 with nearest_pool_1, so only its first N1 rows are ever read), then one gather-add
     launch applies BN + one-hot column + ReLU per point. 29 instead of 168 GFLOP at config 2.
-    `pre`: P1 already emitted by emit_tbase_level1 on stream `pre_sid` (joined here before use)."""
+    `pre`: P1 already emitted by emit_tbase_level1 on stream `pre_sid` (joined here before use).
+
+    With KRRN_TBASE_DISTINCT (and `levels`, TBASE_GATHER) conv2 / conv3 run on each crop's distinct
+    (nn1, nn2) pairs only (emit_pair_compact; `pairs` = its buffers when the fusion emitted it
+    already, on a stream joined before this): h2 and h3 keep their [B*N, 256] shape, but rows
+    j < cnt[b] of crop b hold the rows of the crop's distinct pairs in key order (rows past the
+    last live 128-row tile are never written), and the tail reads point i's row at slot[b, i].
+    Every row is the per-point path's row bit for bit, and so is pred_t. The ops' meta keeps the
+    per-point FLOP count (the algorithmic work)."""
     dev = plan.device
     # one-hot columns, pre-multiplied by the folded BN scale: colv[c] = scale * W1[:, inc_r + c]
     w1, spec1, colv = _conv1_fold(tb, inc_r, num_cls, dev)
@@ -133,6 +162,10 @@ def build_tbase_plan(tb: TBase, plan: Plan, B: int, N: int, feat: torch.Tensor, 
     w4 = tb.conv4.weight.detach()[:3, :, 0].float().contiguous().to(dev)
     b4 = tb.conv4.bias.detach()[:3].float().contiguous().to(dev)
     gathered = levels is not None and TBASE_GATHER
+    if gathered and pairs is None:  # straight after nn1 / nn2 (the fusion joined their stream)
+        pairs = emit_pair_compact(plan, B, N, levels["N1"], levels["N2"], levels["nn1"], levels["nn2"])
+    if not gathered:
+        pairs = None
     h1 = None if gathered else plan.buf((B * N, 1024))
     h2 = plan.buf((B * N, 256))
     h3 = plan.buf((B * N, 256))
@@ -179,18 +212,33 @@ def build_tbase_plan(tb: TBase, plan: Plan, B: int, N: int, feat: torch.Tensor, 
             w2 = tb.conv2.weight.detach()[:, :, 0].to(dev).float() * spec2.scale[:256].reshape(256, 1)
             w3 = ops.gemm_weights_x3(w2.contiguous())
             keep += [w3]
-            plan.add("krrn_gemm_x3_gather_f32", ptr(levels["nn1"]), ptr(P1), N1 * np1, np1, ptr(levels["nn2"]),
-                     ptr(P2), N2 * np1, np1, N, B, 1024, 256, ptr(w3), ptr(spec2.bias), ptr(h2), 256, 1,
-                     meta=dict(kernel="gemm_x3", flops=2.0 * 1024 * 256 * M, tag="tbase_gemm", M=M, N=256, K=1024,
-                               splits=1, mfma_flops=2.0 * M * 256 * 1024 * 6 / 16,
-                               mfma_bf16_flops=2.0 * M * 256 * 1024 * 6))
+            meta = dict(kernel="gemm_x3", flops=2.0 * 1024 * 256 * M, tag="tbase_gemm", M=M, N=256, K=1024,
+                        splits=1, mfma_flops=2.0 * M * 256 * 1024 * 6 / 16, mfma_bf16_flops=2.0 * M * 256 * 1024 * 6)
+            if pairs is not None:
+                plan.add("krrn_gemm_x3_gather_live_f32", ptr(pairs["pa"]), ptr(P1), N1 * np1, np1, ptr(pairs["pb"]),
+                         ptr(P2), N2 * np1, np1, N, B, 1024, 256, ptr(w3), ptr(spec2.bias), ptr(h2), 256, 1,
+                         ptr(pairs["cnt"]), meta=meta)
+            else:
+                plan.add("krrn_gemm_x3_gather_f32", ptr(levels["nn1"]), ptr(P1), N1 * np1, np1, ptr(levels["nn2"]),
+                         ptr(P2), N2 * np1, np1, N, B, 1024, 256, ptr(w3), ptr(spec2.bias), ptr(h2), 256, 1,
+                         meta=meta)
         else:
             plan.add("krrn_gather2_add_f32", ptr(levels["nn2"]), ptr(P2), N2 * np1, np1, ptr(levels["nn1"]),
                      ptr(P1), N1 * np1, np1, N, np1, ptr(spec1.scale), ptr(spec1.bias), ptr(b2), 1, ptr(h1),
                      N * 1024, 1024, B)
     if not gathered:
         gemm(h1, 1024, spec2, h2)
-    gemm(h2, 256, spec3, h3)
-    plan.add("krrn_tbase_tail_f32", ptr(h3), B, N, 256, ptr(w4), ptr(b4), Late(cloud_key), ptr(pred_t), ptr(None))
+    if pairs is not None:
+        # conv3 on the live rows of every crop (one group of N rows per crop), the tail by slot
+        if not add_gemm(plan, a=h2, a_off=0, lda=256, M=N, wt=spec3.wt[0], K=spec3.cin_p, N=ops.pad4(spec3.cout),
+                        scale=spec3.scale, bias=spec3.bias, out=h3, ldo=256, relu=True, batch=B, a_grp=N * 256,
+                        o_grp=N * 256, cin=spec3.cin, cout=spec3.cout, tag="tbase_gemm", require_x3=True,
+                        live=pairs["cnt"]):
+            raise RuntimeError("TBase on distinct rows needs the split-bf16 GEMM (KRRN_GEMM_X3=1)")
+        plan.add("krrn_tbase_tail_slot_f32", ptr(h3), ptr(pairs["slot"]), B, N, 256, ptr(w4), ptr(b4),
+                 Late(cloud_key), ptr(pred_t), ptr(None))
+    else:
+        gemm(h2, 256, spec3, h3)
+        plan.add("krrn_tbase_tail_f32", ptr(h3), B, N, 256, ptr(w4), ptr(b4), Late(cloud_key), ptr(pred_t), ptr(None))
     plan.buffers.append(keep)
-    return pred_t, dict(h1=h1, h2=h2, h3=h3)
+    return pred_t, dict(h1=h1, h2=h2, h3=h3, **(pairs or {}))

@@ -493,13 +493,15 @@ def add_gemm(plan: Plan, *, a: torch.Tensor, a_off: int, lda: int, M: int, wt: t
              scale: Optional[torch.Tensor], bias: Optional[torch.Tensor], out: torch.Tensor, ldo: int, relu: bool,
              res: Optional[torch.Tensor] = None, ldr: int = 0, batch: int = 1, a_grp: int = 0, o_grp: int = 0,
              r_grp: int = 0, cin: Optional[int] = None, cout: Optional[int] = None, tag: str = "gemm",
-             require_x3: bool = False, blas_ok: bool = True) -> bool:
+             require_x3: bool = False, blas_ok: bool = True, live: Optional[torch.Tensor] = None) -> bool:
     """Append a plain GEMM out[m, n] = act(scale[n] * (A[m] . wt[n]) + bias[n] (+ res[m, n])) on hipBLASLt
     (krrn_blas_gemm_*; scale folded into the weights). Returns False when hipBLASLt is disabled
     (KRRN_BLAS=0) or rejects the problem: the caller then emits its own kernel. Short-K GEMMs go to
     the A-stationary split-bf16 kernel and K >= 256 ones to gemm_x3 first (own kernels).
     require_x3: only gemm_x3 will do (its ldr = 0 per-group row broadcast); False if ineligible.
     blas_ok=False: own kernels only (False instead of a hipBLASLt plan).
+    live (int32 [batch], with require_x3): only the first live[g] rows of group g are in use; 128-row
+    tiles past them are skipped (krrn_gemm_x3_live_f32). The FLOP count stays the full M * batch rows'.
     A K = 128 GEMM with a residual is not taken by the panel kernel (its 128-VGPR activation chain
     leaves no room for the residual tile; krrn_gemm_panel_x3_f32 returns KRRN_EUNSUPPORTED), nor is
     one wider than the kernel's 2048-column bias stage (KRRN_ESHAPE)."""
@@ -520,6 +522,8 @@ def add_gemm(plan: Plan, *, a: torch.Tensor, a_off: int, lda: int, M: int, wt: t
         plan.buffers.append([plan._packed[key], wt, scale, bias])
         return plan._packed[key]
     flops = 2.0 * (cin or K) * (cout or N) * M * batch
+    if live is not None and not require_x3:
+        raise ValueError("a live-row GEMM runs on gemm_x3 only (require_x3=True)")
     if GEMM_PANEL and not require_x3 and K in (64, 128) and N % 32 == 0 and N <= 2048 and batch == 1 \
             and lda % 4 == 0 and a_off % 4 == 0 and not (K == 128 and res is not None):
         wp = packed("panel", ops.gemm_weights_panel)
@@ -547,8 +551,9 @@ def add_gemm(plan: Plan, *, a: torch.Tensor, a_off: int, lda: int, M: int, wt: t
             and (res is None or ldr % 4 == 0):
         # own split-bf16 GEMM (gemm_x3.hip): 6 bf16 term products per f32 product
         w3 = packed("x3", ops.gemm_weights_x3)
-        plan.add("krrn_gemm_x3_f32", P(a.data_ptr() + 4 * a_off), lda, M, K, N, ptr(w3), ptr(bias), ptr(res), ldr,
-                 ptr(out), ldo, int(relu), batch, a_grp, o_grp, r_grp,
+        tail = () if live is None else (ptr(live),)
+        plan.add("krrn_gemm_x3_f32" if live is None else "krrn_gemm_x3_live_f32", P(a.data_ptr() + 4 * a_off), lda, M,
+                 K, N, ptr(w3), ptr(bias), ptr(res), ldr, ptr(out), ldo, int(relu), batch, a_grp, o_grp, r_grp, *tail,
                  meta=dict(kernel="gemm_x3", flops=flops, tag=tag, M=M * batch, N=N, K=K, splits=1,
                            mfma_flops=2.0 * M * batch * N * K * 6 / 16, mfma_bf16_flops=2.0 * M * batch * N * K * 6))
         return True
