@@ -257,11 +257,20 @@ int krrn_conv3x3_wino_x3_head_f32(const float* in, int in_cs, int in_co, int B, 
  * out (Ho x Wo = the conv's output size) = act(scale[n] * conv + bias[n] (+ res)) for n < n_store.
  * A block stages the input rows of its 64 / ks output pixels (all channels) in LDS once;
  * 16x16x4 f32 MFMAs; nw = 16-channel output tiles per wave (1..3), ks = waves splitting the
- * reduction of one tile (1, 2, 4; partials summed in LDS in order). */
+ * reduction of one tile (1, 2, 4; partials summed in LDS in order). A last tile of one channel
+ * quad (N % 16 in 1..4) runs on the 4x4x1 f32 MFMA where a wave's share of the reduction is at least
+ * 8 16-wide K steps (ceil(ceil(ksize^2 * cin / 16) / ks) >= 8); its channels are then four
+ * per-k-quad fma chains added as (g0 + g1) + (g2 + g3), still f32, deterministic and independent of
+ * the batch. Shorter reductions and remainders of 2 or 3 quads run as a padded 16-channel tile. */
 int krrn_conv_small_f32(const float* in, int in_cs, int in_co, int B, int H, int W, int cin, const float* wt, int N,
                         int n_store, const float* scale, const float* bias, const float* res, int res_cs, int res_co,
                         float* out, int out_cs, int out_co, int relu, int ksize, int stride, int nw, int ks,
                         void* stream);
+
+/* Test-only: one v_mfma_f32_4x4x1_16b_f32 on one wave, to pin the lane layout krrn_conv_small_f32's
+ * ragged channel tail relies on. a, b: 64 floats (lane l's first / second operand), c: 64 x 4 floats
+ * (lane l's accumulator registers 0..3), d: 64 x 4 floats out, the same layout. c, d 16-byte aligned. */
+int krrn_mfma4x4_probe_f32(const float* a, const float* b, const float* c, float* d, void* stream);
 
 
 /* k nearest neighbours without the [n, n] distance matrix.

@@ -19,7 +19,10 @@
 // k = 4g + s over the 4 lane groups) and the matching weight quad of output channel n = l % 16
 // straight from global memory (the weights are read by every block: L2-resident). The weights are
 // the MFMA's first operand, so each lane ends with 4 consecutive channels of one pixel: the
-// epilogue (BN, residual, ReLU) is one float4 load / store per lane and channel tile.
+// epilogue (BN, residual, ReLU) is one float4 load / store per lane and channel tile. The W18 widths
+// are 20 / 36 / 72 / 144 after padding to quads: a last tile of 4 channels runs on the 16-block
+// v_mfma_f32_4x4x1_16b_f32 instead of a 16x16x4 tile with 12 padding rows, and a tile slot wholly
+// past N (the 6th of 72 channels at NW = 3) is skipped (small_body).
 //
 // Numerics: f32 operands, f32 accumulation (v_mfma_f32_16x16x4_f32 is an fma chain); the k order
 // differs from the implicit-GEMM kernel's, so results agree with it to f32 rounding.
@@ -55,8 +58,23 @@ constexpr unsigned kOOB = 0xFFFFFFF0u;
 // is k-quad 4 st + g, i.e. tap (4 st + g) / q, channels 4 ((4 st + g) % q) .. +3, so a step can
 // straddle two taps and no channel padding is computed). With KS > 1 the K-slices' partial tiles
 // are summed through LDS in slice order (deterministic).
-template <int NW, int KS>
+//
+// Of its NW tile slots a block computes NF full 16-channel tiles and, where T = 1, a tail of one
+// channel quad (N % 16 = 4, where the host takes it: small_launch); the slots after them lie past N and
+// issue no loads, MFMAs or stores. The tail runs on v_mfma_f32_4x4x1_16b_f32 (sixteen independent
+// 4x4x1 products, a quarter of a 16x16x4's passes), so a quad costs 4 / 16 of a tile's MFMA time
+// instead of all of it: block l / 4 of the MFMA is (pixel quad
+// (l / 4) % 4, k-quad g), its column l % 4 the lane's own pixel (the same av register the full tiles
+// use), its rows the quad's 4 channels (lane l supplies the weight of the quad's channel l % 4). Lane l
+// ends with the quad's 4 channels of pixel l % 16 summed over k-quad g only; the four g partials are
+// added across lanes l, l ^ 16, l ^ 32, l ^ 48 as (g0 + g1) + (g2 + g3) once after the K loop, and
+// lane group 0 keeps it (the others zero): from there the tail is one more accumulator tile in the
+// full tiles' layout (K-slice reduction and epilogue unchanged).
+template <int NW, int KS, int NF, int T>
 __device__ __forceinline__ void small_body(const SmallArgs& a, int bx, int by, float* slab) {
+  static_assert(NF >= 0 && (T == 0 || T == 1) && NF + T >= 1 && NF + T <= NW, "tile slots");
+  constexpr int NA = NF + T;             // accumulator tiles after the K loop
+  constexpr int NFa = NF > 0 ? NF : 1;   // array extent (no zero-length arrays)
   constexpr int PM = 4 / KS;
   constexpr int kPixB = 16 * PM;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -133,28 +151,39 @@ __device__ __forceinline__ void small_body(const SmallArgs& a, int bx, int by, f
   const int KQ = taps * Q;  // k-quads
   const __amdgpu_buffer_rsrc_t rsW = __builtin_amdgcn_make_buffer_rsrc(
       (void*)a.wt, (short)0, (int)min((long long)a.N * K * 4, (long long)kOOB), 0x00020000);
-  unsigned wrow[NW];
+  unsigned wrow[NFa], trow = kOOB;
 #pragma unroll
-  for (int j = 0; j < NW; ++j) {
+  for (int j = 0; j < NF; ++j) {
     const int n = n0 + 16 * j + fr;
     wrow[j] = n < a.N ? (unsigned)n * (unsigned)K * 4u : kOOB;
   }
-  f32x4 acc[NW];
+  if constexpr (T) {  // the tail quad: this lane's MFMA row is its channel l % 4
+    const int n = n0 + 16 * NF + (lane & 3);
+    trow = n < a.N ? (unsigned)n * (unsigned)K * 4u : kOOB;
+  }
+  f32x4 acc[NFa], tacc = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-  for (int j = 0; j < NW; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int j = 0; j < NF; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
   __syncthreads();
 
   // ---- K loop over this wave's slice of the 16-wide steps --------------------------------------
   const int nsteps = (KQ + 3) / 4;
   const int per = (nsteps + KS - 1) / KS;
   const int s0 = ks * per, s1 = min(nsteps, s0 + per);
-  auto wload = [&](int st, f32x4 (&w)[NW]) {
+  struct Wts {
+    f32x4 f[NFa], t;  // full tiles' rows, the tail quad's row
+  };
+  auto wload = [&](int st, Wts& w) {
     const int kq = 4 * st + g;
     const bool ok = st < s1 && kq < KQ;
 #pragma unroll
-    for (int j = 0; j < NW; ++j) {
+    for (int j = 0; j < NF; ++j) {
       const unsigned off = (ok && wrow[j] != kOOB) ? wrow[j] + (unsigned)kq * 16u : kOOB;
-      w[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsW, off, 0, 0));
+      w.f[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsW, off, 0, 0));
+    }
+    if constexpr (T) {
+      const unsigned off = (ok && trow != kOOB) ? trow + (unsigned)kq * 16u : kOOB;
+      w.t = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsW, off, 0, 0));
     }
   };
   // this lane's (tap, channel quad) at step s0, advanced by 4 quads per step
@@ -165,7 +194,7 @@ __device__ __forceinline__ void small_body(const SmallArgs& a, int bx, int by, f
 #endif
   // weights KRRN_SMALL_PF steps ahead in a register ring (slot u of every PF-step group)
   constexpr int PF = KRRN_SMALL_PF;
-  f32x4 wr[PF][NW];
+  Wts wr[PF];
 #pragma unroll
   for (int u = 0; u < PF; ++u) wload(s0 + u, wr[u]);
 #if KRRN_SMALL_EXP == 1  // timing experiment: no K loop (staging + epilogue only)
@@ -176,9 +205,7 @@ __device__ __forceinline__ void small_body(const SmallArgs& a, int bx, int by, f
     for (int u = 0; u < PF; ++u) {
       const int st = st0 + u;
       if (st >= s1) break;
-      f32x4 w[NW];
-#pragma unroll
-      for (int j = 0; j < NW; ++j) w[j] = wr[u][j];
+      const Wts w = wr[u];
       wload(st + PF, wr[u]);
       const int t3 = tap + tb;
       const int ty = t3 >= 6 ? 1 : (t3 >= 3 ? 0 : -1);
@@ -188,17 +215,27 @@ __device__ __forceinline__ void small_body(const SmallArgs& a, int bx, int by, f
       f32x4 av = *reinterpret_cast<const f32x4*>(slab + 4 * (px * a.pitch + c4));
       if (!kok) av = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-      for (int s2 = 0; s2 < 4; ++s2)
+      for (int s2 = 0; s2 < 4; ++s2) {
 #pragma unroll
-        for (int j = 0; j < NW; ++j) {
+        for (int j = 0; j < NF; ++j) {
 #if KRRN_SMALL_EXP == 3  // timing experiment: no MFMAs (operands still loaded)
-          acc[j][s2] += av[s2] * w[j][s2];
+          acc[j][s2] += av[s2] * w.f[j][s2];
 #else
           // weights as the first operand (rows = output channels), pixels as the second: lane l's
           // accumulator is channels 4 (l / 16) .. +3 of pixel l % 16 (one float4 in the epilogue)
-          acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[j][s2], av[s2], acc[j], 0, 0, 0);
+          acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(w.f[j][s2], av[s2], acc[j], 0, 0, 0);
 #endif
         }
+        if constexpr (T) {
+#if KRRN_SMALL_EXP == 3
+          tacc[s2] += av[s2] * w.t[s2];
+#else
+          // block l / 4: rows = the quad's channels (lane 4 b + i holds row i), column l % 4 = this
+          // lane's pixel; element i of the result is channel i of that pixel, k-quad g only
+          tacc = __builtin_amdgcn_mfma_f32_4x4x1f32(w.t[s2], av[s2], tacc, 0, 0, 0);
+#endif
+        }
+      }
       c4 += 4;
       if (c4 >= Q) {  // Q >= 4: at most one wrap per step... Q in [1, 4) wraps more
         c4 -= Q;
@@ -211,33 +248,49 @@ __device__ __forceinline__ void small_body(const SmallArgs& a, int bx, int by, f
     }
   }
 
+  // ---- tail: sum the four k-quad partials across lanes, lane group 0 keeps the quad -------------
+  f32x4 accs[NA];
+#pragma unroll
+  for (int j = 0; j < NF; ++j) accs[j] = acc[j];
+  if constexpr (T) {
+    f32x4 v = tacc;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      float x = v[i];
+      x += __shfl_xor(x, 16);  // g0 + g1 | g2 + g3
+      x += __shfl_xor(x, 32);  // (g0 + g1) + (g2 + g3)
+      v[i] = x;
+    }
+    accs[NF] = g == 0 ? v : f32x4{0.f, 0.f, 0.f, 0.f};
+  }
+
   // ---- K-slice reduction through LDS (slice order: deterministic) ------------------------------
   if constexpr (KS > 1) {
     __syncthreads();  // every wave is done reading the slab
     float* part = slab;
 #pragma unroll
-    for (int j = 0; j < NW; ++j)
-      *reinterpret_cast<f32x4*>(part + ((wave * NW + j) * 64 + lane) * 4) = acc[j];
+    for (int j = 0; j < NA; ++j)
+      *reinterpret_cast<f32x4*>(part + ((wave * NW + j) * 64 + lane) * 4) = accs[j];
     __syncthreads();
     if (ks != 0) return;
 #pragma unroll
-    for (int j = 0; j < NW; ++j) {
+    for (int j = 0; j < NA; ++j) {
       f32x4 v = *reinterpret_cast<const f32x4*>(part + ((wave * NW + j) * 64 + lane) * 4);
       for (int q2 = 1; q2 < KS; ++q2) v += *reinterpret_cast<const f32x4*>(part + (((wave + q2) * NW + j) * 64 + lane) * 4);
-      acc[j] = v;
+      accs[j] = v;
     }
   }
 
-  // ---- epilogue: acc[j][i] = (channel n0 + 16j + 4g + i, pixel 16 mi + fr): float4 per lane ------
+  // ---- epilogue: accs[j][i] = (channel n0 + 16j + 4g + i, pixel 16 mi + fr): float4 per lane ------
   const int mo = p0 + 16 * mi + fr;
   if (mo >= a.M) return;
 #pragma unroll
-  for (int j = 0; j < NW; ++j) {
+  for (int j = 0; j < NA; ++j) {
     const int n = n0 + 16 * j + 4 * g;
     if (n >= a.n_store) continue;  // n_store is a multiple of 4
     const f32x4 sc = a.scale ? *reinterpret_cast<const f32x4*>(a.scale + n) : f32x4{1.f, 1.f, 1.f, 1.f};
     const f32x4 bi = a.bias ? *reinterpret_cast<const f32x4*>(a.bias + n) : f32x4{0.f, 0.f, 0.f, 0.f};
-    f32x4 v = acc[j] * sc + bi;
+    f32x4 v = accs[j] * sc + bi;
     if (a.res) v += *reinterpret_cast<const f32x4*>(a.res + (size_t)mo * a.res_cs + a.res_co + n);
     if (a.relu) {
 #pragma unroll
@@ -247,10 +300,19 @@ __device__ __forceinline__ void small_body(const SmallArgs& a, int bx, int by, f
   }
 }
 
-template <int NW, int KS>
+// Every y-block but the last holds NW full tiles; the last one holds NF full tiles and T (0 or 1) tail quads
+// (both fixed at compile time, chosen by the host from N: the K loop carries no per-step branch).
+template <int NW, int KS, int NF, int T>
 __global__ __launch_bounds__(256) void conv_small_kernel(const SmallArgs a) {
   extern __shared__ __attribute__((aligned(16))) float slab[];
-  small_body<NW, KS>(a, blockIdx.x, blockIdx.y, slab);
+  if constexpr (NF == NW && T == 0) {
+    small_body<NW, KS, NW, 0>(a, blockIdx.x, blockIdx.y, slab);
+  } else {
+    if (blockIdx.y + 1 < gridDim.y)
+      small_body<NW, KS, NW, 0>(a, blockIdx.x, blockIdx.y, slab);
+    else
+      small_body<NW, KS, NF, T>(a, blockIdx.x, blockIdx.y, slab);
+  }
 }
 
 // LDS floats of the largest slab any block of this problem stages (host mirror of the kernel's
@@ -288,15 +350,50 @@ int set_lds(const void* fn, long long lds) {
   return KRRN_OK;
 }
 
-template <int NW, int KS>
-int small_launch(const SmallArgs& a, hipStream_t s) {
+// Only a remainder of one quad is a tail. A quad needs its own b128 weight load per step, as a full
+// tile does: one quad for a tile trades 128 MFMA cycles per step for 32 at the same loads; two quads
+// add a load and measured slower than the padded tile on every shape, so a
+// remainder of 2 or 3 quads runs as a padded full tile.
+// The tail's cross-lane sum is a fixed cost per wave, so it is taken only where a wave's reduction is
+// long enough to pay for it (measured: a loss at 2-3 K steps per wave, the 1x1 projections; even at 6;
+// a gain at 11-12, the branch convs). Shorter reductions run the remainder as a padded full tile.
+// ops.small_conv_rows (the plan's mfma_flops) restates this rule with the same 8: a library built with
+// another value mis-states that figure unless SMALL_TAIL_STEPS in ops.py moves with it.
+#ifndef KRRN_SMALL_TAIL_STEPS
+#define KRRN_SMALL_TAIL_STEPS 8
+#endif
+
+template <int NW, int KS, int NF, int T>
+int small_launch_tail(const SmallArgs& a, hipStream_t s) {
   constexpr int pixb = 64 / KS;
   const long long lds = small_lds(a, NW, KS);
-  const int st = set_lds((const void*)conv_small_kernel<NW, KS>, lds);
+  const int st = set_lds((const void*)conv_small_kernel<NW, KS, NF, T>, lds);
   if (st != KRRN_OK) return st;
   const dim3 grid(krrn_cdiv(a.M, pixb), krrn_cdiv(krrn_cdiv(a.N, 16), NW));
-  hipLaunchKernelGGL((conv_small_kernel<NW, KS>), grid, dim3(256), (size_t)lds, s, a);
+  hipLaunchKernelGGL((conv_small_kernel<NW, KS, NF, T>), grid, dim3(256), (size_t)lds, s, a);
   return krrn_launch_status();
+}
+
+// The last y-block's tile slots: a remainder N % 16 of one quad is the tail after the full tiles, if a
+// wave runs at least KRRN_SMALL_TAIL_STEPS K steps; otherwise the remainder is one more (padded) full tile.
+template <int NW, int KS>
+int small_launch(const SmallArgs& a, hipStream_t s) {
+  const int ntiles = krrn_cdiv(a.N, 16);
+  const int slots = ntiles - (krrn_cdiv(ntiles, NW) - 1) * NW;  // 1 .. NW tiles in the last y-block
+  const int tq = krrn_cdiv(a.N % 16, 4);
+  const int per = krrn_cdiv(krrn_cdiv(a.ksz * a.ksz * a.q, 4), KS);  // K steps per wave
+  const int t = (tq == 1 && per >= KRRN_SMALL_TAIL_STEPS) ? 1 : 0;
+  const int nf = t ? slots - 1 : slots;
+#define KRRN_SMALL_T(NFV, TV)                                    \
+  if constexpr (NFV + TV <= NW) {                                \
+    if (nf == NFV && t == TV) return small_launch_tail<NW, KS, NFV, TV>(a, s); \
+  }
+  KRRN_SMALL_T(0, 1)
+  KRRN_SMALL_T(1, 0) KRRN_SMALL_T(1, 1)
+  KRRN_SMALL_T(2, 0) KRRN_SMALL_T(2, 1)
+  KRRN_SMALL_T(3, 0)
+#undef KRRN_SMALL_T
+  return KRRN_EARG;
 }
 
 int make_args(const float* in, int in_cs, int in_co, int B, int H, int W, int cin, const float* wt, int N,

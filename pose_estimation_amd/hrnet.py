@@ -321,13 +321,14 @@ class _Builder:
         taps = spec.ksize * spec.ksize
         ntiles = (np_ + 15) // 16
         nw, ks = ops.small_conv_config(M, ntiles, spec.cin_p)
+        ksteps = (taps * spec.cin_p // 4 + 3) // 4  # 16-wide K steps, 4 MFMAs deep per tile
         return dict(x=ptr(x.t), in_cs=x.cs, in_co=x.co, B=x.B, H=x.H, W=x.W, cin=spec.cin_p, wt=ptr(spec.wt[0]),
                     N=np_, n_store=np_, scale=ptr(spec.scale), bias=ptr(spec.bias),
                     res=ptr(res.t) if res is not None else ptr(None), res_cs=res.cs if res is not None else 0,
                     res_co=res.co if res is not None else 0, out=ptr(out.t), out_cs=out.cs, out_co=out.co,
                     relu=int(relu), ksize=spec.ksize, stride=spec.stride, nw=nw, ks=ks, M=M,
                     flops=2.0 * spec.cin * spec.cout * taps * M,
-                    mfma_flops=2.0 * 16 * ((taps * spec.cin_p // 4 + 3) // 4) * 16 * ntiles * M)
+                    mfma_flops=2.0 * 16 * ksteps * ops.small_conv_rows(np_, ksteps, ks) * M)
 
     def emit_small(self, x: Act, spec, out: Act, res: Optional[Act], relu: bool, tag: str = "conv"):
         p = self.small_problem(x, spec, out, res, relu)

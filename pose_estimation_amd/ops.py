@@ -406,6 +406,20 @@ def small_conv_config(M: int, ntiles: int, cin_p: int):
     return nw, ks
 
 
+# krrn_conv_small_f32's KRRN_SMALL_TAIL_STEPS (conv_small.hip): the two move together
+SMALL_TAIL_STEPS = 8
+
+
+def small_conv_rows(np_: int, ksteps: int, ks: int) -> int:
+    """Output-channel rows krrn_conv_small_f32 issues MFMAs for (its host dispatch restated): 16 per full
+    16-channel tile, 4 for a last tile of one quad (N % 16 = 4, on the 4x4x1 MFMA) when a wave runs at
+    least SMALL_TAIL_STEPS = 8 of the ksteps 16-wide K steps (ks waves share them); a shorter reduction, or a remainder of
+    2 or 3 quads, runs as a padded full tile. Tile slots wholly past N issue nothing."""
+    full, tq = np_ // 16, (np_ % 16 + 3) // 4
+    tail = tq == 1 and (ksteps + ks - 1) // ks >= SMALL_TAIL_STEPS
+    return 16 * full + (4 if tail else 16 * (tq > 0))
+
+
 def small_conv_eligible(spec: ConvSpec, x) -> bool:
     """krrn_conv_small_f32: narrow convs whose 64-pixel blocks' input rows fit the LDS (up to 256
     physical input channels): every 3x3 / stride-1 / pad-1 conv (the HRNet branches' BasicBlocks),
