@@ -32,7 +32,7 @@ extern "C" {
 #define KRRN_EARG (-1)
 #define KRRN_ESHAPE (-2)
 #define KRRN_EALIGN (-3)
-#define KRRN_EUNSUPPORTED (-4) /* hipBLASLt rejected the problem, or a form the kernel does not offer */
+#define KRRN_EUNSUPPORTED (-4) /* valid arguments, but a form the kernel does not offer */
 
 /* Implicit-GEMM convolution / GEMM on the f32 matrix cores, BN folded into scale/bias.
  * Replaces nn.Conv2d + BatchNorm2d (+ residual add) (+ ReLU) of BasicBlock / Bottleneck /
@@ -119,26 +119,12 @@ int krrn_convT_s2_x3_f32(const float* in, int in_cs, int in_co, int B, int Hi, i
                          const void* U3, int N, const float* scale, const float* bias, int relu, float* out,
                          int out_cs, int out_co, int Ho, int Wo, void* stream);
 
-/* Plain f32 GEMM on hipBLASLt (library-shaped GEMMs of the fusion / TBase, see blas.hip):
- *   out[m*ldo + n] = act(sum_k A[m*lda + k] W[n*K + k] + bias[n] + res[m*ldr + n]),  0 <= n < N
- * in `batch` strided groups of M rows (A / out / res advance a_grp / o_grp / r_grp floats per
- * group, W [N][K] shared). create: heuristic query once, the plan is caller-owned (destroy frees
- * it); *ws_bytes = the workspace run() needs (<= max_ws). run: one hipblasLtMatmul on `stream`
- * (graph-capturable); bias / res must be given iff the plan was created with them.
- * KRRN_EUNSUPPORTED when hipBLASLt has no algorithm or fails. */
-typedef struct krrn_blas_gemm krrn_blas_gemm;
-int krrn_blas_gemm_create(int M, int N, int K, int lda, int ldo, int batch, long long a_grp, long long o_grp,
-                          int has_bias, int relu, int has_res, int ldr, long long r_grp, long long max_ws,
-                          krrn_blas_gemm** out_plan, long long* ws_bytes);
-int krrn_blas_gemm_run(const krrn_blas_gemm* g, const float* a, const float* w, const float* bias, const float* res,
-                       float* out, void* workspace, long long ws_bytes, void* stream);
-int krrn_blas_gemm_destroy(krrn_blas_gemm* g);
-
-/* The same GEMM on the bf16 matrix cores at f32 accuracy (gemm_x3.hip: split-bf16 operands,
+/* Plain GEMM on the bf16 matrix cores at f32 accuracy (gemm_x3.hip: split-bf16 operands,
  * six term products per f32 product): the GCN `feature_map @ weights` of G6/G7
  * (lib/network/point/gcn3d.py:125-127, 184-186) and TBase's Conv1d chain (posenet.py:51-96).
- *   out[m*ldo + n] = act(sum_k A[m*lda + k] W[n][k] + bias[n] + res[m*ldr + n])
- * in `batch` strided groups of M rows (a_grp / o_grp / r_grp floats per group); ldr = 0 adds one
+ *   out[m*ldo + n] = act(sum_k A[m*lda + k] W[n][k] + bias[n] + res[m*ldr + n]),  0 <= n < N
+ * in `batch` strided groups of M rows (A / out / res advance a_grp / o_grp / r_grp floats per
+ * group, W [N][K] shared); ldr = 0 adds one
  * res row per group (res[g*r_grp + n], a per-crop bias). w3f holds W split
  * into per-wave MFMA fragments (ops.gemm_weights_x3: [N/32][K/8][2][64 lanes][4] u32).
  * K % 32 == 0, N % 128 == 0, lda / ldo / ldr % 4 == 0, 16-byte aligned A / W / out / res. */

@@ -37,7 +37,7 @@ _lib = None
 _ERRORS = {-1: "KRRN_EARG (null pointer / bad argument)",
            -2: "KRRN_ESHAPE (dimension outside the supported range)",
            -3: "KRRN_EALIGN (16-byte alignment / channel stride violation)",
-           -4: "KRRN_EUNSUPPORTED (hipBLASLt rejected the problem)"}
+           -4: "KRRN_EUNSUPPORTED (a form the kernel does not offer)"}
 
 # include/krrn_hip.h is the ABI, and the ctypes signatures are read from it: every declaration there is
 # `int krrn_name(type name, ...);` with a pointer or one of these scalar types per parameter

@@ -91,11 +91,6 @@ class FusionNetLite(nn.Module):
 FEAT_SID = 4  # plan stream of the materialised output concat (joined by the caller)
 # crops per chunk of the level-0 GEMM + gather-conv (0: the whole batch in one launch each)
 FUSION_CHUNK = knobs.integer("KRRN_FUSION_CHUNK")
-# the launches that read only p9 and the perms (pool kNNs, sampled vertices, idx1, idx2, nn1, nn2) on
-# their own plan stream GEOM_SID from the level-0 kNN on, instead of where their consumers are (a
-# kept alternative, off by default: the same bits, measured 0.6 % slower per step)
-GEOM_EARLY = knobs.flag("KRRN_GEOM_EARLY")
-GEOM_SID = 8
 
 def level_sizes(N: int, k0: int):
     N1 = int(N / 4)
@@ -208,9 +203,7 @@ def build_fusion_plan(fu: FusionNetLite, plan: Plan, B: int, N: int, p9: torch.T
     leaves the chip underused. materialize=False skips writing the 1280-wide concat (returns None
     for it): its only consumer, TBase conv1, reads the level rows by linearity.
     early: emit_fusion_cloud_part's buffers when that part was emitted already (joined before this).
-    With KRRN_GEOM_EARLY the geometry-only launches run on stream GEOM_SID (forked here, after the
-    level-0 kNN, and joined before this returns). hooks['pairs'] run right after nn2 on its stream (that
-    one, or stream 3), given dict(nn1, nn2). The same launches on the same values either way.
+    hooks['pairs'] run right after the nn2 kNN on its stream (3, where nn1 ran too), given dict(nn1, nn2).
     """
     hooks = hooks or {}
     dev = plan.device
@@ -253,85 +246,29 @@ def build_fusion_plan(fu: FusionNetLite, plan: Plan, B: int, N: int, p9: torch.T
     e = _Emit(fu, plan, B, keep)
     knn, gcn, gemm, off = e.knn, e.gcn, e.gemm, _off
 
-    # the launches that read only geometry (p9 and the perms), stated once for both emission orders
-    def pool_knn(bi, br):  # pools (fusion.py:197-202): kNN(4) at the sampled rows
-        knn(off(p9, 3 * bi), N * 9, 9, N1, ptr(perms[br]), off(p9, 3 * bi), N * 9, 9, N, 3, 4, 1, 0, nb4[br])
-
-    def pool_verts(bi, br):  # ... and the sampled vertices
-        plan.add("krrn_gather_rows_f32", ptr(perms[br]), 0, 0, N1, off(p9, 3 * bi), N * 9, 9, off(V1, 3 * bi),
-                 N1 * 9, 9, 3, B)
-
-    def pool1_verts():
-        plan.add("krrn_gather_rows_f32", ptr(perms["p1"]), 0, 0, N1, off(p9, 0), N * 9, 9, off(PV1, 0), N1 * 9, 9, 9, B)
-
-    def knn_idx1():  # level 1 graph (fusion.py:205)
-        knn(off(V1, 0), N1 * 9, 9, N1, ptr(None), off(V1, 0), N1 * 9, 9, N1, 3, k1, 1, 0, idx1)
-
-    def knn_nn1():  # nearest-index to pool_1 (fusion.py:231) only needs PV1
-        knn(off(p9, 0), N * 9, 9, N, ptr(None), off(PV1, 0), N1 * 9, 9, N1, 3, 1, 0, 1, nn1)
-
-    def pool2_knn():  # pool_2 (fusion.py:219): kNN on pool_1[..., :3] at the sampled rows
-        knn(off(PV1, 0), N1 * 9, 9, N2, ptr(perms["p2"]), off(PV1, 0), N1 * 9, 9, N1, 3, 4, 1, 0, nb4b)
-
-    def pool2_verts():
-        plan.add("krrn_gather_rows_f32", ptr(perms["p2"]), 0, 0, N2, off(PV1, 0), N1 * 9, 9, off(PV2, 0), N2 * 9, 9, 9, B)
-
-    def knn_idx2():  # level 2 graph (fusion.py:223): 9-D kNN
-        knn(off(PV2, 0), N2 * 9, 9, N2, ptr(None), off(PV2, 0), N2 * 9, 9, N2, 9, k2, 1, 0, idx2)
-
-    def knn_nn2():  # nearest-index to pool_2 (fusion.py:232)
-        knn(off(p9, 0), N * 9, 9, N, ptr(None), off(PV2, 0), N2 * 9, 9, N2, 3, 1, 0, 1, nn2)
-
-    # GEOM_EARLY: those launches run on plan stream GEOM_SID from here on, ahead of the feature chain
-    # (emitted in the list just before the point where a consumer waits, so a consumer's sync waits
-    # for what it reads and the launches ahead of it on that stream, not for the whole stream)
-    geom = GEOM_EARLY
-
-    def on_geom(*fns):
-        with plan.on_stream(GEOM_SID):
-            for fn in fns:
-                fn()
-
-    def wait_geom(dst):  # side stream to side stream: a capture edge
-        if dst == 0:
-            plan.sync(GEOM_SID, 0)
-        else:
-            plan.edge(GEOM_SID, dst)
-
     # level 0: idx0 = kNN(cloud, 10) (fusion.py:175); then the v / x / n branches (conv_0,
     # conv_1 + BN + ReLU, pool_1_*) are independent until the concat: branch bi on stream bi
     if not early:
         knn(off(p9, 0), N * 9, 9, N, ptr(None), off(p9, 0), N * 9, 9, N, 3, k0, 1, 0, idx0)
-    if geom:
-        plan.fork([GEOM_SID])
-        on_geom(*[lambda bi=bi, br=br: pool_knn(bi, br) for bi, br in enumerate(("v", "x", "n"))],
-                *[lambda bi=bi, br=br: pool_verts(bi, br) for bi, br in enumerate(("v", "x", "n"))], pool1_verts)
     plan.fork([1, 2])
     for bi, br in enumerate(("v", "x", "n")):
         with plan.on_stream(bi):
             if not (early and bi == 0):
                 _level0_branch(e, fu, bi, br, N, idx0, off(p9, 3 * bi), N * 9, 9, F0, Y1[bi], feat1, cy)
-            if geom:
-                wait_geom(bi)
-            else:
-                pool_knn(bi, br)
+            # pools (fusion.py:197-202): kNN(4) at the sampled rows + max, and the sampled vertices
+            knn(off(p9, 3 * bi), N * 9, 9, N1, ptr(perms[br]), off(p9, 3 * bi), N * 9, 9, N, 3, 4, 1, 0, nb4[br])
             plan.add("krrn_pool_max_f32", ptr(nb4[br]), N1, 4, off(feat1, 128 * bi), N * 384, 384, 128,
                      off(FP1, 128 * bi), N1 * 384, 384, B)
-            if not geom:
-                pool_verts(bi, br)
-    if not geom:
-        pool1_verts()
+            plan.add("krrn_gather_rows_f32", ptr(perms[br]), 0, 0, N1, off(p9, 3 * bi), N * 9, 9, off(V1, 3 * bi),
+                     N1 * 9, 9, 3, B)
+    plan.add("krrn_gather_rows_f32", ptr(perms["p1"]), 0, 0, N1, off(p9, 0), N * 9, 9, off(PV1, 0), N1 * 9, 9, 9, B)
     plan.join([1, 2])
     # level 1 (fusion.py:205-216)
-    if geom:
-        on_geom(knn_idx1)
-        wait_geom(0)
-        plan.fork([1, 2])
-    else:
-        knn_idx1()
-        plan.fork([1, 2, 3])
-        with plan.on_stream(3):
-            knn_nn1()
+    knn(off(V1, 0), N1 * 9, 9, N1, ptr(None), off(V1, 0), N1 * 9, 9, N1, 3, k1, 1, 0, idx1)
+    plan.fork([1, 2, 3])
+    with plan.on_stream(3):
+        # nearest-index to pool_1 (fusion.py:231) only needs PV1
+        knn(off(p9, 0), N * 9, 9, N, ptr(None), off(PV1, 0), N1 * 9, 9, N1, 3, 1, 0, 1, nn1)
     for bi, br in enumerate(("v", "x", "n")):
         with plan.on_stream(bi):
             c2 = getattr(fu, f"conv_2_{br}")
@@ -341,37 +278,27 @@ def build_fusion_plan(fu: FusionNetLite, plan: Plan, B: int, N: int, p9: torch.T
     plan.join([1, 2])
     for h in hooks.get("level1", []):
         h(dict(feat1=feat1, feat2=feat2))
-    if geom:
-        on_geom(pool2_knn, pool2_verts, knn_idx2)
-        wait_geom(0)
-    else:
-        pool2_knn()
+    # pool_2 (fusion.py:219): kNN on pool_1[..., :3] at the sampled rows
+    knn(off(PV1, 0), N1 * 9, 9, N2, ptr(perms["p2"]), off(PV1, 0), N1 * 9, 9, N1, 3, 4, 1, 0, nb4b)
     plan.add("krrn_pool_max_f32", ptr(nb4b), N2, 4, off(feat2, 0), N1 * 384, 384, 384, off(FP2, 0), N2 * 384, 384, B)
-    if not geom:
-        pool2_verts()
-        # level 2 (fusion.py:223-229): 9-D kNN, Conv_fuse_layer x2, no activation
-        knn_idx2()
+    plan.add("krrn_gather_rows_f32", ptr(perms["p2"]), 0, 0, N2, off(PV1, 0), N1 * 9, 9, off(PV2, 0), N2 * 9, 9, 9, B)
+    # level 2 (fusion.py:223-229): 9-D kNN, Conv_fuse_layer x2, no activation
+    knn(off(PV2, 0), N2 * 9, 9, N2, ptr(None), off(PV2, 0), N2 * 9, 9, N2, 9, k2, 1, 0, idx2)
     for h in hooks.get("level2", []):
         h(dict(feat1=feat1, feat2=feat2))
-    pair_hooks = [lambda h=h: h(dict(nn1=nn1, nn2=nn2)) for h in hooks.get("pairs", [])]
-    if geom:
-        on_geom(knn_nn1, knn_nn2, *pair_hooks)
-    else:
-        plan.fork([3])
-        with plan.on_stream(3):
-            knn_nn2()
-            for h in pair_hooks:  # nn1 ran on this stream too
-                h()
+    plan.fork([3])
+    with plan.on_stream(3):
+        # nearest-index to pool_2 (fusion.py:232); nn1 ran on this stream too
+        knn(off(p9, 0), N * 9, 9, N, ptr(None), off(PV2, 0), N2 * 9, 9, N2, 3, 1, 0, 1, nn2)
+        for h in hooks.get("pairs", []):
+            h(dict(nn1=nn1, nn2=nn2))
     gemm(FP2, 384, 0, B * N2, fu.conv_4, Y4)
     gcn(idx2, N2, k2, off(PV2, 0), N2 * 9, 9, _dn(fu.conv_4.directions, dev), 512, Y4, None, False,
         off(fm4, 0), N2 * 512, 512)
     gemm(fm4, 512, 0, B * N2, fu.conv_5, Y5)
     gcn(idx2, N2, k2, off(PV2, 0), N2 * 9, 9, _dn(fu.conv_5.directions, dev), 512, Y5, None, False,
         off(fm5, 0), N2 * 512, 512)
-    if geom:
-        wait_geom(0)
-    else:
-        plan.join([3])
+    plan.join([3])
     # the 1280-wide concat (fusion.py:234-238). TBase consumes it by linearity from the level rows
     # (posenet.build_tbase_plan), so the materialised concat (the module's output, kept for
     # inspection) is written on side stream FEAT_SID, off the critical path; the caller joins it.

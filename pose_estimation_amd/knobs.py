@@ -39,19 +39,14 @@ KNOBS: Dict[str, Tuple[Optional[str], str]] = {
     "KRRN_DECONV_FOLD": ("1", "fold last_layer_2 into the deconv (272 instead of 400 input channels); "
                               "0 = the literal cat + deconv"),
     "KRRN_FUSE_ID_FIRST": ("1", "HRNet fuse sums start from the identity branch; 0 = the reference's j order"),
-    "KRRN_BLAS": ("1", "GEMMs no hand-written kernel takes go to hipBLASLt; 0 = the implicit-GEMM conv"),
-    "KRRN_GEMM_X3": ("1", "GEMMs with K >= 256 on the split-bf16 GEMM"),
-    "KRRN_GEMM_PANEL": ("1", "K = 64 / 128 GEMMs on the A-stationary panel GEMM"),
+    "KRRN_GEMM_X3": ("1", "GEMMs with K >= 256 on the split-bf16 GEMM; 0 = the implicit-GEMM conv (TBase's "
+                          "GEMMs, which need its row-broadcast and live-row forms, raise)"),
+    "KRRN_GEMM_PANEL": ("1", "K = 64 / 128 GEMMs on the A-stationary panel GEMM; 0 = the implicit-GEMM conv"),
     "KRRN_SPLITK": ("1", "split-K for implicit-GEMM convs with few output tiles; 0 = never"),
     "KRRN_TBASE_EARLY": ("1", "TBase conv1's level-1 half runs as soon as level 1 is done (side stream)"),
-    "KRRN_TBASE_GATHER": ("1", "TBase conv1 / conv2 by linearity on the fusion's level rows (gathered "
-                               "GEMM); 0 = on the materialised 1280-wide concat"),
-    "KRRN_TBASE_DISTINCT": ("1", "with KRRN_TBASE_GATHER, TBase conv2 / conv3 run once per distinct (nn1, nn2) "
+    "KRRN_TBASE_DISTINCT": ("1", "TBase conv2 / conv3 run once per distinct (nn1, nn2) "
                                  "pair of a crop and the tail reads each point's row by its slot (same bits); "
                                  "0 = once per point"),
-    "KRRN_GEOM_EARLY": ("0", "1 = the fusion launches that read only p9 and the perms (pool kNNs, vertex gathers, "
-                             "idx1, idx2, nn1, nn2) run on their own plan stream from the level-0 kNN on "
-                             "(same bits; measured 0.6 % slower); 0 = where their consumers are"),
     "KRRN_POSE_AT": ("level1", "where the fused pose step forks off the forward plan: level1 / level2 / heads"),
     "KRRN_FUSION_CHUNK": ("16", "crops per chunk of the level-0 GCN GEMM + gather-conv, through a chunk-sized "
                                 "Y buffer per branch (0 = the whole batch at once; same results)"),

@@ -190,7 +190,7 @@ class KRRNPlan:
             if pose_hook is not None and pose_at != "heads":
                 hooks[pose_at].append(tracked(lambda fb: emit_pose()))
             # TBase conv1's level-0/1 half (P1, 0.3 ms of GEMMs) needs only feat1 / feat2: it runs on
-            # its own stream beside the level-2 GCN chain and joins before the per-point gather-add
+            # its own stream beside the level-2 GCN chain and joins before conv2 gathers its rows
             tb_pre = {}
             tb_sid = self.TBASE_SID if pose_stream else 0
 
@@ -217,8 +217,8 @@ class KRRNPlan:
             fb = self.fusion_bufs
             levels = dict(fm5=fb["fm5"], feat1=fb["feat1"], feat2=fb["feat2"], nn1=fb["nn1"], nn2=fb["nn2"], N1=N1,
                           N2=N2)
-            self.pred_t, self.tbase_bufs = build_tbase_plan(model.pose.t_net, plan, B, N, feat, "cls", "cloud",
-                                                            cfg.Module.POSENet.INC_R, C, levels=levels,
+            self.pred_t, self.tbase_bufs = build_tbase_plan(model.pose.t_net, plan, B, N, "cls", "cloud",
+                                                            cfg.Module.POSENet.INC_R, C, levels,
                                                             pre=tb_pre or None, pre_sid=tb_sid,
                                                             pairs=tb_pairs or None)
             if feat is not None:

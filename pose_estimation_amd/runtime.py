@@ -462,12 +462,9 @@ def add_conv_group(plan: Plan, problems: List[dict], tile: int = None, tag: str 
     plan.add("krrn_conv2d_group_x3_f32" if x3 else "krrn_conv2d_group_f32", ctypes.cast(arr, P), n, tile, meta=meta)
 
 
-BLAS = knobs.flag("KRRN_BLAS")
-BLAS_MAX_WS = 64 << 20
-# plain GEMMs with K >= GEMM_X3_MINK on gemm_x3.hip (split-bf16), the rest on hipBLASLt: measured
-# (profiles/bench_gemm.py, MI355X) 10-18 % faster at K = 256..1024, 10 % slower at K = 128 (the
-# level-0 GCN GEMMs: 198 vs 180 us, output-write-bound) and slower at layer1's K = 64 (all
-# eligible GEMMs on gemm_x3: 1.98 vs 1.77 ms of GEMMs per step)
+# plain GEMMs with K >= GEMM_X3_MINK on gemm_x3.hip (split-bf16); the short-K ones go to the panel kernel
+# below: gemm_x3 measured 10 % slower than a library f32 GEMM at K = 128 (the level-0 GCN GEMMs: 198 vs
+# 180 us, output-write-bound) and slower at layer1's K = 64 (profiles/bench_gemm.py, MI355X)
 GEMM_X3 = knobs.flag("KRRN_GEMM_X3")
 # short-K GEMMs (K = 64 / 128, N % 32 == 0, one row group) on the A-stationary split-bf16 kernel
 # (gemm_panel.hip): the level-0 / level-1 GCN GEMMs, whose 262 MB output makes them write streams
@@ -475,41 +472,22 @@ GEMM_PANEL = knobs.flag("KRRN_GEMM_PANEL")
 GEMM_X3_MINK = 256
 
 
-class _BlasPlan:
-    """Owns one krrn_blas_gemm plan (destroyed with the launch plan that keeps it)."""
-
-    def __init__(self, handle):
-        self.handle = handle
-
-    def __del__(self):
-        try:
-            if self.handle:
-                _lib.lib().krrn_blas_gemm_destroy(self.handle)
-        except Exception:  # interpreter shutdown
-            pass
-
-
 def add_gemm(plan: Plan, *, a: torch.Tensor, a_off: int, lda: int, M: int, wt: torch.Tensor, K: int, N: int,
              scale: Optional[torch.Tensor], bias: Optional[torch.Tensor], out: torch.Tensor, ldo: int, relu: bool,
              res: Optional[torch.Tensor] = None, ldr: int = 0, batch: int = 1, a_grp: int = 0, o_grp: int = 0,
              r_grp: int = 0, cin: Optional[int] = None, cout: Optional[int] = None, tag: str = "gemm",
-             require_x3: bool = False, blas_ok: bool = True, live: Optional[torch.Tensor] = None) -> bool:
-    """Append a plain GEMM out[m, n] = act(scale[n] * (A[m] . wt[n]) + bias[n] (+ res[m, n])) on hipBLASLt
-    (krrn_blas_gemm_*; scale folded into the weights). Returns False when hipBLASLt is disabled
-    (KRRN_BLAS=0) or rejects the problem: the caller then emits its own kernel. Short-K GEMMs go to
-    the A-stationary split-bf16 kernel and K >= 256 ones to gemm_x3 first (own kernels).
+             require_x3: bool = False, live: Optional[torch.Tensor] = None) -> bool:
+    """Append a plain GEMM out[m, n] = act(scale[n] * (A[m] . wt[n]) + bias[n] (+ res[m, n])) on one of the
+    two split-bf16 GEMM kernels (scale folded into the packed weights): the A-stationary panel kernel for
+    short K (64 / 128, one row group), else gemm_x3 for K >= 256. Returns False, with nothing appended,
+    when neither takes the problem (its shape or alignment, or KRRN_GEMM_PANEL / KRRN_GEMM_X3 = 0): the
+    caller then emits the implicit-GEMM conv, or raises where only this form will do.
     require_x3: only gemm_x3 will do (its ldr = 0 per-group row broadcast); False if ineligible.
-    blas_ok=False: own kernels only (False instead of a hipBLASLt plan).
     live (int32 [batch], with require_x3): only the first live[g] rows of group g are in use; 128-row
     tiles past them are skipped (krrn_gemm_x3_live_f32). The FLOP count stays the full M * batch rows'.
     A K = 128 GEMM with a residual is not taken by the panel kernel (its 128-VGPR activation chain
     leaves no room for the residual tile; krrn_gemm_panel_x3_f32 returns KRRN_EUNSUPPORTED), nor is
     one wider than the kernel's 2048-column bias stage (KRRN_ESHAPE)."""
-    dev = plan.device
-    w = wt.reshape(N, -1)[:, :K].float()
-    if scale is not None:
-        w = w * scale.reshape(N, 1).to(w.device)
-    w = w.contiguous()
     wkey = (wt.data_ptr(), scale.data_ptr() if scale is not None else 0, K, N)
 
     def packed(kind: str, fn):
@@ -518,7 +496,10 @@ def add_gemm(plan: Plan, *, a: torch.Tensor, a_off: int, lda: int, M: int, wt: t
         wt's and scale's addresses and the launch reads this call's bias: the plan keeps all three."""
         key = wkey + (kind,)
         if key not in plan._packed:
-            plan._packed[key] = fn(w)
+            w = wt.reshape(N, -1)[:, :K].float()
+            if scale is not None:
+                w = w * scale.reshape(N, 1).to(w.device)
+            plan._packed[key] = fn(w.contiguous())
         plan.buffers.append([plan._packed[key], wt, scale, bias])
         return plan._packed[key]
     flops = 2.0 * (cin or K) * (cout or N) * M * batch
@@ -557,20 +538,4 @@ def add_gemm(plan: Plan, *, a: torch.Tensor, a_off: int, lda: int, M: int, wt: t
                  meta=dict(kernel="gemm_x3", flops=flops, tag=tag, M=M * batch, N=N, K=K, splits=1,
                            mfma_flops=2.0 * M * batch * N * K * 6 / 16, mfma_bf16_flops=2.0 * M * batch * N * K * 6))
         return True
-    if not BLAS or require_x3 or not blas_ok:
-        return False
-    h = ctypes.c_void_p()
-    wsb = ctypes.c_longlong()
-    st = _lib.lib().krrn_blas_gemm_create(M, N, K, lda, ldo, batch, a_grp, o_grp, int(bias is not None), int(relu),
-                                          int(res is not None), ldr, r_grp, BLAS_MAX_WS, ctypes.byref(h),
-                                          ctypes.byref(wsb))
-    if st != 0:
-        return False
-    owner = _BlasPlan(h)
-    ws = plan.buf((max(int(wsb.value), 16),), torch.uint8, zero=False)
-    plan.buffers.append([owner, w, bias])
-    a_ptr = P(a.data_ptr() + 4 * a_off)
-    plan.add("krrn_blas_gemm_run", h, a_ptr, ptr(w), ptr(bias), ptr(res), ptr(out), ptr(ws), int(wsb.value),
-             meta=dict(kernel="hipblaslt_gemm_f32", flops=2.0 * (cin or K) * (cout or N) * M * batch, tag=tag,
-                       M=M * batch, N=N, K=K, splits=1))
-    return True
+    return False

@@ -72,8 +72,6 @@ def ranges_of(ts):
 def pointers(op):
     out = []
     for ai, a in enumerate(op.args):
-        if op.name == "krrn_blas_gemm_run" and ai == 0:
-            continue
         if isinstance(a, ctypes.c_void_p) and a.value:
             out.append((str(ai), a.value))
         elif isinstance(a, ctypes.Array):

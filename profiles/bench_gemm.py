@@ -1,5 +1,5 @@
 """Micro-bench: krrn_conv2d_f32 as a plain GEMM (the GCN `feature_map @ weights` and TBase shapes)
-over the tile menu, vs hipBLASLt (torch.mm, f32). usage: python3 profiles/bench_gemm.py
+over the tile menu and krrn_gemm_x3_f32, vs the vendor library (torch.addmm, f32). usage: python3 profiles/bench_gemm.py
 env SHAPES="M,K,N[,a_cs];..." TILES="1,2,..." X3=1 """
 import os
 import sys
@@ -56,23 +56,6 @@ for shp in shapes:
     from pose_estimation_amd import _lib
     from pose_estimation_amd.runtime import P
     st = P(torch.cuda.current_stream().cuda_stream)
-    import ctypes
-    h = ctypes.c_void_p()
-    wsb = ctypes.c_longlong()
-    _lib.check(_lib.lib().krrn_blas_gemm_create(M, N, K, a_cs, N, 1, 0, 0, 1, 0, 0, 0, 0, 64 << 20, ctypes.byref(h),
-                                                ctypes.byref(wsb)), "blas create")
-    ws = torch.empty(max(wsb.value, 16), dtype=torch.uint8, device=dev)
-    out = torch.zeros(M, N, device=dev)
-    fn = lambda: _lib.check(_lib.lib().krrn_blas_gemm_run(h, ptr(A), ptr(W), ptr(bias), ptr(None), ptr(out), ptr(ws),  # noqa: E731
-                                                          wsb.value, st), "blas run")
-    ms = ev_time(fn)
-    o1 = out.clone()
-    fn()
-    torch.cuda.synchronize()
-    err = float((out - ref).abs().max() / ref.abs().max())
-    line.append(f"LT {ms*1e3:.1f}us {fl/ms/1e9:.0f}TF ws={wsb.value}" + (" ERR" if err > 1e-5 else "") +
-                ("" if torch.equal(o1, out) else " NONDET"))
-    _lib.lib().krrn_blas_gemm_destroy(h)
     w3f = ops.gemm_weights_x3(W)
     out = torch.zeros(M, N, device=dev)
     fn = lambda: _lib.check(_lib.lib().krrn_gemm_x3_f32(ptr(A), a_cs, M, K, N, ptr(w3f), ptr(bias), ptr(None), 0,  # noqa: E731
@@ -81,8 +64,10 @@ for shp in shapes:
         ms = ev_time(fn)
         err = float((out - ref).abs().max() / ref.abs().max())
         line.append(f"GX3 {ms*1e3:.1f}us {fl/ms/1e9:.0f}TF" + (" ERR" if err > 1e-5 else ""))
+    # the vendor library's f32 GEMM with the bias epilogue (torch.addmm runs on hipBLASLt)
     Ac = A[:, :K].contiguous()
     Wt = W.t().contiguous()
-    ms = ev_time(lambda: torch.mm(Ac, Wt))
-    line.append(f"torch.mm {ms*1e3:.1f}us {fl/ms/1e9:.0f}TF")
+    ms = ev_time(lambda: torch.addmm(bias, Ac, Wt))
+    err = float((torch.addmm(bias, Ac, Wt) - ref).abs().max() / ref.abs().max())
+    line.append(f"torch.addmm {ms*1e3:.1f}us {fl/ms/1e9:.0f}TF" + (" ERR" if err > 1e-5 else ""))
     print(" | ".join(line), flush=True)

@@ -13,5 +13,5 @@ for f in *.hip; do
     -Xclang -target-feature -Xclang -packed-fp32-ops -c $f -o $out/$b.o 2>/dev/null &
 done
 wait
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../../build/variants/nopk.so $out/*.o -L/opt/rocm/lib -lhipblaslt -Wl,-rpath,/opt/rocm/lib
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../../build/variants/nopk.so $out/*.o -L/opt/rocm/lib -Wl,-rpath,/opt/rocm/lib
 echo built build/variants/nopk.so

@@ -18,5 +18,5 @@ extra=""
 [ "$2" = pnp ] && extra="-ffp-contract=off"
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=fast-honor-pragmas \
   -Xclang -target-feature -Xclang -packed-fp32-ops -I. $extra $3 -c $src -o $VDIR/$1_$2.o
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $VDIR/$1.so $objs $VDIR/$1_$2.o -L/opt/rocm/lib -lhipblaslt -Wl,-rpath,/opt/rocm/lib
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $VDIR/$1.so $objs $VDIR/$1_$2.o -L/opt/rocm/lib -Wl,-rpath,/opt/rocm/lib
 echo built $VDIR/$1.so

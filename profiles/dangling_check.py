@@ -62,8 +62,6 @@ for name, pp in (("plain", pipes[0]), ("pipelined", pipes[1])):
                 descs = ctypes.cast(ctypes.c_void_p(op.args[0].value), ctypes.POINTER(ConvDesc * n)).contents
                 ptrs = [(f"desc{q}.{f}", ctypes.c_void_p(getattr(descs[q], f))) for q in range(n)
                         for f in ("in_", "wt", "scale", "bias", "bias2", "res", "out", "workspace")]
-            elif op.name == "krrn_blas_gemm_run":
-                ptrs = ptrs[1:]  # arg 0 is the host-side plan handle
             for ai, a in ptrs:
                 if isinstance(a, ctypes.c_void_p) and a.value and a.value >= (0x7 << 44):
                     seen += 1

@@ -15,7 +15,7 @@ run base "" &&
 run no_small krrn_conv_small_f32 &&
 run no_wino krrn_conv3x3_wino_x3_f32 &&
 run no_gcn krrn_gcn_conv_f32 &&
-run no_gemm krrn_gemm_x3_f32,krrn_gemm_panel_x3_f32,krrn_blas_gemm_run &&
+run no_gemm krrn_gemm_x3_f32,krrn_gemm_panel_x3_f32 &&
 run no_pnp krrn_pnp_ransac_f32 &&
 run no_group krrn_conv2d_group_x3_f32,krrn_conv2d_x3_f32,krrn_conv2d_f32 &&
 run no_resize krrn_resize_bilinear_f32 &&

@@ -47,7 +47,6 @@ EXPECTED = {
     "krrn_conv2d_f32": [_P] + [_I] * 10 + [_P, _P, _P, _I, _I, _P, _P, _P, _I, _P, _I, _I, _P] + [_I] * 12 + [_P, _P],
     "krrn_knn_f32": [_P, _L, _I, _I, _P, _P, _L, _I, _I, _I, _I, _I, _I, _I, _P, _P],  # long long strides
     "krrn_pnp_ransac_f32": [_P, _I, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _I, _F, _D, _P, _P, _P, _P, _P, _I, _P],
-    "krrn_blas_gemm_create": [_I] * 6 + [_L, _L, _I, _I, _I, _I, _L, _L, _P, _P],  # ** and * out-parameters
     "krrn_randperm_i32": [_P, _U, _I, _I, _I, _P, _P],  # unsigned int
 }
 

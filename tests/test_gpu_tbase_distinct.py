@@ -1,6 +1,5 @@
-"""TBase on each crop's distinct (nn1, nn2) rows (KRRN_TBASE_DISTINCT) and the fusion's geometry stream
-(KRRN_GEOM_EARLY): the four entry points against their references, exactly, and the whole forward with
-both knobs off against both on, torch.equal on every output.
+"""TBase on each crop's distinct (nn1, nn2) rows (KRRN_TBASE_DISTINCT): the four entry points against
+their references, exactly, and the whole forward with the knob off against on, torch.equal on every output.
 
   krrn_pair_compact_i32          vs tests/pairs_ref.py (torch.unique per crop + the padding rule)
   krrn_gemm_x3_gather_live_f32   live rows vs krrn_gemm_x3_gather_f32 on the same index pairs; a dead
@@ -11,7 +10,7 @@ both knobs off against both on, torch.equal on every output.
 import pytest
 import torch
 
-from pose_estimation_amd import KRRN, _lib, fusion, make_config, ops, posenet
+from pose_estimation_amd import KRRN, _lib, make_config, ops, posenet
 from pose_estimation_amd._lib import P, ptr
 from pose_estimation_amd.fusion import level_sizes
 from pose_estimation_amd.synthetic import init_weights, make_batch
@@ -187,7 +186,7 @@ def test_rejects(dev):
     assert ts(ok, ok, 1, 0, 16, ok, ok, ok, ok, N, s) == ESHAPE
 
 
-# ---- the whole forward: both knobs off against both on --------------------------------------------
+# ---- the whole forward: the knob off against on --------------------------------------------------------
 B, S, N = 20, 64, 256
 
 
@@ -209,7 +208,6 @@ def _run(dev, sd, args, perms):
 
 
 def test_forward_is_bit_identical_with_both_knobs(dev, monkeypatch):
-    assert posenet.TBASE_GATHER
     m0 = KRRN(cfg=make_config(num_cls=1, backbone="w18"))
     sd = init_weights(m0, 0)
     d = make_batch(B, S, N, seed=11)
@@ -219,11 +217,9 @@ def test_forward_is_bit_identical_with_both_knobs(dev, monkeypatch):
     perms = [torch.randperm(N, generator=g)[:N1] for _ in range(4)] + [torch.randperm(N1, generator=g)[:N2]]
     perms = [p.to(dev) for p in perms]
     monkeypatch.setattr(posenet, "TBASE_DISTINCT", False)
-    monkeypatch.setattr(fusion, "GEOM_EARLY", False)
     off_outs, off_bufs, off_tb, off_names = _run(dev, sd, args, perms)
     assert "krrn_pair_compact_i32" not in off_names and "krrn_tbase_tail_f32" in off_names
     monkeypatch.setattr(posenet, "TBASE_DISTINCT", True)
-    monkeypatch.setattr(fusion, "GEOM_EARLY", True)
     on_outs, on_bufs, on_tb, on_names = _run(dev, sd, args, perms)
     for nm in ("krrn_pair_compact_i32", "krrn_gemm_x3_gather_live_f32", "krrn_gemm_x3_live_f32",
                "krrn_tbase_tail_slot_f32"):

@@ -58,7 +58,7 @@ def test_header_params_cover_plan_entry_points():
     """Every entry point a plan calls has its pointer parameters classified from the header."""
     params = header_pointer_params()
     for name in ("krrn_gcn_conv_f32", "krrn_conv3x3_wino_x3_f32", "krrn_gemm_panel_x3_f32", "krrn_knn_f32",
-                 "krrn_pnp_ransac_f32", "krrn_points_gather_f32", "krrn_blas_gemm_run"):
+                 "krrn_pnp_ransac_f32", "krrn_points_gather_f32"):
         w, r = params[name]
         assert w and r, name
     w, r = params["krrn_gcn_conv_f32"]
