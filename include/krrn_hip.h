@@ -190,21 +190,16 @@ int krrn_conv1x1_nchw_x3_f32(const float* in, int in_cs, int in_co, int B, int H
 
 /* 3x3 stride-1 pad-1 convolution by fused Winograd F(2x2, 3x3) (the head / last_layer /
  * deconv-BasicBlock convs: krrn.py:46-84, myhrnet.py:324-346; cuDNN / MIOpen use the same
- * algorithm for these f32 convs). U = G g G^T are the transformed weights, f32 in chunk-major
- * order [ceil(cin/8)][16][N][8] (element xi = 4u + v of the 4x4 transform; input channels
- * padded to a multiple of 8 with zeros), computed once per plan; epilogue as
+ * algorithm for these f32 convs), on the bf16 matrix cores at f32 accuracy: every operand split
+ * into three bf16 terms (x = x_h + x_m + x_l, round-to-nearest, exact), each product summed over
+ * the six term pairs hh, hm, mh, hl, lh, mm (the dropped ones are below 2^-23 |a b|), accumulated
+ * in f32. U = G g G^T are the transformed weights, f32 in chunk-major order
+ * [ceil(cin/8)][16][N][8] (element xi = 4u + v of the 4x4 transform; input channels padded to a
+ * multiple of 8 with zeros), computed once per plan (wino_weights); U3 is U split on the host
+ * (wino_weights_x3): plane U_mh [ceil(cin/8)][16][N][2][8] bf16 (m0..m3 h0..h3 of channels
+ * 4 half .. 4 half + 3) followed by plane U_l [ceil(cin/8)][16][N][2][4] bf16. Epilogue as
  * krrn_conv2d_f32: out = act(scale[n] * conv + bias[n] (+ res)). NHWC in/out with channel
- * stride / offset; cin multiple of 4, U 16-byte aligned. */
-int krrn_conv3x3_wino_f32(const float* in, int in_cs, int in_co, int B, int H, int W, int cin, const float* U,
-                          int N, int n_store, const float* scale, const float* bias, const float* res, int res_cs,
-                          int res_co, float* out, int out_cs, int out_co, int relu, void* stream);
-/* krrn_conv3x3_wino_f32 on the bf16 matrix cores at f32 accuracy: every operand split into
- * three bf16 terms (x = x_h + x_m + x_l, round-to-nearest, exact), each product summed over the
- * six term pairs hh, hm, mh, hl, lh, mm (the dropped ones are below 2^-23 |a b|), accumulated in
- * f32. U3 is wino_weights' U split on the host (wino_weights_x3): plane U_mh
- * [ceil(cin/8)][16][N][2][8] bf16 (m0..m3 h0..h3 of channels 4 half .. 4 half + 3) followed by
- * plane U_l [ceil(cin/8)][16][N][2][4] bf16; U3 16-byte aligned. Other arguments as
- * krrn_conv3x3_wino_f32. */
+ * stride / offset; cin multiple of 4, U3 16-byte aligned. */
 int krrn_conv3x3_wino_x3_f32(const float* in, int in_cs, int in_co, int B, int H, int W, int cin, const void* U3,
                              int N, int n_store, const float* scale, const float* bias, const float* res, int res_cs,
                              int res_co, float* out, int out_cs, int out_co, int relu, void* stream);

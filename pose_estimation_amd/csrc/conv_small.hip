@@ -101,9 +101,6 @@ __device__ __forceinline__ void small_body(const SmallArgs& a, int bx, int by, f
   // kSU independent loads in flight per thread, then their LDS writes (a rolled load -> write
   // loop would serialise one memory latency per element)
   constexpr int kSU = 8;
-#if KRRN_SMALL_EXP == 2  // timing experiment: no staging loads (LDS left as is)
-  if (total < 0)
-#endif
   for (int e0 = 0; e0 < total; e0 += 256 * kSU) {
     f32x4 v[kSU];
     int dst[kSU];
@@ -189,17 +186,11 @@ __device__ __forceinline__ void small_body(const SmallArgs& a, int bx, int by, f
   // this lane's (tap, channel quad) at step s0, advanced by 4 quads per step
   int kq0 = 4 * s0 + g;
   int tap = kq0 / Q, c4 = kq0 - (kq0 / Q) * Q;
-#ifndef KRRN_SMALL_PF
-#define KRRN_SMALL_PF 2
-#endif
-  // weights KRRN_SMALL_PF steps ahead in a register ring (slot u of every PF-step group)
-  constexpr int PF = KRRN_SMALL_PF;
+  // weights PF steps ahead in a register ring (slot u of every PF-step group)
+  constexpr int PF = 2;
   Wts wr[PF];
 #pragma unroll
   for (int u = 0; u < PF; ++u) wload(s0 + u, wr[u]);
-#if KRRN_SMALL_EXP == 1  // timing experiment: no K loop (staging + epilogue only)
-  if (s1 > 0x7fffffff - 1)
-#endif
   for (int st0 = s0; st0 < s1; st0 += PF) {
 #pragma unroll
     for (int u = 0; u < PF; ++u) {
@@ -218,22 +209,14 @@ __device__ __forceinline__ void small_body(const SmallArgs& a, int bx, int by, f
       for (int s2 = 0; s2 < 4; ++s2) {
 #pragma unroll
         for (int j = 0; j < NF; ++j) {
-#if KRRN_SMALL_EXP == 3  // timing experiment: no MFMAs (operands still loaded)
-          acc[j][s2] += av[s2] * w.f[j][s2];
-#else
           // weights as the first operand (rows = output channels), pixels as the second: lane l's
           // accumulator is channels 4 (l / 16) .. +3 of pixel l % 16 (one float4 in the epilogue)
           acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(w.f[j][s2], av[s2], acc[j], 0, 0, 0);
-#endif
         }
         if constexpr (T) {
-#if KRRN_SMALL_EXP == 3
-          tacc[s2] += av[s2] * w.t[s2];
-#else
           // block l / 4: rows = the quad's channels (lane 4 b + i holds row i), column l % 4 = this
           // lane's pixel; element i of the result is channel i of that pixel, k-quad g only
           tacc = __builtin_amdgcn_mfma_f32_4x4x1f32(w.t[s2], av[s2], tacc, 0, 0, 0);
-#endif
         }
       }
       c4 += 4;
@@ -357,11 +340,9 @@ int set_lds(const void* fn, long long lds) {
 // The tail's cross-lane sum is a fixed cost per wave, so it is taken only where a wave's reduction is
 // long enough to pay for it (measured: a loss at 2-3 K steps per wave, the 1x1 projections; even at 6;
 // a gain at 11-12, the branch convs). Shorter reductions run the remainder as a padded full tile.
-// ops.small_conv_rows (the plan's mfma_flops) restates this rule with the same 8: a library built with
-// another value mis-states that figure unless SMALL_TAIL_STEPS in ops.py moves with it.
-#ifndef KRRN_SMALL_TAIL_STEPS
-#define KRRN_SMALL_TAIL_STEPS 8
-#endif
+// ops.small_conv_rows (the plan's mfma_flops) restates this rule with the same 8: SMALL_TAIL_STEPS in
+// ops.py moves with it.
+constexpr int kSmallTailSteps = 8;
 
 template <int NW, int KS, int NF, int T>
 int small_launch_tail(const SmallArgs& a, hipStream_t s) {
@@ -375,14 +356,14 @@ int small_launch_tail(const SmallArgs& a, hipStream_t s) {
 }
 
 // The last y-block's tile slots: a remainder N % 16 of one quad is the tail after the full tiles, if a
-// wave runs at least KRRN_SMALL_TAIL_STEPS K steps; otherwise the remainder is one more (padded) full tile.
+// wave runs at least kSmallTailSteps K steps; otherwise the remainder is one more (padded) full tile.
 template <int NW, int KS>
 int small_launch(const SmallArgs& a, hipStream_t s) {
   const int ntiles = krrn_cdiv(a.N, 16);
   const int slots = ntiles - (krrn_cdiv(ntiles, NW) - 1) * NW;  // 1 .. NW tiles in the last y-block
   const int tq = krrn_cdiv(a.N % 16, 4);
   const int per = krrn_cdiv(krrn_cdiv(a.ksz * a.ksz * a.q, 4), KS);  // K steps per wave
-  const int t = (tq == 1 && per >= KRRN_SMALL_TAIL_STEPS) ? 1 : 0;
+  const int t = (tq == 1 && per >= kSmallTailSteps) ? 1 : 0;
   const int nf = t ? slots - 1 : slots;
 #define KRRN_SMALL_T(NFV, TV)                                    \
   if constexpr (NFV + TV <= NW) {                                \

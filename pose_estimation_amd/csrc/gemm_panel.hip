@@ -29,14 +29,9 @@
 namespace {
 
 constexpr int kPanelMaxN = 2048;  // columns whose bias a block stages in LDS
-#ifndef KRRN_GP_EXP
-#define KRRN_GP_EXP 0  // timing experiments only (results wrong): 1 no output stores, 2 no MFMAs
-#endif
-#ifndef KRRN_GP_NW128
-// waves (32-row panels) per block at K = 128: 4 (two blocks per CU) or 8 (one; half the weight-tile
-// copies into LDS, measured no faster: DESIGN.md "Next (after round 6)")
-#define KRRN_GP_NW128 4
-#endif
+// waves (32-row panels) per block at K = 128: 4 (two blocks per CU); 8 (one; half the weight-tile
+// copies into LDS) measured no faster: DESIGN.md "Next (after round 6)"
+constexpr int kNW128 = 4;
 
 struct PanelArgs {
   const float* a;
@@ -143,9 +138,7 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void gemm_pdma_x3_kernel(const Pan
       for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
     }
     const unsigned vo = (unsigned)(((8 * j + trow) * g.ldo + tcol) * 4);
-    if (KRRN_GP_EXP & 1) {
-      if (v[0] == 1234.5f) g.out[0] = v[1];
-    } else if (g.vec) {
+    if (g.vec) {
       __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rsO, vo, ctp * 128, 0);
     } else {
       // out / ldo not 16-B aligned: four dword stores. (Not __builtin_bit_cast(unsigned, v[e]): on an
@@ -200,20 +193,16 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void gemm_pdma_x3_kernel(const Pan
         const u32x4 mh = *reinterpret_cast<const u32x4*>(bp + gi * 384);  // [m h]
         const u32x2 lp = *reinterpret_cast<const u32x2*>(cur + gi * 384 + 256 + lane * 2);
         const u32x4 hl = {mh[2], mh[3], lp[0], lp[1]};  // [h l]
-#if KRRN_GP_EXP & 2
-        acc[gi & 15] += __uint_as_float(hl[0] ^ mh[1] ^ ca[gi][0]);
-#else
         acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(krrn_op(hl), krrn_sub4(ca[gi], 0), acc, 0, 0, 0);  // hh + lh
         acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(krrn_op(mh), krrn_sub4(ca[gi], 2), acc, 0, 0, 0);  // mh + hm
         acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(krrn_op(mh), krrn_sub4(ca[gi], 4), acc, 0, 0, 0);  // mm + hl
-#endif
       }
       if (st && gi % (G / 4) == 0) epilogue_t(ct - 1, gi / (G / 4));
     }
     accp = acc;
     // this wave's DMA into nxt must have landed before any wave reads it: vmcnt retires in order and
     // only the tile's 4 stores (issued by a live wave past its first tile) follow the DMA
-    if (st && !(KRRN_GP_EXP & 1)) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+    if (st) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
   };
@@ -244,8 +233,8 @@ KRRN_API int krrn_gemm_panel_x3_f32(const float* a, int lda, int M, int K, int N
   hipStream_t s = (hipStream_t)stream;
   const unsigned gy = (unsigned)krrn_cdiv(ntiles, per);
   if (K == 128)
-    hipLaunchKernelGGL((gemm_pdma_x3_kernel<128, false, KRRN_GP_NW128>),
-                       dim3((unsigned)krrn_cdiv(M, 32 * KRRN_GP_NW128), gy), dim3(64 * KRRN_GP_NW128), 0, s, g);
+    hipLaunchKernelGGL((gemm_pdma_x3_kernel<128, false, kNW128>),
+                       dim3((unsigned)krrn_cdiv(M, 32 * kNW128), gy), dim3(64 * kNW128), 0, s, g);
   else if (res) hipLaunchKernelGGL((gemm_pdma_x3_kernel<64, true, 4>), dim3((unsigned)krrn_cdiv(M, 128), gy), dim3(256), 0, s, g);
   else hipLaunchKernelGGL((gemm_pdma_x3_kernel<64, false, 4>), dim3((unsigned)krrn_cdiv(M, 128), gy), dim3(256), 0, s, g);
   return krrn_launch_status();

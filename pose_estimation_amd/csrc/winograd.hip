@@ -1,9 +1,10 @@
-// Winograd F(2x2, 3x3) convolution on the gfx950 f32 matrix cores, fully fused.
+// Winograd F(2x2, 3x3) convolution on the gfx950 bf16 matrix cores at f32 accuracy (split-bf16
+// operands), fully fused.
 //
 // Serves the stride-1, pad-1 3x3 convs of the KRRN heads (XYZNet / NMLNet at S/2 and S,
-// lib/network/krrn.py:46-84), the HRNet last_layer (myhrnet.py:328-346) and the deconv
-// BasicBlock (myhrnet.py:324). cuDNN / MIOpen pick Winograd for exactly these f32 convs on the
-// reference's own GPU path; here it is one kernel:
+// lib/network/krrn.py:46-84) that F(4x4) (winograd4.hip) does not take, the HRNet last_layer
+// (myhrnet.py:328-346) and the deconv BasicBlock (myhrnet.py:324). cuDNN / MIOpen pick Winograd for
+// exactly these f32 convs on the reference's own GPU path; here it is one kernel:
 //
 //   per 2x2 output tile t and input channel c: V = B^T d B  (d = the 4x4 input patch, pad 0)
 //   per output channel n:                      U = G g G^T  (host, f64, once per plan)
@@ -14,44 +15,34 @@
 // (Lavin & Gray 2016). The 16 products per tile replace 36 multiply-adds of the direct
 // conv: 2.25x fewer MFMA flops. Neither V nor M ever leaves the CU.
 //
-// Default kernel (wino_f23_ring_kernel): block = 16 x 2 output tiles of one image x 64 output
-// channels, 256 threads = 4 waves; wave w owns the components xi = 4w .. 4w+3 (row u = w of the
-// 4x4 grid) over the whole 32 x 64 block (2 x v_mfma_f32_32x32x2_f32 n-blocks each, 128
-// accumulator registers). Input channels stream in chunks of 8. Per chunk the block stages the
-// RAW input region of its 32 tiles (6 x 34 pixels x 8 channels, one b128 load per 16-B piece, 2
-// per thread, zero outside the image) into a 3-slot LDS ring; each lane reads the 2 patch rows its
-// component row needs (8 ds_read_b128) and forms its MFMA A operands V = B^T d B in registers,
-// for chunk ck+1 while chunk ck's MFMAs issue. A wave's weights are disjoint from the other
-// waves', so they skip LDS: 8 b128 loads per lane per chunk (1 KB contiguous per instruction),
-// one chunk ahead. One barrier per chunk. The output transform: wave w holds row u = w of every
-// (tile, channel)'s 4x4 M, so the column combination is lane-local and only 2 of 4 values per
-// row go through LDS; stores are float4 channel runs. The step runs the split-bf16 forms below
-// (wino_f23_x3_kernel); this f32 kernel is its accuracy reference.
-// Round 1's register-staged kernel (every thread transforming one (tile, channel) patch into an
-// LDS image of V, weights staged through LDS, two barriers per chunk: bit-identical, 1.55 ms) and
-// the ring without the transform overlap were removed in round 4.
-// Measured (MI355X, 64 x 128 -> 128 x 120 x 120, profiles/bench_wino.py): staged 1.55 ms, ring
-// 1.41 ms (84 TF in the matrix pipe; 68 % MFMA-busy by SQ_VALU_MFMA_BUSY_CYCLES at 2.05 GHz,
-// waves 73 % issue-stalled, 10 % in s_waitcnt / barriers), ring without the transform overlap
-// 1.44 ms; the epilogue costs 6-8 % (1.35 ms with it skipped). Rejected: an LDS-free variant
-// (every lane loading its own 8 patch vectors: 1.46 ms, TA busy 2.3x), s-outer MFMA order (no
-// gain), and from round 1: double-buffered LDS at one wave per SIMD (2.24 ms), persistent blocks
-// prefetching the next tile during the epilogue (1.57 ms, spills), s_setprio around the MFMA
-// cluster (+2 %), a 32-wide N tile at 3 blocks/CU (1.54-1.56 ms), a ping-pong kernel with two
-// wave groups (1.95 ms), LDS-DMA weights (1.49 ms).
+// The kernel (wino_f23_x3_kernel): block = 16 x 2 output tiles of one image x 64 output channels,
+// 256 threads = 4 waves; wave w owns the components xi = 4w .. 4w+3 (row u = w of the 4x4 grid)
+// over the whole 32 x 64 block (2 x v_mfma_f32_32x32x16_bf16 n-blocks each, 128 accumulator
+// registers). Input channels stream in chunks of 8. Per chunk the block stages the RAW input region
+// of its 32 tiles (6 x 34 pixels x 8 channels, one b128 load per 16-B piece, 2 per thread, zero
+// outside the image) into a 3-slot LDS ring; each lane reads the 2 patch rows its component row
+// needs (8 ds_read_b128), forms V = B^T d B in registers and splits it into its MFMA A operands.
+// A wave's weights are disjoint from the other waves', so they skip LDS: per lane and chunk 8 b128 +
+// 8 b64 loads of the host-split planes. One barrier per chunk. The output transform: wave w holds
+// row u = w of every (tile, channel)'s 4x4 M, so the column combination is lane-local and only 2 of
+// 4 values per row go through LDS; stores are float4 channel runs.
+// Removed after measurement (DESIGN.md sections 3 and 4 keep the numbers; the code is in the history
+// before this form): the f32-MFMA ring kernel this one grew out of (krrn_conv3x3_wino_f32: the same
+// block, ring and transform on v_mfma_f32_32x32x2_f32, 1.39-1.47 ms against 1.03-1.06 ms at 64 x 128
+// -> 128 x 120 x 120; it was the split kernel's accuracy reference, now an f64 conv in the tests),
+// round 1's register-staged kernel (1.55 ms), an LDS-free variant (1.46 ms, TA busy 2.3x), s-outer
+// MFMA order (no gain), double-buffered LDS at one wave per SIMD (2.24 ms), persistent blocks
+// prefetching the next tile during the epilogue (1.57 ms, spills), s_setprio around the MFMA cluster
+// (+2 %), a 32-wide N tile at 3 blocks/CU (1.54-1.56 ms), a ping-pong kernel with two wave groups
+// (1.95 ms), LDS-DMA weights (1.49 ms), and the knock-out timing builds that attributed the time
+// (no MFMAs, no loads, no split, no epilogue).
 #include "krrn_common.h"
 #include "krrn_split.h"
 
 namespace {
 
 constexpr int kWT = 32;       // tiles per block
-#ifndef KRRN_WINO_EXP
-#define KRRN_WINO_EXP 0
-#endif
-#ifndef KRRN_WINO_WN
-#define KRRN_WINO_WN 64
-#endif
-constexpr int kWN = KRRN_WINO_WN;  // output channels per block
+constexpr int kWN = 64;       // output channels per block
 constexpr int kNJ = kWN / 32;      // 32-wide n-blocks per wave
 constexpr int kN4 = kWN / 4;       // 4-channel groups per tile
 constexpr int kWC = 8;        // input channels per chunk
@@ -103,17 +94,11 @@ __device__ __forceinline__ void wino_epi_put(float* smem, f32x16 (&acc)[4][kNJ])
     }
 }
 
-// ---- The f32 ring kernel (krrn_conv3x3_wino_f32): raw input patches through a 3-slot LDS ring,
-// the transform done by the consuming waves, weights straight to registers ---------------------
-// Block = 16 x 2 output tiles (32 x 4 output pixels of one image) x 64 output channels; wave w
-// owns component row u = w (xi = 4w .. 4w+3) as above. Per 8-channel chunk the block stages the
-// RAW input region its 32 tiles read (6 rows x 34 cols x 8 channels = 408 16-B pieces, 2 per
-// thread, one b128 load each) into a ring slot; each lane then reads the 2 patch rows its
-// component row needs (8 ds_read_b128 = 4 columns x 2 rows x its 4 channels), forms
-// t = B^T-row (d_a +- d_b) and V[v] = t-combinations in registers (the same f32 operations as the
-// staged kernel: bit-identical operands), and feeds them as MFMA A operands. The weights of a
-// wave's own 4 components are disjoint from the other waves', so they skip LDS: 8 b128 loads per
-// lane per chunk (1 KB contiguous per wave-instruction), one chunk ahead. One barrier per chunk.
+// ---- The raw-input ring: per 8-channel chunk the block stages the RAW input region its 32 tiles
+// read (6 rows x 34 cols x 8 channels = 408 16-B pieces, 2 per thread, one b128 load each) into a
+// ring slot; each lane then reads the 2 patch rows its component row needs (8 ds_read_b128 = 4
+// columns x 2 rows x its 4 channels) and forms t = B^T-row (d_a +- d_b) and V[v] = t-combinations
+// in registers.
 constexpr int kGX = 16, kGY = 2;                 // tiles per block (x, y): kGX * kGY == kWT
 constexpr int kRR = 2 * kGY + 2, kRC = 2 * kGX + 2;  // raw rows / cols of a block
 constexpr int kRPieces = kRR * kRC * 2;          // 16-B pieces per chunk
@@ -274,167 +259,14 @@ __global__ __launch_bounds__(256) void wino_head_finish_kernel(const float* __re
     if (o < p1) out[(b * out_c + o) * HW + p] = v[o] + (b1 ? b1[o] : 0.f);
 }
 
-__global__ __launch_bounds__(256, 2) void wino_f23_ring_kernel(const WinoArgs a) {
-  __shared__ __attribute__((aligned(16))) float smem[4 * 2 * kWT * kSP];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int gxn = krrn_cdiv(a.Wt, kGX), gyn = krrn_cdiv(a.Ht, kGY), nbn = krrn_cdiv(a.N, kWN);
-  const int per_img = gxn * gyn;
-  const int bid = krrn_xcd_remap(blockIdx.x, a.B * per_img * nbn);
-  const int sp = bid / nbn, nb = bid - (bid / nbn) * nbn;
-  const int b = sp / per_img, r2 = sp - (sp / per_img) * per_img;
-  const int by = r2 / gxn, bx = r2 - (r2 / gxn) * gxn;
-  const int n0 = nb * kWN;
-  const int ty0 = by * kGY, tx0 = bx * kGX;
-  const int nck = krrn_cdiv(a.cin, kWC);
-
-  // raw staging: this thread's 2 pieces (pixel q/2 of the block's raw region, channel half q&1)
-  const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)(a.in + (size_t)b * a.img + a.in_co), (short)0, (int)min(a.img * 4 - (long long)a.in_co * 4, 0x7FFFFFFFLL),
-      0x00020000);
-  unsigned roff[2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int q = tid + 256 * i;
-    const int pix = q >> 1, hh = q & 1;
-    const int rr = pix / kRC, rc = pix - (pix / kRC) * kRC;
-    const int iy = 2 * ty0 - 1 + rr, ix = 2 * tx0 - 1 + rc;
-    const bool ok = q < kRPieces && iy >= 0 && iy < a.H && ix >= 0 && ix < a.W;
-    roff[i] = ok ? (unsigned)((((long long)iy * a.W + ix) * a.in_cs + 4 * hh) * 4) : kWOOB;
-  }
-  const int hq0 = tid & 1;  // channel half of piece 0 (piece 1 = tid + 256: the same half)
-  auto load_raw = [&](int ck, f32x4 (&r)[2]) {
-    const unsigned cb = (unsigned)(ck * kWC) * 4u;
-    const unsigned cm = (ck < nck && ck * kWC + 4 * hq0 < a.cin) ? 0u : kWOOB;
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-      r[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsA, (roff[i] + cb) | cm, 0, 0));
-  };
-  int wslot[2];  // this thread's 2 pieces in the padded slot layout (pieces past the region: a dummy slot)
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int q = tid + 256 * i;
-    const int pix = q >> 1, rr = pix / kRC;
-    wslot[i] = q < kRPieces ? ring_slot(rr, pix - rr * kRC, q & 1) : kRDummy;
-  }
-  auto store_raw = [&](int slot, const f32x4 (&r)[2]) {
-    float* dst = smem + slot * kRSlot;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) *reinterpret_cast<f32x4*>(dst + 4 * wslot[i]) = r[i];
-  };
-
-  // weights of this wave's components: lane (n = j*32 + fr, channels 4h..4h+3) of U[ck][xi][n]
-  const int fr = lane & 31, h = lane >> 5;
-  const __amdgpu_buffer_rsrc_t rsU = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)a.U, (short)0, (int)min((long long)nck * 16 * a.N * kWC * 4, 0x7FFFFFFFLL), 0x00020000);
-  unsigned uoff[4][kNJ];
-#pragma unroll
-  for (int v = 0; v < 4; ++v)
-#pragma unroll
-    for (int j = 0; j < kNJ; ++j) {
-      const int n = n0 + j * 32 + fr;
-      uoff[v][j] = n < a.N ? (unsigned)((((long long)(4 * wave + v) * a.N + n) * kWC + 4 * h) * 4) : kWOOB;
-    }
-  const unsigned ustride = (unsigned)(16 * a.N * kWC * 4);
-  auto load_w = [&](int ck, f32x4 (&w)[4][kNJ]) {
-    const unsigned wb = (unsigned)ck * ustride;
-    const unsigned wm = ck < nck ? 0u : kWOOB;
-#pragma unroll
-    for (int v = 0; v < 4; ++v)
-#pragma unroll
-      for (int j = 0; j < kNJ; ++j)
-        w[v][j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsU, (uoff[v][j] + wb) | wm, 0, 0));
-  };
-
-  // this lane's patch rows: t_u = d[ra] + sgn * d[rb] (B^T row u)
-  const int ra = wave == 0 ? 0 : (wave == 2 ? 2 : 1);
-  const int rb = wave == 0 ? 2 : (wave == 3 ? 3 : (wave == 1 ? 2 : 1));
-  const float sgn = wave == 1 ? 1.f : -1.f;
-  const int tx = fr % kGX, ty = fr / kGX;
-  const int pa = ring_slot(2 * ty + ra, 2 * tx, h);  // slot of (row ra, patch column 0)
-  const int pb = ring_slot(2 * ty + rb, 2 * tx, h);
-
-  f32x16 acc[4][kNJ];
-#pragma unroll
-  for (int x = 0; x < 4; ++x)
-#pragma unroll
-    for (int j = 0; j < kNJ; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[x][j][r] = 0.f;
-
-  auto make_v = [&](const float* sl, f32x4 (&V)[4]) {
-    f32x4 t[4];
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      const f32x4 da = *reinterpret_cast<const f32x4*>(sl + 4 * (pa + kColOff[c]));
-      const f32x4 db = *reinterpret_cast<const f32x4*>(sl + 4 * (pb + kColOff[c]));
-      t[c] = da + sgn * db;
-    }
-    V[0] = t[0] - t[2];
-    V[1] = t[1] + t[2];
-    V[2] = t[2] - t[1];
-    V[3] = t[1] - t[3];
-  };
-  auto mma = [&](const f32x4 (&V)[4], const f32x4 (&wc)[4][kNJ]) {
-#pragma unroll
-    for (int v = 0; v < 4; ++v)
-#pragma unroll
-      for (int j = 0; j < kNJ; ++j)
-#pragma unroll
-        for (int s2 = 0; s2 < 4; ++s2)
-          acc[v][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(V[v][s2], wc[v][j][s2], acc[v][j], 0, 0, 0);
-  };
-
-  f32x4 raw[2];
-  f32x4 w[4][kNJ];
-    // 3-slot ring: V of chunk ck+1 is formed (LDS reads + transform) beside chunk ck's MFMAs
-    load_raw(0, raw);
-    load_w(0, w);
-    store_raw(0, raw);
-    load_raw(1, raw);
-    __syncthreads();
-    store_raw(1, raw);
-    load_raw(2, raw);
-    f32x4 V[4];
-    make_v(smem, V);
-    __syncthreads();
-    for (int ck = 0; ck < nck; ++ck) {
-      f32x4 wc[4][kNJ];
-#pragma unroll
-      for (int v = 0; v < 4; ++v)
-#pragma unroll
-        for (int j = 0; j < kNJ; ++j) wc[v][j] = w[v][j];
-      load_w(ck + 1, w);
-      f32x4 Vn[4];
-      make_v(smem + ((ck + 1) % 3) * kRSlot, Vn);
-      mma(V, wc);
-      store_raw((ck + 2) % 3, raw);
-      load_raw(ck + 3, raw);
-#pragma unroll
-      for (int v = 0; v < 4; ++v) V[v] = Vn[v];
-      __syncthreads();
-    }
-#if KRRN_WINO_EXP == 4  // timing experiment: one store per lane instead of the epilogue
-  float sum = 0.f;
-#pragma unroll
-  for (int x = 0; x < 4; ++x)
-#pragma unroll
-    for (int j = 0; j < kNJ; ++j) sum += acc[x][j][0] + acc[x][j][15];
-  if (sum == 12345.f) a.out[tid] = sum;
-  return;
-#endif
-  wino_epi_put(smem, acc);
-  __syncthreads();
-  wino_epi_finish2d(a, smem, b, ty0, tx0, n0);
-}
-
-// ---- Split-bf16 ring kernel: the same block, ring and transform as wino_f23_ring_kernel<1>, the
+// ---- Split-bf16 ring kernel: the block, ring and transform above, the
 // 16 channel GEMMs on the bf16 matrix cores (v_mfma_f32_32x32x16_bf16, 16x the f32 rate) at f32
 // accuracy. Every f32 operand is split round-to-nearest into three bf16 terms,
 // x = x_h + x_m + x_l with |x_m| <= 2^-8 |x|, |x_l| <= 2^-16 |x| (exact: 24 significand bits),
 // and a product a b is summed over the 6 term pairs h h, h m, m h, h l, l h, m m; the 3 dropped
 // (m l, l m, l l) are below 2^-23 |a b|, the size of the f32 MFMA's own product rounding, and
-// everything accumulates in f32 (profiles/bench_wino_x3.py: RMS error vs f64 2.8e-7 against the
-// f32 kernel's 3.0e-7).
+// everything accumulates in f32 (RMS error vs f64 2.8e-7 against 3.0e-7 of the removed f32-MFMA
+// kernel, measured while both existed).
 // Register chains, no copies: a lane's 8 bf16 of an MFMA operand are 2 term kinds x its 4 channels
 // (k = 8 half + i pairs A and B element i of the same lane), so with the A chain [V_m V_h V_l] and
 // the B chain [U_m U_h U_l] (one b128 of plane U_mh + one b64 of plane U_l), 6 registers each, the
@@ -449,9 +281,9 @@ __global__ __launch_bounds__(256, 2) void wino_f23_ring_kernel(const WinoArgs a)
 // (SALU); a wave reloads component v's weights for the next chunk as soon as its MFMAs have
 // issued (one weight buffer in registers: acc 128 + weights 48 VGPRs).
 // Measured (MI355X, profiles/bench_wino_x3.py, 64 x 128 -> 128): 120x120 1.03-1.06 ms against
-// the f32 ring kernel's 1.39-1.47 ms, 60x60 0.27 vs 0.37 ms; in the step 412 vs 483 us per launch
-// (12.99 vs 13.68 ms per step on one box). The bf16 MFMAs take ~280 us of the 1.05 ms: timing
-// experiments (KRRN_WINO_EXP) put the rest in VALU issue (the split is 5.5 VALU per value, the
+// the removed f32 ring kernel's 1.39-1.47 ms, 60x60 0.27 vs 0.37 ms; in the step 412 vs 483 us per
+// launch (12.99 vs 13.68 ms per step on one box). The bf16 MFMAs take ~280 us of the 1.05 ms: knock-out
+// timing builds (removed) put the rest in VALU issue (the split is 5.5 VALU per value, the
 // transform ~2.5; a build with no MFMAs and no loads still takes 0.65 ms), then the weight and raw
 // loads (-15 % / -11 % without them) and the epilogue (-15 %). Rejected: a 64-tile, 512-thread
 // block (2 components x 2 tile-blocks x 2 n-blocks per wave: half the weight loads per MFMA and a
@@ -495,9 +327,6 @@ __global__ __launch_bounds__(256, 2) void wino_f23_x3_kernel(const WinoArgs a) {
     roffm[i] = hh ? kWOOB : roff[i];
   }
   auto load_raw = [&](int ck, f32x4 (&r)[2]) {  // chunks past the last reload the last (unused)
-#if KRRN_WINO_EXP == 6  // timing experiment: the first chunk's raw input only
-    if (ck > 0) return;
-#endif
     ck = min(ck, nck - 1);
     const bool half = ck * kWC + 4 >= a.cin;
 #pragma unroll
@@ -533,9 +362,6 @@ __global__ __launch_bounds__(256, 2) void wino_f23_x3_kernel(const WinoArgs a) {
   u32x4 wmh[4][kNJ];
   u32x2 wl[4][kNJ];
   auto load_wv = [&](int ck, int v) {
-#if KRRN_WINO_EXP == 5  // timing experiment: the first chunk's weights only
-    if (ck > 0) return;
-#endif
     ck = min(ck, nck - 1);
     const unsigned srec = (unsigned)(((ck * 16 + 4 * wave + v) * a.N) * 2);  // uniform
 #pragma unroll
@@ -595,24 +421,15 @@ __global__ __launch_bounds__(256, 2) void wino_f23_x3_kernel(const WinoArgs a) {
     make_v(smem + (ck % 3) * kRSlot, V);
 #pragma unroll
     for (int v = 0; v < 4; ++v) {
-#if KRRN_WINO_EXP == 8  // timing experiment: no split (V's bits as the operand chain)
-      u32x6 ac = {__float_as_uint(V[v][0]), __float_as_uint(V[v][1]), __float_as_uint(V[v][2]),
-                  __float_as_uint(V[v][3]), __float_as_uint(V[v][0]), __float_as_uint(V[v][1])};
-#else
       u32x6 ac = split3_chain(V[v]);
-#endif
       asm volatile("" : "+v"(ac));  // one register tuple: the MFMA operands are its sub-registers
 #pragma unroll
       for (int j = 0; j < kNJ; ++j) {
         u32x6 bc = {wmh[v][j][0], wmh[v][j][1], wmh[v][j][2], wmh[v][j][3], wl[v][j][0], wl[v][j][1]};
         asm volatile("" : "+v"(bc));
-#if KRRN_WINO_EXP == 7  // timing experiment: no MFMAs (operands still formed and loaded)
-        acc[v][j][0] += __uint_as_float(ac[0] ^ ac[4] ^ bc[0] ^ bc[4]);
-#else
         acc[v][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(krrn_sub4(ac, 0), krrn_sub4(bc, 0), acc[v][j], 0, 0, 0);  // mm + hh
         acc[v][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(krrn_sub4(ac, 0), krrn_sub4(bc, 2), acc[v][j], 0, 0, 0);  // mh + hl
         acc[v][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(krrn_sub4(ac, 2), krrn_sub4(bc, 0), acc[v][j], 0, 0, 0);  // hm + lh
-#endif
       }
       load_wv(ck + 1, v);
       // keep the reload here (hipcc otherwise sinks every weight load below all the MFMAs)
@@ -620,19 +437,8 @@ __global__ __launch_bounds__(256, 2) void wino_f23_x3_kernel(const WinoArgs a) {
     }
     store_raw((ck + 2) % 3, raw);
     load_raw(ck + 3, raw);
-#if KRRN_WINO_EXP != 10  // timing experiment 10: no barrier per chunk (results wrong)
     __syncthreads();
-#endif
   }
-#if KRRN_WINO_EXP == 11  // timing experiment: one store per lane instead of the epilogue
-  float sum = 0.f;
-#pragma unroll
-  for (int x = 0; x < 4; ++x)
-#pragma unroll
-    for (int j = 0; j < kNJ; ++j) sum += acc[x][j][0] + acc[x][j][15];
-  if (sum == 12345.f) a.out[tid] = sum;
-  return;
-#endif
   wino_epi_put(smem, acc);
   __syncthreads();
   if constexpr (HEAD)
@@ -642,41 +448,6 @@ __global__ __launch_bounds__(256, 2) void wino_f23_x3_kernel(const WinoArgs a) {
 }
 
 }  // namespace
-
-KRRN_API int krrn_conv3x3_wino_f32(const float* in, int in_cs, int in_co, int B, int H, int W, int cin,
-                                   const float* U, int N, int n_store, const float* scale, const float* bias,
-                                   const float* res, int res_cs, int res_co, float* out, int out_cs, int out_co,
-                                   int relu, void* stream) {
-  if (!in || !U || !out) return KRRN_EARG;
-  if (B < 1 || H < 1 || W < 1 || N < 1 || n_store < 1 || n_store > N) return KRRN_ESHAPE;
-  if (cin < 4 || (cin & 3) || in_co + cin > in_cs) return KRRN_EALIGN;
-  if (!krrn_aligned16(U) || (((uintptr_t)in) & 3u)) return KRRN_EALIGN;
-  if (out_co + n_store > out_cs) return KRRN_ESHAPE;
-  WinoArgs a;
-  a.in = in; a.in_cs = in_cs; a.in_co = in_co; a.B = B; a.H = H; a.W = W; a.cin = cin;
-  a.img = (long long)H * W * in_cs;
-  a.U = U; a.N = N; a.n_store = n_store; a.scale = scale; a.bias = bias;
-  a.res = res; a.res_cs = res_cs; a.res_co = res_co;
-  a.out = out; a.out_cs = out_cs; a.out_co = out_co; a.relu = relu;
-  a.w1 = nullptr; a.part = nullptr;
-  a.Ht = (H + 1) / 2; a.Wt = (W + 1) / 2;
-  const bool ov = !(out_cs & 3) && !(out_co & 3) && krrn_aligned16(out);
-  const bool rv = !res || (!(res_cs & 3) && !(res_co & 3) && krrn_aligned16(res));
-  const bool sv = (!scale || krrn_aligned16(scale)) && (!bias || krrn_aligned16(bias));
-  a.vec = (ov && rv && sv && !(n_store & 3)) ? 1 : 0;
-  const long long T = (long long)B * a.Ht * a.Wt;
-  if (T > 0x7fffffffLL) return KRRN_ESHAPE;
-  a.T = (int)T;
-  // 32-bit buffer offsets: the images one block's 32 tiles touch, and the weights
-  const long long span = ((kWT + (long long)a.Ht * a.Wt - 1) / ((long long)a.Ht * a.Wt) + 1) * a.img * 4;
-  if (span >= 0x7FFF0000LL || (long long)krrn_cdiv(cin, kWC) * 16 * N * kWC * 4 >= 0x7FFF0000LL) return KRRN_ESHAPE;
-  const long long blocks = (long long)krrn_cdiv(a.T, kWT) * krrn_cdiv(N, kWN);
-  if (blocks > 0x7fffffffLL) return KRRN_ESHAPE;
-  const long long rb = (long long)B * krrn_cdiv(a.Ht, kGY) * krrn_cdiv(a.Wt, kGX) * krrn_cdiv(N, kWN);
-  if (rb > 0x7fffffffLL || a.img * 4 >= 0x7FFF0000LL) return KRRN_ESHAPE;
-  hipLaunchKernelGGL(wino_f23_ring_kernel, dim3((unsigned)rb), dim3(256), 0, (hipStream_t)stream, a);
-  return krrn_launch_status();
-}
 
 KRRN_API int krrn_conv3x3_wino_x3_f32(const float* in, int in_cs, int in_co, int B, int H, int W, int cin,
                                       const void* U3, int N, int n_store, const float* scale, const float* bias,

@@ -27,7 +27,7 @@
 //            reads), requested after component 6 of chunk ck;
 //     T    : the transform of chunk ck + 1, interleaved with M(ck) (its steps sit in the MFMA gaps of
 //            each component): waves 0..5 own columns v = 0..5 of the 6x6 transform (waves 6, 7
-//            only multiply; KRRN_W4_TSPLIT); lane (tile, channel
+//            only multiply); lane (tile, channel
 //            half h) forms e[r] = B_v(d[r][.]) for the 6 patch rows, then V[u][v] = B_u(e[.]), splits
 //            each into the three bf16 terms and writes the MFMA operand chain [V_m V_h | V_l]
 //            (b128 + b64) to a 2-slot V buffer; V[comp][h][tile] = lane order, so the consumer's read
@@ -40,11 +40,9 @@
 //   Epilogue: 2 passes of 16 tiles through LDS ([comp][tile][n]); thread (channel quad, tile, output
 //   row i) forms t[v] = A_i(M[.][v]) and Y[i][j] = A_j(t), applies BN / bias / residual / ReLU and
 //   stores float4 channel runs.
-// Where the time goes (profiles/w4_trace.py, per-wave cycle stamps): the chunk
+// Where the time goes (profiles/r6_w4_trace.txt, per-wave cycle stamps): the chunk
 // loop 75 %, the epilogue 14 % (VALU-bound A^T transform), the prologue 8 %; the chip runs at
 // ~1.5 GHz under this kernel against ~2.1 GHz with either the MFMAs or the transform removed.
-#include <type_traits>
-
 #include "krrn_common.h"
 #include "krrn_split.h"
 
@@ -61,42 +59,12 @@ constexpr int kVMH = 36 * 64 * 4;                 // u32 per V buffer, plane [V_
 constexpr int kVL = 36 * 64 * 2;                  // u32 per V buffer, plane [V_l]
 constexpr int kET = kN * 4;                       // epilogue bytes per (component, tile): [64 n] f32
 constexpr unsigned kOOB = 0xFFFF0000u;
-// timing experiments only (results wrong; profiles/build_variant.sh), a bit mask: 1 no MFMAs, 2 no weight reloads,
-// 4 no transform, 8 no raw staging after the prologue, 16 no epilogue, 32 no output stores,
-// 64 one transform tap read per patch row (the VALU unchanged)
-#ifndef KRRN_W4_EXP
-#define KRRN_W4_EXP 0
-#endif
-#ifndef KRRN_W4_TSPLIT
-// 0 (default): waves 0-5 own transform columns 0-5, waves 6, 7 skip the transform; 1: waves 4 / 6 and
-// 5 / 7 split columns 4 / 5 (each SIMD the same transform VALU, but both waves of a pair redo the
-// column's row steps): 0.9 % slower under sustained load (760 vs 753 us per 120-px launch)
-#define KRRN_W4_TSPLIT 0
-#endif
-#ifndef KRRN_W4_TPAIR
-// 1: waves 2 pr + h (pr < 3) transform the column pair (2 pr, 2 pr + 1) of channel half h, one channel
-// pair per lane: 5 ds_read_b64 per patch row shared by both columns instead of 4 ds_read_b128 per column
-// (-37 % transform LDS-array cycles, but 6 ds_write_b32 per output for 2): 0.8 % slower under sustained
-// load (762 / 765 vs 756 / 759 us per 120-px launch, profiles/r6_tpair_ab.txt), so 0 (default)
-#define KRRN_W4_TPAIR 0
-#endif
-static_assert(!(KRRN_W4_TPAIR && KRRN_W4_TSPLIT), "one transform split");
-#ifndef KRRN_W4_SKIP3
-// 1: waves 0 / 5 skip the zero-coefficient 4th tap read of rows 1-5. The uniform branch splits the
-// chunk body's scheduling regions: 1.9 % slower under sustained load (772 vs 758 us, r6_w4_skip3_ab.txt)
-#define KRRN_W4_SKIP3 0
-#endif
-#ifndef KRRN_W4_TRACE
-#define KRRN_W4_TRACE 0  // 1: per-wave cycle stamps of the first 256 blocks (profiles/w4_trace.py; timing study only)
-#endif
-#ifndef KRRN_W4_RAWK
-#define KRRN_W4_RAWK 6
-#endif
-#ifndef KRRN_W4_GAP
-#define KRRN_W4_GAP 6
-#endif
-constexpr int kRawK = KRRN_W4_RAWK;  // component slot after which the raw chunk two ahead is requested
-constexpr int kGap = KRRN_W4_GAP;    // transform VALU instructions placed in each MFMA gap
+// Measured and rejected, removed from this file (DESIGN.md section 3 has the numbers): waves 4 / 6 and
+// 5 / 7 splitting transform columns 4 / 5 (0.9 % slower), a column-pair transform on ds_read_b64 (0.8 %
+// slower, profiles/r6_tpair_ab.txt), skipping the zero-coefficient 4th tap read (1.9 % slower,
+// profiles/r6_w4_skip3_ab.txt).
+constexpr int kRawK = 6;  // component slot after which the raw chunk two ahead is requested
+constexpr int kGap = 6;   // transform VALU instructions placed in each MFMA gap
 static_assert(kRR * kRS <= kRing && kRing == 3 * 512, "raw ring");
 static_assert(2 * (kRC - 1) + 1 + (kRC - 1) / 4 < kRS && (kRS * 4) % 16 == 0, "padded raw row");
 // LDS bytes: V plane MH x 2 | V plane L x 2 | raw ring x 2 (the epilogue's [36][64][12] f32 reuses
@@ -139,12 +107,6 @@ __device__ __forceinline__ float dpp_f(float x) {
 __device__ __forceinline__ u32x6 split3(const f32x4 x) {
   const KrrnSplit3 s = krrn_split3(x);
   return u32x6{s.m0, s.m1, s.h0, s.h1, s.l0, s.l1};
-}
-
-// x (a channel pair) -> its packed bf16 terms {m, h, l}
-__device__ __forceinline__ u32x3 split3_pair(const f32x2 x) {
-  const KrrnSplit3Pair s = krrn_split3_pair(x);
-  return u32x3{s.m, s.h, s.l};
 }
 
 // row K of B^T applied to x[0..5] (scalar f32, element-wise over the vector's channels)
@@ -285,7 +247,7 @@ __device__ __forceinline__ void epi_row(const Wino4Args& a, const char* E, int n
 #pragma unroll
         for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
       }
-      if (!(KRRN_W4_EXP & 32) || v[0] == 1234.5f) *reinterpret_cast<f32x4*>(o + j * a.out_cs) = v;
+      *reinterpret_cast<f32x4*>(o + j * a.out_cs) = v;
     }
     return;
   }
@@ -318,29 +280,11 @@ __global__ __launch_bounds__(256) void wino4_head_finish_kernel(const float* __r
     if (o < p1) out[(b * out_c + o) * HW + p] = v[o] + (b1 ? b1[o] : 0.f);
 }
 
-#if KRRN_W4_TRACE
-constexpr int kTrN = 52;  // per wave: [16 chunks][start, after component 4, before the barrier], 4 more
-__device__ unsigned g_w4_trace[256 * 8 * kTrN];
-#define W4_MARK(i)                                                  \
-  do {                                                              \
-    const unsigned t_ = (unsigned)__builtin_readcyclecounter();     \
-    if (lane == 0 && (i) < kTrN) trace_lds[wave * kTrN + (i)] = t_; \
-  } while (0)
-#else
-#define W4_MARK(i) \
-  do {             \
-  } while (0)
-#endif
-
 template <int HP>  // 0: conv output stored; 1..4: head form, HP rows of w1
 __global__ __launch_bounds__(512, 1) void wino_f43_x3_kernel(const Wino4Args a) {
   __shared__ __attribute__((aligned(16))) char smem[kLdsBytes];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-#if KRRN_W4_TRACE
-  __shared__ unsigned trace_lds[8 * kTrN];
-#endif
-  W4_MARK(48);
   const int gxn = krrn_cdiv(a.Wt, kGX), gyn = krrn_cdiv(a.Ht, kGY), nbn = krrn_cdiv(a.N, kN);
   const int per_img = gxn * gyn;
   const int bid = krrn_xcd_remap(blockIdx.x, a.B * per_img * nbn);
@@ -405,94 +349,11 @@ __global__ __launch_bounds__(512, 1) void wino_f43_x3_kernel(const Wino4Args a) 
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[k][r] = 0.f;
 
-#if KRRN_W4_TPAIR
-  // T, column pairs: wave 2 pr + th (pr < 3) transforms columns 2 pr and 2 pr + 1 of channel half th;
-  // lane (tile = lane >> 1, channel pair tq = lane & 1) reads 5 taps per patch row as f32x2 (one tile
-  // row per 32-lane ds_read_b64 group: 16 slots 36 dwords apart x 2 halves, conflict-free) in an order
-  // where column 2 pr takes taps 0..3 and column 2 pr + 1 taps 1..4 (the pair (2, 3) reads tap 1 twice),
-  // and writes each output's m / h / l bf16 pairs into the consumer's chain entry (16 tiles x 2 pairs
-  // per 32-lane ds_write_b32 group: 2-way, free)
-  const int tpr = wave < 6 ? wave >> 1 : 0, th = wave & 1;
-  const int ttile = lane >> 1, tq = lane & 1;
-  int tcol[5];
-  float ka[4], kb[4];
-  switch (tpr) {
-    case 0:  // 4 d0 - 5 d2 + d4 | -4 (d1 + d2) + d3 + d4
-      tcol[0] = 0; tcol[1] = 2; tcol[2] = 4; tcol[3] = 1; tcol[4] = 3;
-      ka[0] = 4.f; ka[1] = -5.f; ka[2] = 1.f; ka[3] = 0.f; kb[0] = -4.f; kb[1] = 1.f; kb[2] = -4.f; kb[3] = 1.f;
-      break;
-    case 1:  // 4 (d1 - d2) + d4 - d3 | 2 (d3 - d1) + d4 - d2
-      tcol[0] = 1; tcol[1] = 2; tcol[2] = 3; tcol[3] = 4; tcol[4] = 1;
-      ka[0] = 4.f; ka[1] = -4.f; ka[2] = -1.f; ka[3] = 1.f; kb[0] = -1.f; kb[1] = 2.f; kb[2] = 1.f; kb[3] = -2.f;
-      break;
-    default:  // 2 (d1 - d3) + d4 - d2 | 4 d1 - 5 d3 + d5
-      tcol[0] = 2; tcol[1] = 4; tcol[2] = 1; tcol[3] = 3; tcol[4] = 5;
-      ka[0] = -1.f; ka[1] = 1.f; ka[2] = 2.f; ka[3] = -2.f; kb[0] = 0.f; kb[1] = 4.f; kb[2] = -5.f; kb[3] = 1.f;
-      break;
-  }
-  const int pbase = (4 * (ttile >> 4)) * kRS + 9 * (ttile & 15) + th;  // patch origin slot
-  const char* tb[5];
-  char* twm = nullptr;  // this lane's word in the V entry of component 2 pr (plane MH)
-  char* twl = nullptr;  // (plane L)
-  f32x2 td[5], tea[6], teb[6];
-  auto t_begin = [&](int ck) {
-    const int p = ck & 1;
-    const char* rb = smem + kOffR + p * (kRingF * 4) + 16 * pbase + 8 * tq;
-#pragma unroll
-    for (int t = 0; t < 5; ++t) tb[t] = rb + 16 * (2 * tcol[t] + (tcol[t] >> 2));
-    twm = smem + p * (kVMH * 4) + 2 * tpr * 1024 + 16 * (32 * th + ttile) + 4 * tq;
-    twl = smem + kOffL + p * (kVL * 4) + 2 * tpr * 512 + 8 * (32 * th + ttile) + 4 * tq;
-#pragma unroll
-    for (int t = 0; t < 5; ++t) td[t] = *reinterpret_cast<const f32x2*>(tb[t]);
-  };
-  auto t_step = [&](int s) {
-    if (s < 6) {
-#pragma unroll
-      for (int e = 0; e < 2; ++e) {
-        tea[s][e] = __builtin_fmaf(ka[3], td[3][e], __builtin_fmaf(ka[2], td[2][e], __builtin_fmaf(ka[1], td[1][e], ka[0] * td[0][e])));
-        teb[s][e] = __builtin_fmaf(kb[3], td[4][e], __builtin_fmaf(kb[2], td[3][e], __builtin_fmaf(kb[1], td[2][e], kb[0] * td[1][e])));
-      }
-      if (s < 5) {
-#pragma unroll
-        for (int t = 0; t < 5; ++t) td[t] = *reinterpret_cast<const f32x2*>(tb[t] + (s + 1) * kRS * 16);
-      }
-      return;
-    }
-    const int u = s - 6;
-    f32x2 xa, xb;
-    switch (u) {
-      case 0: xa = bt_row<0>(tea); xb = bt_row<0>(teb); break;
-      case 1: xa = bt_row<1>(tea); xb = bt_row<1>(teb); break;
-      case 2: xa = bt_row<2>(tea); xb = bt_row<2>(teb); break;
-      case 3: xa = bt_row<3>(tea); xb = bt_row<3>(teb); break;
-      case 4: xa = bt_row<4>(tea); xb = bt_row<4>(teb); break;
-      default: xa = bt_row<5>(tea); xb = bt_row<5>(teb); break;
-    }
-    const u32x3 ca = split3_pair(xa), cb = split3_pair(xb);
-    char* wm = twm + 6 * u * 1024;
-    char* wl = twl + 6 * u * 512;
-    *reinterpret_cast<unsigned*>(wm) = ca[0];
-    *reinterpret_cast<unsigned*>(wm + 8) = ca[1];
-    *reinterpret_cast<unsigned*>(wl) = ca[2];
-    *reinterpret_cast<unsigned*>(wm + 1024) = cb[0];
-    *reinterpret_cast<unsigned*>(wm + 1024 + 8) = cb[1];
-    *reinterpret_cast<unsigned*>(wl + 512) = cb[2];
-  };
-#else
   // T: wave tv = wave < 6 transforms column tv of every (tile, channel half) patch: lane (tile, h)
   // forms e[r] = B_tv(d[r][.]) over the 6 patch rows (the row's taps: up to 4 columns with
   // wave-uniform coefficients), then V[u][tv] = B_u(e) for u = 0..5, split into the operand chain
   // and written to the V buffer at (6u + tv, h, tile) = the M phase's read address.
-  // balanced over the SIMDs (waves w and w + 4 share one): waves 0..3 transform columns 0..3 whole,
-  // waves 4 / 6 column 4 and waves 5 / 7 column 5, each pair splitting its 6 outputs (u < 3 / u >= 3)
-  // and both doing the column's 6 row steps: 326 + 211 VALU per SIMD instead of 326 + 326 / 326
-#if KRRN_W4_TSPLIT
-  const int tv = wave < 4 ? wave : 4 + (wave & 1);
-  const int tulo = wave < 6 ? 0 : 3, tuhi = wave < 4 ? 6 : (wave < 6 ? 3 : 6);
-#else
   const int tv = wave < 6 ? wave : 5;  // waves 6, 7 skip the transform
-  const int tulo = 0, tuhi = 6;
-#endif
   int tcol[4];
   float tk[4];
   switch (tv) {
@@ -518,7 +379,7 @@ __global__ __launch_bounds__(512, 1) void wino_f43_x3_kernel(const Wino4Args a) 
     twm = smem + p * (kVMH * 4) + tv * 1024 + 16 * lane;
     twl = smem + kOffL + p * (kVL * 4) + tv * 512 + 8 * lane;
 #pragma unroll
-    for (int t = 0; t < 4; ++t) td[t] = *reinterpret_cast<const f32x4*>(tb[(KRRN_W4_EXP & 64) ? 0 : t]);
+    for (int t = 0; t < 4; ++t) td[t] = *reinterpret_cast<const f32x4*>(tb[t]);
   };
   // step s < 6: e[s] from row s's taps, then row s + 1's reads; step 6 + u: output u
   auto t_step = [&](int s) {
@@ -529,21 +390,15 @@ __global__ __launch_bounds__(512, 1) void wino_f43_x3_kernel(const Wino4Args a) 
       if (s < 5) {
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
-          if ((KRRN_W4_EXP & 64) && t > 0) {  // timing study: one tap read per row, VALU unchanged
-            td[t] = td[0];
-            asm volatile("" : "+v"(td[t]));
-          } else if (KRRN_W4_SKIP3 && t == 3) {
-            // columns 0 / 5 have 3 taps (tk[3] = 0): keep row 0's finite 4th tap instead of re-reading
-            if (tv >= 1 && tv <= 4) td[3] = *reinterpret_cast<const f32x4*>(tb[3] + (s + 1) * kRS * 16);
-          } else {
-            td[t] = *reinterpret_cast<const f32x4*>(tb[t] + (s + 1) * kRS * 16);
-          }
+          // naming tv keeps it in this lambda's closure, where the removed tap-skipping form had it: hipcc
+          // orders the prologue's scalar moves by the closure's layout, and the measured binary has this one
+          (void)tv;
+          td[t] = *reinterpret_cast<const f32x4*>(tb[t] + (s + 1) * kRS * 16);
         }
       }
       return;
     }
     const int u = s - 6;
-    if (u < tulo || u >= tuhi) return;
     f32x4 x;
     switch (u) {
       case 0: x = bt_row<0>(te); break;
@@ -557,7 +412,6 @@ __global__ __launch_bounds__(512, 1) void wino_f43_x3_kernel(const Wino4Args a) 
     *reinterpret_cast<u32x4*>(twm + 6 * u * 1024) = u32x4{ch[0], ch[1], ch[2], ch[3]};
     *reinterpret_cast<u32x2*>(twl + 6 * u * 512) = u32x2{ch[4], ch[5]};
   };
-#endif
   // which transform steps run after component k's MFMAs (the VALU work beside the matrix pipe)
   constexpr int kStep0[10] = {0, 1, 2, 3, 4, 5, 7, 9, 11, 12};  // steps kStep0[k] .. kStep0[k + 1] - 1
 
@@ -565,7 +419,7 @@ __global__ __launch_bounds__(512, 1) void wino_f43_x3_kernel(const Wino4Args a) 
   // one chunk: M(ck) on V[ck & 1], interleaved with T(ck + 1) into V[(ck + 1) & 1]; the raw input
   // of chunk ck + 2 goes into the ring slot T(ck) has read
   auto do_chunk = [&](int ck) {
-    const bool tr = !(KRRN_W4_EXP & 4) && ck + 1 < nck && (KRRN_W4_TSPLIT || wave < 6);  // the last chunk: no T
+    const bool tr = ck + 1 < nck && wave < 6;  // the last chunk: no T
     const int p = ck & 1;
     const char* vm = smem + p * (kVMH * 4) + 16 * lane;
     const char* vlo = smem + kOffL + p * (kVL * 4) + 8 * lane;
@@ -574,7 +428,7 @@ __global__ __launch_bounds__(512, 1) void wino_f43_x3_kernel(const Wino4Args a) 
       const u32x2 l = *reinterpret_cast<const u32x2*>(vlo + comp_of(k) * 512);
       return u32x6{mh[0], mh[1], mh[2], mh[3], l[0], l[1]};
     };
-    const bool stage = ck + 2 < nck && !(KRRN_W4_EXP & 8);
+    const bool stage = ck + 2 < nck;
     __builtin_amdgcn_sched_barrier(0);
     if (tr) t_begin(ck + 1 < nck ? ck + 1 : ck + 1 - 2);  // past the last chunk: a harmless repeat
     u32x6 acn = chain(0);
@@ -585,23 +439,16 @@ __global__ __launch_bounds__(512, 1) void wino_f43_x3_kernel(const Wino4Args a) 
       asm volatile("" : "+v"(ac));  // one register tuple: the MFMA operands are its sub-registers
       u32x6 bc = {wmh[k % 3][0], wmh[k % 3][1], wmh[k % 3][2], wmh[k % 3][3], wl[k % 3][0], wl[k % 3][1]};
       asm volatile("" : "+v"(bc));
-#if KRRN_W4_EXP & 1
-      acc[k][0] += __uint_as_float(ac[0] ^ ac[4] ^ bc[0] ^ bc[4]);
-#else
       acc[k] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(krrn_sub4(ac, 0), krrn_sub4(bc, 0), acc[k], 0, 0, 0);  // mm + hh
       acc[k] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(krrn_sub4(ac, 0), krrn_sub4(bc, 2), acc[k], 0, 0, 0);  // mh + hl
       acc[k] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(krrn_sub4(ac, 2), krrn_sub4(bc, 0), acc[k], 0, 0, 0);  // hm + lh
-#endif
-#if !(KRRN_W4_EXP & 2)
       if (k < 6) load_w(ck, k + 3); else load_w(ck + 1, k - 6);
-#endif
       if (tr) {
 #pragma unroll
         for (int st = kStep0[k]; st < kStep0[k + 1]; ++st) t_step(st);
       }
       // the raw input of chunk ck + 2, into the ring slot T(ck) read during chunk ck - 1 (requested at
-      // the chunk's start instead, it only moves the wait: profiles/w4_trace.py)
-      if (k == 4 && ck < 16) W4_MARK(3 * ck + 1);
+      // the chunk's start instead, it only moves the wait: profiles/r6_w4_trace.txt)
       if (k == kRawK && stage) dma_raw(ck + 2, p);
       // issue shape of the slot: the next operands' LDS reads first, then the three MFMAs with the
       // transform VALU in their gaps (one wave's in-order issue would otherwise wait out each
@@ -628,38 +475,25 @@ __global__ __launch_bounds__(512, 1) void wino_f43_x3_kernel(const Wino4Args a) 
     asm volatile("s_waitcnt vmcnt(9)\n\ts_barrier" ::: "memory");
   else
     asm volatile("s_waitcnt vmcnt(6)\n\ts_barrier" ::: "memory");
-  if (!(KRRN_W4_EXP & 4) && (KRRN_W4_TSPLIT || wave < 6)) {
+  if (wave < 6) {
     t_begin(0);
 #pragma unroll
     for (int st = 0; st < 12; ++st) t_step(st);
   }
   asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)\n\ts_barrier" ::: "memory");
 
-  W4_MARK(49);
   for (int ck = 0; ck < nck; ++ck) {
-    if (ck < 16) W4_MARK(3 * ck);
     do_chunk(ck);
-    if (ck < 16) W4_MARK(3 * ck + 2);
     // hand-offs through LDS: the V buffers (lgkmcnt) and the raw chunk this wave's DMA wrote (issued
     // after component kRawK: the 2 (b128 + b64) weight loads of each later component may stay in flight)
     static_assert(kRawK >= 6 && kRawK <= 8, "vmcnt count below");
     asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(2 * (8 - kRawK)) : "memory");
   }
 
-#if KRRN_W4_EXP & 16
-  {
-    float sum = 0.f;
-#pragma unroll
-    for (int k = 0; k < 9; ++k) sum += acc[k][0] + acc[k][15];
-    if (sum == 12345.f) a.out[tid] = sum;
-    return;
-  }
-#endif
   // epilogue: 2 passes of 16 tiles (accumulator rows 8 pass .. 8 pass + 7 of each lane: local tile
   // (r & 3) + 8 ((r >> 2) & 1) + 4 h of the pass); a pass's stores free its 72 accumulator registers.
   // Then wave w forms output row i = w & 3 of tile groups (w >> 2) and (w >> 2) + 2: lane (tile of
   // the group, channel quad) -> float4 channel-run stores.
-  W4_MARK(50);
   const int enq = lane & 15, etl = lane >> 4, ei = wave & 3;
 #pragma unroll
   for (int pass = 0; pass < 2; ++pass) {
@@ -688,21 +522,9 @@ __global__ __launch_bounds__(512, 1) void wino_f43_x3_kernel(const Wino4Args a) 
     }
     __syncthreads();
   }
-#if KRRN_W4_TRACE
-  W4_MARK(51);
-  __syncthreads();
-  if (blockIdx.x < 256)
-    for (int i = tid; i < 8 * kTrN; i += 512) g_w4_trace[blockIdx.x * 8 * kTrN + i] = trace_lds[i];
-#endif
 }
 
 }  // namespace
-
-#if KRRN_W4_TRACE
-KRRN_API int krrn_w4_trace_copy(void* dst) {  // 256 blocks x 8 waves x kTrN u32 cycle stamps
-  return hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_w4_trace), sizeof(g_w4_trace)) == hipSuccess ? 0 : -1;
-}
-#endif
 
 KRRN_API int krrn_conv3x3_wino4_x3_f32(const float* in, int in_cs, int in_co, int B, int H, int W, int cin,
                                        const void* U3, int N, int n_store, const float* scale, const float* bias,

@@ -31,16 +31,6 @@ from .ops import Act, pad4
 from .runtime import add_conv_group, add_gemm, Plan, add_conv, ptr
 
 # switches (pose_estimation_amd/knobs.py has each one's meaning)
-DECONV_FOLD = knobs.flag("KRRN_DECONV_FOLD")
-CONVT_S2 = knobs.flag("KRRN_CONVT_S2")
-SMALL_CONV = knobs.flag("KRRN_SMALL_CONV")
-GEMM_1X1 = knobs.flag("KRRN_GEMM_1X1")
-FUSE_ID_FIRST = knobs.flag("KRRN_FUSE_ID_FIRST")
-WINO_X3 = knobs.flag("KRRN_WINO_X3")
-# a head's final 1x1 conv with <= 4 outputs (nml_final of a one-class model) fused into the split
-# Winograd of the conv before it (krrn_conv3x3_wino_x3_head_f32): its 128-channel input map is never
-# written or re-read
-HEAD_FUSE = knobs.flag("KRRN_HEAD_FUSE")
 # each HRNet fuse output waits for the branches it reads through capture edges (runtime.Edge)
 # instead of the module barrier (join into stream 0 + fork)
 FUSE_EDGES = knobs.flag("KRRN_FUSE_EDGES")
@@ -235,22 +225,31 @@ class _Builder:
         if out is None:
             out = self.act(Ho, Wo, spec.cout)
         assert (out.H, out.W) == (Ho, Wo) and out.cp >= pad4(spec.cout)
-        if (WINO_X3 and ops.wino_eligible(spec, x.B * Ho * Wo) and (Ho, Wo) == (x.H, x.W)
-                and ops.wino4_eligible(spec, x, Ho, Wo)):
-            U = ops.wino_weights_x3(ops.wino4_weights(conv, self.dev, cin_map=cin_map, cin_p=x.cp))
-            self.specs.append(U)
-            self.emit_wino4(x, spec, U, out, res, relu)
-        elif ops.wino_eligible(spec, x.B * Ho * Wo) and x.cs % 2 == 0 and x.co % 2 == 0:
-            U = ops.wino_weights(conv, self.dev, cin_map=cin_map, cin_p=x.cp)
-            if WINO_X3:
-                U = ops.wino_weights_x3(U)
-            self.specs.append(U)
-            self.emit_wino(x, spec, U, out, res, relu)
-        elif SMALL_CONV and ops.small_conv_eligible(spec, x):
+        wino = ops.wino_eligible(spec, x.B * Ho * Wo)  # stride 1, pad 1: (Ho, Wo) == (x.H, x.W)
+        if wino and ops.wino4_eligible(spec, x, Ho, Wo):
+            self.emit_wino(x, conv, spec, out, res, relu, f4=True, cin_map=cin_map)
+        elif wino and x.cs % 2 == 0 and x.co % 2 == 0:
+            self.emit_wino(x, conv, spec, out, res, relu, f4=False, cin_map=cin_map)
+        elif ops.small_conv_eligible(spec, x):
             self.emit_small(x, spec, out, res, relu)
-        elif not (GEMM_1X1 and self.emit_gemm(x, spec, out, res, relu)):
+        elif not self.emit_gemm(x, spec, out, res, relu):
             self.emit_conv(x, spec, out, res, relu)
         return out
+
+    def wino_problem(self, x: Act, conv: nn.Conv2d, spec, f4: bool, cin_map=None) -> Tuple[torch.Tensor, dict]:
+        """The split-bf16 Winograd's weight planes (ops.wino_weights_x3 of F(4x4)'s U when f4, else of
+        F(2x2)'s) and the launch's meta but its FLOP count: F(4x4) is 36 component products per 4x4
+        output tile, F(2x2) 16 per 2x2 tile. Matrix-pipe FLOPs: 2 per (component, tile, channel in,
+        channel out) in f32 terms; the split kernels issue 6 bf16 term products each (12 FLOPs) at 16x
+        the f32 rate, counted in f32-pipe time (/ 16) so all_conv's pipe fraction stays one scale."""
+        t, comps = (4, 36) if f4 else (2, 16)
+        np_ = pad4(spec.cout)
+        U = ops.wino_weights_x3((ops.wino4_weights if f4 else ops.wino_weights)(conv, self.dev, cin_map=cin_map,
+                                                                                cin_p=x.cp))
+        self.specs.append(U)  # kept alive with the plan
+        pipe = 2.0 * comps * spec.cin_p * np_ * x.B * ((x.H + t - 1) // t) * ((x.W + t - 1) // t)
+        return U, dict(kernel="wino_f43_x3" if f4 else "wino_f23_x3", M=x.B * x.H * x.W, N=np_, K=spec.cin_p * 9,
+                       mfma_flops=pipe * 6 / 16, mfma_bf16_flops=pipe * 6)
 
     def conv_head(self, x: Act, conv: nn.Module, bn: Optional[nn.Module], final: nn.Conv2d, out: torch.Tensor,
                   n_store: int) -> bool:
@@ -258,33 +257,27 @@ class _Builder:
         one split-Winograd launch plus a partial-sum pass (krrn_conv3x3_wino_x3_head_f32), for a final
         conv with at most 4 outputs (nml_final with one class, krrn.py:80-84, 98). False (nothing
         emitted) when it does not apply."""
-        if not (HEAD_FUSE and WINO_X3 and isinstance(conv, nn.Conv2d) and tuple(final.kernel_size) == (1, 1)
+        if not (isinstance(conv, nn.Conv2d) and tuple(final.kernel_size) == (1, 1)
                 and tuple(final.stride) == (1, 1) and final.in_channels == conv.out_channels
                 and n_store <= min(4, final.out_channels) and x.cs % 2 == 0 and x.co % 2 == 0):
             return False
         spec = ops.make_conv(conv, bn, self.dev, cin_p=x.cp)
-        Ho, Wo = ops.conv_out_hw(spec, x.H, x.W)
-        M = x.B * Ho * Wo
-        if not ops.wino_eligible(spec, M) or (Ho, Wo) != (x.H, x.W):
+        M = x.B * x.H * x.W
+        if not ops.wino_eligible(spec, M):
             return False
         np_ = pad4(spec.cout)
-        f4 = ops.wino4_eligible(spec, x, Ho, Wo)
-        U = ops.wino_weights_x3((ops.wino4_weights if f4 else ops.wino_weights)(conv, self.dev, cin_p=x.cp))
+        f4 = ops.wino4_eligible(spec, x, x.H, x.W)
+        U, meta = self.wino_problem(x, conv, spec, f4)
         w1 = torch.zeros(4, np_, device=self.dev)
         w1[:final.out_channels, :spec.cout] = final.weight.detach().reshape(final.out_channels, -1).float().to(self.dev)
         b1 = None
         if final.bias is not None:
             b1 = torch.zeros(4, device=self.dev)
             b1[:final.out_channels] = final.bias.detach().float().to(self.dev)
-        self.specs += [spec, U, w1] + ([b1] if b1 is not None else [])
+        self.specs += [spec, w1] + ([b1] if b1 is not None else [])
         part = self.plan.scratch(((np_ + 63) // 64) * M * 4)
-        if f4:
-            pipe = 2.0 * 36 * spec.cin_p * np_ * x.B * ((Ho + 3) // 4) * ((Wo + 3) // 4)
-        else:
-            pipe = 2.0 * 16 * spec.cin_p * np_ * x.B * ((Ho + 1) // 2) * ((Wo + 1) // 2)
-        meta = dict(kernel="wino_f43_x3_head" if f4 else "wino_f23_x3_head", tag="conv_wino_head", M=M, N=np_,
-                    K=spec.cin_p * 9, flops=2.0 * spec.cin * spec.cout * 9 * M + 2.0 * spec.cout * n_store * M,
-                    mfma_flops=pipe * 6 / 16, mfma_bf16_flops=pipe * 6)
+        meta.update(kernel=meta["kernel"] + "_head", tag="conv_wino_head",
+                    flops=2.0 * spec.cin * spec.cout * 9 * M + 2.0 * spec.cout * n_store * M)
         self.plan.add("krrn_conv3x3_wino4_x3_head_f32" if f4 else "krrn_conv3x3_wino_x3_head_f32", ptr(x.t), x.cs,
                       x.co, x.B, x.H, x.W, spec.cin_p, ptr(U), np_,
                       ptr(spec.scale), ptr(spec.bias), ptr(None), 0, 0, 1, ptr(w1), ptr(b1), n_store, ptr(part),
@@ -338,41 +331,17 @@ class _Builder:
                       meta=dict(kernel=f"conv_small<{p['nw']},{p['ks']}>", flops=p["flops"], tag=tag, M=p["M"], N=p["N"],
                                 K=spec.cin_p * spec.ksize ** 2, splits=1, mfma_flops=p["mfma_flops"]))
 
-    def emit_wino(self, x: Act, spec, U: torch.Tensor, out: Act, res: Optional[Act], relu: bool,
-                  tag: str = "conv"):
-        """Fused Winograd F(2x2,3x3): on the bf16 matrix cores with split operands (U = the
-        wino_weights_x3 planes) or on the f32 ones (U f32)."""
-        np_ = pad4(spec.cout)
-        M = x.B * out.H * out.W
-        x3 = U.dtype == torch.bfloat16
-        tiles = x.B * ((out.H + 1) // 2) * ((out.W + 1) // 2)
-        # matrix-pipe FLOPs: f32 MFMA 2 per (component, tile, channel in, channel out); the split
-        # kernel issues 6 bf16 term products each (12 FLOPs) at 16x the f32 rate, counted here in
-        # f32-pipe time (/ 16) so all_conv's pipe fraction stays one scale
-        pipe = 2.0 * 16 * spec.cin_p * np_ * tiles
-        meta = dict(kernel="wino_f23_x3" if x3 else "wino_f23<32,32,16>", flops=2.0 * spec.cin * spec.cout * 9 * M,
-                    tag=tag + "_wino", M=M, N=np_, K=spec.cin_p * 9, mfma_flops=pipe * 6 / 16 if x3 else pipe)
-        if x3:
-            meta["mfma_bf16_flops"] = pipe * 6
-        self.plan.add("krrn_conv3x3_wino_x3_f32" if x3 else "krrn_conv3x3_wino_f32", ptr(x.t), x.cs, x.co, x.B, x.H,
-                      x.W, spec.cin_p, ptr(U), np_, np_, ptr(spec.scale), ptr(spec.bias),
+    def emit_wino(self, x: Act, conv: nn.Conv2d, spec, out: Act, res: Optional[Act], relu: bool, f4: bool,
+                  cin_map=None):
+        """Fused Winograd on split-bf16 operands: F(4x4,3x3) (krrn_conv3x3_wino4_x3_f32) when f4, else
+        F(2x2,3x3) (krrn_conv3x3_wino_x3_f32)."""
+        U, meta = self.wino_problem(x, conv, spec, f4, cin_map)
+        np_ = meta["N"]
+        meta.update(flops=2.0 * spec.cin * spec.cout * 9 * meta["M"], tag="conv_wino")
+        self.plan.add("krrn_conv3x3_wino4_x3_f32" if f4 else "krrn_conv3x3_wino_x3_f32", ptr(x.t), x.cs, x.co, x.B,
+                      x.H, x.W, spec.cin_p, ptr(U), np_, np_, ptr(spec.scale), ptr(spec.bias),
                       ptr(res.t) if res is not None else ptr(None), res.cs if res is not None else 0,
                       res.co if res is not None else 0, ptr(out.t), out.cs, out.co, int(relu), meta=meta)
-
-    def emit_wino4(self, x: Act, spec, U: torch.Tensor, out: Act, res: Optional[Act], relu: bool,
-                   tag: str = "conv"):
-        """Fused Winograd F(4x4,3x3) on split-bf16 operands (krrn_conv3x3_wino4_x3_f32; U = the
-        wino_weights_x3 planes of wino4_weights)."""
-        np_ = pad4(spec.cout)
-        M = x.B * out.H * out.W
-        tiles = x.B * ((out.H + 3) // 4) * ((out.W + 3) // 4)
-        pipe = 2.0 * 36 * spec.cin_p * np_ * tiles  # f32-equivalent component products (see emit_wino)
-        meta = dict(kernel="wino_f43_x3", flops=2.0 * spec.cin * spec.cout * 9 * M, tag=tag + "_wino", M=M, N=np_,
-                    K=spec.cin_p * 9, mfma_flops=pipe * 6 / 16, mfma_bf16_flops=pipe * 6)
-        self.plan.add("krrn_conv3x3_wino4_x3_f32", ptr(x.t), x.cs, x.co, x.B, x.H, x.W, spec.cin_p, ptr(U), np_, np_,
-                      ptr(spec.scale), ptr(spec.bias), ptr(res.t) if res is not None else ptr(None),
-                      res.cs if res is not None else 0, res.co if res is not None else 0, ptr(out.t), out.cs,
-                      out.co, int(relu), meta=meta)
 
     def emit_convT_s2(self, x: Act, spec, out: Act, relu: bool, tag: str = "conv"):
         """A stride-2 transposed conv with 128 outputs (the deconv, myhrnet.py:314-326; XYZNet's first
@@ -391,7 +360,7 @@ class _Builder:
 
     def emit_conv(self, x: Act, spec, out: Act, res: Optional[Act], relu: bool, tag: str = "conv"):
         np_ = pad4(spec.cout)
-        if CONVT_S2 and ops.convT_s2_eligible(spec, x, out, res):
+        if ops.convT_s2_eligible(spec, x, out, res):
             self.emit_convT_s2(x, spec, out, relu, tag)
             return
         if spec.kind == "convT" and 1 < len(spec.taps) <= 4:
@@ -515,23 +484,16 @@ class _Builder:
 
     def _fuse_output(self, ys: List[Act], m: HighResolutionModule, i: int, out: Optional[Act],
                      pre: Optional[dict] = None) -> Act:
-        """relu(sum_j fuse_layers[i][j](ys[j])) (myhrnet.py:232-248). With FUSE_ID_FIRST the identity
-        term opens the sum (read in place) and every other term adds it in its producer's epilogue
-        (conv residual / resize add), so no separate add launch exists; the f32 summation order then
-        differs from the reference's j order (rounding-level)."""
+        """relu(sum_j fuse_layers[i][j](ys[j])) (myhrnet.py:232-248). The identity term opens the sum
+        (read in place) and every other term adds the running sum in its producer's epilogue (conv
+        residual / resize add), so no separate add launch exists; the f32 summation order differs
+        from the reference's j order (rounding-level)."""
         nb = m.num_branches
         out = out if out is not None else self.act(ys[i].H, ys[i].W, ys[i].c)
-        acc: Optional[Act] = None  # running sum lives in `out` once written
-        order = ([i] + [j for j in range(nb) if j != i]) if FUSE_ID_FIRST else list(range(nb))
-        for pos, j in enumerate(order):
-            last = pos == nb - 1
-            if j == i:
-                if acc is None:
-                    acc = ys[i]  # identity term: read in place, no copy
-                else:
-                    self.add_relu(acc, ys[i], out, relu=last)
-                    acc = out
-            elif j > i:
+        acc = ys[i]  # the identity term, read in place; the running sum lives in `out` once written
+        for pos, j in enumerate(j for j in range(nb) if j != i):
+            last = pos == nb - 2
+            if j > i:
                 seq = m.fuse_layers[i][j]
                 low = pre[(i, j)] if pre and (i, j) in pre else self.conv(ys[j], seq[0], seq[1])
                 self.resize(low, out, add=acc, align=False, relu=last)
@@ -640,7 +602,7 @@ def build_hrnet_plan(net: HRNet, plan: Plan, x: Act, after_layer1=None) -> Tuple
     bld.conv(cat, net.last_layer[0][0], net.last_layer[0][1], out=x1, relu=True, cin_map=cat_map)
     x2 = ycat.slice(Lpp, Cb)
     bld.conv(x1, net.last_layer[1], None, out=x2, relu=False)
-    if DECONV_FOLD and Lpp > L:
+    if Lpp > L:
         # deconv(cat(x1, x2)) with x2 = W2 x1 + b2 (last_layer_2 is linear, myhrnet.py:339-345) ==
         # a transposed conv on [x1 | 1] alone: W_eff = W_a + W2^T W_b per tap, and the constant
         # channel carries W_b^T b2 (exact at the borders too: the ones channel is out of range

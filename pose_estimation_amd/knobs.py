@@ -23,26 +23,13 @@ KNOBS: Dict[str, Tuple[Optional[str], str]] = {
                                   "recently used (B, S, N) plan"),
     "KRRN_DIAG_DROP": ("", "comma list of C-ABI entry points left out of new plans: a what-if timing "
                            "diagnostic (profiles/whatif.sh); outputs are meaningless with it set"),
-    # --- kernel path selection (each alternative is a kept, tested path)
-    "KRRN_WINO": ("1", "3x3 stride-1 convs on the Winograd kernels; 0 = the implicit-GEMM conv"),
-    "KRRN_WINO_X3": ("1", "Winograd with split-bf16 MFMAs (f32 accuracy); 0 = the f32 Winograd"),
-    "KRRN_WINO4": ("1", "the heads' wide 3x3 convs on the split-bf16 Winograd F(4x4, 3x3); 0 = F(2x2, 3x3)"),
+    # --- plan scheduling (each alternative is a kept, tested path; which kernel runs a conv or GEMM
+    # is decided by shape eligibility alone: hrnet._Builder.conv, runtime.add_gemm)
     "KRRN_FUSE_EARLY": ("1", "HRNet fuse terms that read one branch start on that branch's stream before the join"),
     "KRRN_MODULE_STREAMS": ("1", "consecutive HRNet modules of a stage keep each branch on its stream (no barrier between them)"),
     "KRRN_STAGE_STREAMS": ("1", "with KRRN_MODULE_STREAMS, HRNet stages chain per branch stream too (transitions on their branch's stream)"),
     "KRRN_FUSION_EARLY": ("1", "the fusion work that reads only the input cloud runs beside the HRNet phase (side stream)"),
     "KRRN_FUSE_EDGES": ("1", "each HRNet fuse output waits for exactly its branches (capture edges); 0 = module barrier"),
-    "KRRN_HEAD_FUSE": ("1", "a <= 4-output final 1x1 fused into the head's last split Winograd; 0 = two launches"),
-    "KRRN_SMALL_CONV": ("1", "HRNet branch / fuse convs on the LDS-slab conv_small kernel; 0 = implicit GEMM"),
-    "KRRN_GEMM_1X1": ("1", "stride-1 1x1 convs as plain GEMMs; 0 = implicit-GEMM conv"),
-    "KRRN_CONVT_S2": ("1", "stride-2 transposed convs with 128 outputs on the all-classes-per-block kernel (convt.hip); 0 = the grouped implicit GEMM"),
-    "KRRN_DECONV_FOLD": ("1", "fold last_layer_2 into the deconv (272 instead of 400 input channels); "
-                              "0 = the literal cat + deconv"),
-    "KRRN_FUSE_ID_FIRST": ("1", "HRNet fuse sums start from the identity branch; 0 = the reference's j order"),
-    "KRRN_GEMM_X3": ("1", "GEMMs with K >= 256 on the split-bf16 GEMM; 0 = the implicit-GEMM conv (TBase's "
-                          "GEMMs, which need its row-broadcast and live-row forms, raise)"),
-    "KRRN_GEMM_PANEL": ("1", "K = 64 / 128 GEMMs on the A-stationary panel GEMM; 0 = the implicit-GEMM conv"),
-    "KRRN_SPLITK": ("1", "split-K for implicit-GEMM convs with few output tiles; 0 = never"),
     "KRRN_TBASE_EARLY": ("1", "TBase conv1's level-1 half runs as soon as level 1 is done (side stream)"),
     "KRRN_TBASE_DISTINCT": ("1", "TBase conv2 / conv3 run once per distinct (nn1, nn2) "
                                  "pair of a crop and the tail reads each point's row by its slot (same bits); "

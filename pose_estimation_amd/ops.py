@@ -12,7 +12,7 @@ from typing import List, Optional, Sequence, Tuple
 
 import torch
 
-from . import _lib, knobs
+from . import _lib
 from ._lib import ptr, stream_ptr
 
 
@@ -213,18 +213,14 @@ def make_conv(conv: torch.nn.Conv2d, bn: Optional[torch.nn.Module], device, cin_
     return ConvSpec([wt], [taps], [(0, 0)], scale, bias, cin_p, cout, s, "conv", k, pad, len(cin_map))
 
 
-# Winograd switches, read at import like every other knob (knobs.py)
-WINO = knobs.flag("KRRN_WINO")
-WINO4 = knobs.flag("KRRN_WINO4")
-
 # Winograd F(2x2, 3x3) weight transform G (Lavin & Gray 2016): U = G g G^T
 WINO_G = torch.tensor([[1.0, 0.0, 0.0], [0.5, 0.5, 0.5], [0.5, -0.5, 0.5], [0.0, 0.0, 1.0]], dtype=torch.float64)
 
 
 def wino_weights(conv: torch.nn.Conv2d, device, cin_map: Optional[List[int]] = None,
                  cin_p: Optional[int] = None) -> torch.Tensor:
-    """[cout, cin, 3, 3] -> U f32 in the kernel's chunk-major order [ceil(cin_p/8)][16][pad4(cout)][8]
-    (xi = 4u + v; channels past cin_p are zero), transformed in f64."""
+    """[cout, cin, 3, 3] -> U f32 for krrn_conv3x3_wino_x3_f32 in chunk-major order
+    [ceil(cin_p/8)][16][pad4(cout)][8] (xi = 4u + v; channels past cin_p are zero), transformed in f64."""
     w = conv.weight.detach().cpu().double()
     cout, cin = w.shape[:2]
     if cin_map is None:
@@ -378,8 +374,6 @@ def gemm_weights_panel(wt: torch.Tensor) -> torch.Tensor:
 def wino_eligible(spec: ConvSpec, M: int) -> bool:
     """Fused Winograd for the wide stride-1 3x3 convs (>= 32 channels in and out, >= 32k output
     pixels); the narrow HRNet branches stay on the implicit GEMM (latency-bound there)."""
-    if not WINO:
-        return False
     return (spec.kind == "conv" and spec.ksize == 3 and spec.stride == 1 and spec.pad == 1
             and spec.cin_p >= 32 and spec.cout >= 32 and M >= 32768)
 
@@ -390,8 +384,6 @@ def wino4_eligible(spec: ConvSpec, x, H: int, W: int) -> bool:
     least 32 x 32, whose NHWC input is 16-byte aligned. The narrower / smaller Winograd convs (layer1
     and last_layer at S/4, 64 / 272 channels at 30 x 30) keep F(2x2): measured per shape,
     DESIGN.md section 3."""
-    if not WINO4:
-        return False
     return (spec.cin_p % 8 == 0 and spec.cin_p >= 64 and spec.cout >= 64 and min(H, W) >= 32
             and x.cs % 4 == 0 and x.co % 4 == 0)
 
@@ -406,7 +398,7 @@ def small_conv_config(M: int, ntiles: int, cin_p: int):
     return nw, ks
 
 
-# krrn_conv_small_f32's KRRN_SMALL_TAIL_STEPS (conv_small.hip): the two move together
+# krrn_conv_small_f32's kSmallTailSteps (conv_small.hip): the two move together
 SMALL_TAIL_STEPS = 8
 
 

@@ -59,7 +59,7 @@ def _conv1_fold(tb: TBase, inc_r: int, num_cls: int, dev):
     return w1, spec1, colv
 
 
-NEEDS_X3 = "TBase's GEMMs need the split-bf16 GEMM (KRRN_GEMM_X3=1)"
+NEEDS_X3 = "TBase's GEMMs need the split-bf16 GEMM, which does not take this shape (runtime.add_gemm)"
 
 
 def emit_tbase_level1(tb: TBase, plan: Plan, B: int, N: int, N1: int, feat1: torch.Tensor,

@@ -341,7 +341,6 @@ TILE_SHAPES = {1: (128, 128, 16), 2: (128, 64, 16), 3: (64, 64, 16), 4: (128, 12
                6: (128, 32, 32), 7: (128, 64, 32), 8: (64, 64, 32)}
 
 
-SPLITK = knobs.flag("KRRN_SPLITK")
 SPLITK_TILES = 256  # split only launches with fewer tiles
 SPLITK_NKT = 8      # ... and at least this many k-tiles
 SPLITK_PER = 4      # k-tiles per split at least
@@ -355,7 +354,7 @@ def conv_splits(M: int, N: int, K: int, tile: int) -> int:
     cd = lambda a, b: (a + b - 1) // b  # noqa: E731
     tiles = cd(M, BM) * cd(N, BN)
     nkt = cd(K, BK)
-    if tiles >= SPLITK_TILES or nkt < SPLITK_NKT or N % 4 or not SPLITK:
+    if tiles >= SPLITK_TILES or nkt < SPLITK_NKT or N % 4:
         return 1
     return max(1, min(cd(512, tiles), nkt // SPLITK_PER, 16))
 
@@ -465,11 +464,9 @@ def add_conv_group(plan: Plan, problems: List[dict], tile: int = None, tag: str 
 # plain GEMMs with K >= GEMM_X3_MINK on gemm_x3.hip (split-bf16); the short-K ones go to the panel kernel
 # below: gemm_x3 measured 10 % slower than a library f32 GEMM at K = 128 (the level-0 GCN GEMMs: 198 vs
 # 180 us, output-write-bound) and slower at layer1's K = 64 (profiles/bench_gemm.py, MI355X)
-GEMM_X3 = knobs.flag("KRRN_GEMM_X3")
-# short-K GEMMs (K = 64 / 128, N % 32 == 0, one row group) on the A-stationary split-bf16 kernel
-# (gemm_panel.hip): the level-0 / level-1 GCN GEMMs, whose 262 MB output makes them write streams
-GEMM_PANEL = knobs.flag("KRRN_GEMM_PANEL")
 GEMM_X3_MINK = 256
+# short-K GEMMs (K = 64 / 128, N % 32 == 0, one row group) run on the A-stationary split-bf16 kernel
+# (gemm_panel.hip): the level-0 / level-1 GCN GEMMs, whose 262 MB output makes them write streams
 
 
 def add_gemm(plan: Plan, *, a: torch.Tensor, a_off: int, lda: int, M: int, wt: torch.Tensor, K: int, N: int,
@@ -480,8 +477,8 @@ def add_gemm(plan: Plan, *, a: torch.Tensor, a_off: int, lda: int, M: int, wt: t
     """Append a plain GEMM out[m, n] = act(scale[n] * (A[m] . wt[n]) + bias[n] (+ res[m, n])) on one of the
     two split-bf16 GEMM kernels (scale folded into the packed weights): the A-stationary panel kernel for
     short K (64 / 128, one row group), else gemm_x3 for K >= 256. Returns False, with nothing appended,
-    when neither takes the problem (its shape or alignment, or KRRN_GEMM_PANEL / KRRN_GEMM_X3 = 0): the
-    caller then emits the implicit-GEMM conv, or raises where only this form will do.
+    when neither takes the problem (its shape or alignment): the caller then emits the implicit-GEMM
+    conv, or raises where only this form will do.
     require_x3: only gemm_x3 will do (its ldr = 0 per-group row broadcast); False if ineligible.
     live (int32 [batch], with require_x3): only the first live[g] rows of group g are in use; 128-row
     tiles past them are skipped (krrn_gemm_x3_live_f32). The FLOP count stays the full M * batch rows'.
@@ -505,7 +502,7 @@ def add_gemm(plan: Plan, *, a: torch.Tensor, a_off: int, lda: int, M: int, wt: t
     flops = 2.0 * (cin or K) * (cout or N) * M * batch
     if live is not None and not require_x3:
         raise ValueError("a live-row GEMM runs on gemm_x3 only (require_x3=True)")
-    if GEMM_PANEL and not require_x3 and K in (64, 128) and N % 32 == 0 and N <= 2048 and batch == 1 \
+    if not require_x3 and K in (64, 128) and N % 32 == 0 and N <= 2048 and batch == 1 \
             and lda % 4 == 0 and a_off % 4 == 0 and not (K == 128 and res is not None):
         wp = packed("panel", ops.gemm_weights_panel)
         csplit = 1
@@ -528,7 +525,7 @@ def add_gemm(plan: Plan, *, a: torch.Tensor, a_off: int, lda: int, M: int, wt: t
                            mfma_flops=2.0 * M * N * K * 6 / 16, mfma_bf16_flops=2.0 * M * N * K * 6,
                            bytes=4.0 * (M * K + M * N)))
         return True
-    if GEMM_X3 and K >= GEMM_X3_MINK and K % 32 == 0 and N % 128 == 0 and lda % 4 == 0 and ldo % 4 == 0 and a_off % 4 == 0 \
+    if K >= GEMM_X3_MINK and K % 32 == 0 and N % 128 == 0 and lda % 4 == 0 and ldo % 4 == 0 and a_off % 4 == 0 \
             and (res is None or ldr % 4 == 0):
         # own split-bf16 GEMM (gemm_x3.hip): 6 bf16 term products per f32 product
         w3 = packed("x3", ops.gemm_weights_x3)

@@ -1,4 +1,4 @@
-"""Micro-bench: krrn_conv3x3_wino_f32 (f32 MFMA), krrn_conv3x3_wino_x3_f32 (split-bf16 F(2x2,3x3))
+"""Micro-bench: krrn_conv3x3_wino_x3_f32 (split-bf16 F(2x2,3x3))
 and krrn_conv3x3_wino4_x3_f32 (split-bf16 F(4x4,3x3)) on the step's Winograd shapes: time per launch,
 and the error of each against an f64 CPU conv of the first 2 images (max |err| / max |ref| and RMS
 err / RMS ref).
@@ -42,18 +42,13 @@ for B, cin, cout, H, W in shapes:
     x = torch.relu(torch.randn(B, cin, H, W, generator=g))
     xa = ops.new_act(B, H, W, cin, dev, cs=cin)
     xa.t.copy_(x.permute(0, 2, 3, 1).to(dev))
-    U = ops.wino_weights(conv, dev, cin_p=cin)
-    U3 = ops.wino_weights_x3(U)
+    U3 = ops.wino_weights_x3(ops.wino_weights(conv, dev, cin_p=cin))
     U4 = ops.wino_weights_x3(ops.wino4_weights(conv, dev, cin_p=cin)) if cin % 8 == 0 else None
     out = ops.new_act(B, H, W, cout, dev, cs=cout)
     st = P(torch.cuda.current_stream().cuda_stream)
     with torch.no_grad():
         ref = (torch.nn.functional.conv2d(x[:2].double(), conv.weight.double(), padding=1).permute(0, 2, 3, 1)
                if not os.environ.get("NOREF") else None)
-
-    def f32():
-        _lib.check(L.krrn_conv3x3_wino_f32(ptr(xa.t), xa.cs, 0, B, H, W, cin, ptr(U), cout, cout, ptr(None), ptr(None),
-                                           ptr(None), 0, 0, ptr(out.t), out.cs, 0, 0, st), "wino")
 
     def x3():
         _lib.check(L.krrn_conv3x3_wino_x3_f32(ptr(xa.t), xa.cs, 0, B, H, W, cin, ptr(U3), cout, cout, ptr(None),
@@ -65,8 +60,8 @@ for B, cin, cout, H, W in shapes:
 
     fl = 2.0 * B * H * W * cin * cout * 9
     line = f"B{B} {cin}->{cout} {H}x{W}:"
-    kinds = os.environ.get("KERNELS", "f32,x3,w4").split(",")
-    for name, fn in (("f32", f32), ("x3", x3), ("w4", w4)):
+    kinds = os.environ.get("KERNELS", "x3,w4").split(",")
+    for name, fn in (("x3", x3), ("w4", w4)):
         if name not in kinds or (name == "w4" and U4 is None):
             continue
         out.t.zero_()

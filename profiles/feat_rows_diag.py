@@ -5,7 +5,7 @@ error (fm5 0-511 level 2, feat1 512-895 level 0 v / x / n, feat2 896-1279 level 
 distance from the point's predicted xyz / normal to its nearest other point in that space (a level-0
 surface conv normalises v_j - v_i: near-coincident predicted points amplify f32 noise).
 
-usage (GPU box): python3 profiles/feat_rows_diag.py   (KRRN_CONVT_S2=0/1 to compare kernels)
+usage (GPU box): python3 profiles/feat_rows_diag.py
 """
 import os
 import sys
@@ -50,7 +50,7 @@ err = (feat - fr).abs() / fr.abs().max()
 row = err.amax(-1)
 bad = (row >= 1e-3).nonzero().tolist()
 p9 = plan.p9.cpu()
-print(f"lib convT_s2={os.environ.get('KRRN_CONVT_S2', '1')} rows {row.numel()} failing {len(bad)} max {float(row.max()):.2e}")
+print(f"rows {row.numel()} failing {len(bad)} max {float(row.max()):.2e}")
 for b, p in bad:
     col = int(err[b, p].argmax())
     blk = "fm5" if col < 512 else ("feat1_" + "vxn"[(col - 512) // 128] if col < 896 else "feat2")

@@ -13,5 +13,4 @@ run pose_heads KRRN_POSE_AT=heads
 run pose_level2 KRRN_POSE_AT=level2
 run tbase_late KRRN_TBASE_EARLY=0
 run no_plan_streams KRRN_PLAN_STREAMS=0
-run splitk0 KRRN_SPLITK=0
 run base2 KRRN_X=0

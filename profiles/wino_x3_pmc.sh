@@ -1,6 +1,6 @@
 #!/bin/bash
-# SQ / TA counters of the f32 and split-bf16 Winograd kernels (profiles/bench_wino_x3.py; both
-# kernels in one run, rocprofv3 reports per dispatch), three --pmc passes per split-kernel variant:
+# SQ / TA counters of the split-bf16 Winograd kernels (profiles/bench_wino_x3.py; F(2x2) and F(4x4)
+# in one run, rocprofv3 reports per dispatch), three --pmc passes per split-kernel variant:
 #   bash profiles/wino_x3_pmc.sh "1 0" [SHAPES]
 set -e
 cd /tmp && export TMPDIR=/tmp

@@ -298,7 +298,20 @@ def test_conv_epilogue_float4_and_scalar(dev, x3, tile):
 @pytest.mark.parametrize("cin,cout,H,W,co", [(128, 128, 30, 30, 0), (64, 72, 17, 23, 4), (272, 272, 15, 15, 0),
                                              (36, 40, 9, 8, 8), (20, 132, 61, 35, 0), (128, 64, 120, 120, 0)])
 def test_conv3x3_winograd(dev, cin, cout, H, W, co):
-    """Fused Winograd F(2x2,3x3) (odd sizes, channel-offset input, residual) vs torch fp32 conv."""
+    """Fused Winograd F(2x2,3x3) on split-bf16 operands (krrn_conv3x3_wino_x3_f32; odd sizes,
+    channel-offset input, residual) vs torch fp32 conv (TOL) and vs an f64 conv + BN + residual + ReLU:
+    max |err| <= 1.02516e-6 max |ref|. The bound is twice the largest ratio measured on the commit before
+    the f32-MFMA Winograd (krrn_conv3x3_wino_f32, until then this test's cross-check) was removed, over
+    both kernels and these six shapes (MI355X, fixed seeds; the factor 2 covers contraction and ordering
+    changes between compiler versions):
+        shape (cin, cout, H, W, co)     f32 kernel    split kernel
+        (128, 128,  30,  30, 0)         5.1258e-07    4.0222e-07
+        ( 64,  72,  17,  23, 4)         2.7275e-07    2.2781e-07
+        (272, 272,  15,  15, 0)         4.7671e-07    4.9079e-07
+        ( 36,  40,   9,   8, 8)         1.7520e-07    1.7275e-07
+        ( 20, 132,  61,  35, 0)         1.6174e-07    1.5490e-07
+        (128,  64, 120, 120, 0)         4.4906e-07    4.6666e-07
+    F(4x4)'s larger transform constants get 1e-5 (test_conv3x3_winograd4)."""
     from pose_estimation_amd import _lib
     from pose_estimation_amd.runtime import P, ptr
     g = torch.Generator().manual_seed(cin + cout + H)
@@ -311,24 +324,19 @@ def test_conv3x3_winograd(dev, cin, cout, H, W, co):
     x = torch.randn(B, cin, H, W, generator=g)
     res = torch.randn(B, cout, H, W, generator=g)
     ref = torch.relu(bn(conv(x)) + res).detach()
+    with torch.no_grad():
+        s64 = bn.weight.double() / torch.sqrt(bn.running_var.double() + bn.eps)
+        y64 = F.conv2d(x.double(), conv.weight.double(), conv.bias.double(), padding=1)
+        ref64 = torch.relu((y64 - bn.running_mean.double()[:, None, None]) * s64[:, None, None]
+                           + bn.bias.double()[:, None, None] + res.double())
     cs = ops.pad4(cin) + co + 4
     xa = _nhwc(x, dev, cs=cs, co=co)
     spec = ops.make_conv(conv, bn, dev, cin_p=ops.pad4(cin))
-    U = ops.wino_weights(conv, dev, cin_p=ops.pad4(cin))
+    U3 = ops.wino_weights_x3(ops.wino_weights(conv, dev, cin_p=ops.pad4(cin)))
     ra = _nhwc(res, dev)
     out = ops.new_act(B, H, W, cout, dev, cs=ops.pad4(cout) + 4)
     np_ = ops.pad4(cout)
     L = _lib.lib()
-    out.t.fill_(float("nan"))
-    out.t[..., np_:] = 0.0
-    _lib.check(L.krrn_conv3x3_wino_f32(ptr(xa.t), xa.cs, xa.co, B, H, W, ops.pad4(cin), ptr(U), np_, np_,
-                                       ptr(spec.scale), ptr(spec.bias), ptr(ra.t), ra.cs, 0, ptr(out.t), out.cs, 0, 1,
-                                       P(torch.cuda.current_stream().cuda_stream)), "wino")
-    torch.cuda.synchronize()
-    got = out.t[..., :cout].permute(0, 3, 1, 2).cpu()
-    torch.testing.assert_close(got, ref, **TOL)
-    assert torch.count_nonzero(out.t[..., np_:]).item() == 0
-    U3 = ops.wino_weights_x3(U)
     out.t.fill_(float("nan"))
     out.t[..., np_:] = 0.0
     _lib.check(L.krrn_conv3x3_wino_x3_f32(ptr(xa.t), xa.cs, xa.co, B, H, W, ops.pad4(cin), ptr(U3), np_, np_,
@@ -338,8 +346,8 @@ def test_conv3x3_winograd(dev, cin, cout, H, W, co):
     got3 = out.t[..., :cout].permute(0, 3, 1, 2).cpu()
     torch.testing.assert_close(got3, ref, **TOL)
     assert torch.count_nonzero(out.t[..., np_:]).item() == 0
-    scale = float(ref.abs().max())
-    torch.testing.assert_close(got3, got, rtol=1e-5, atol=2e-6 * scale)
+    err = float((got3.double() - ref64).abs().max() / ref64.abs().max())
+    assert err <= 2 * 5.1258e-07, err
 
 
 @pytest.mark.parametrize("cin,k,op,H,W,ci,co,relu,bias", [
