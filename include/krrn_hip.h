@@ -479,7 +479,10 @@ int krrn_crop_inputs_u8(const unsigned char* rgb, const float* depth, const unsi
  * Then x_map / y_map = full-frame column / row (:712-715) and cloud [B][N][3] = ((x - cx) * z / fx,
  * (y - cy) * z / fy, z) with z = depth / depth_scale, f32 arithmetic in the reference's order
  * (:718-721); K4 [B][4] = fx, fy, cx, cy. count [B] = mask pixels (0 -> zeros everywhere: the
- * reference drops such a sample). choose int64 [B][N] (crop-local r*S + c). */
+ * reference drops such a sample). choose int64 [B][N] (crop-local r*S + c).
+ * 0 <= stream_id <= 65534 (KRRN_ESHAPE otherwise, before any launch): the id enters the key's top 16 bits
+ * as stream_id + 1, so ids further apart would draw the same subsets. A caller that needs more draws per
+ * seed than that advances the seed (PoseDataset.batch does). */
 int krrn_choose_points(const unsigned char* mask, int B, int S, int N, const float* depth, int H, int W,
                        const int* frame, const int* rc, const float* K4, float depth_scale, const long long* seed,
                        int stream_id, long long* choose, float* cloud, float* xmap, float* ymap, int* count,

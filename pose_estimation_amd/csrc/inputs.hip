@@ -21,6 +21,7 @@ namespace {
 
 constexpr int kChooseThreads = 1024;
 constexpr int kChooseWaves = kChooseThreads / 64;
+constexpr int kChooseStreamMax = 65534;
 
 __device__ __forceinline__ unsigned mix32(unsigned long long x) {
   // splitmix64 finaliser, high half
@@ -211,6 +212,9 @@ KRRN_API int krrn_choose_points(const unsigned char* mask, int B, int S, int N, 
   if (!mask || !depth || !frame || !rc || !K4 || !seed || !choose || !cloud || !xmap || !ymap || !count)
     return KRRN_EARG;
   if (B < 1 || S < 1 || N < 1 || H < 1 || W < 1 || S > H || S > W || depth_scale == 0.f) return KRRN_ESHAPE;
+  // (stream_id + 1) << 48 keeps 16 bits of the id: 65535 would give the keys of no stream term at all and
+  // 65536 those of 0, so ids outside 0 .. 65534 are refused instead of aliasing
+  if (stream_id < 0 || stream_id > kChooseStreamMax) return KRRN_ESHAPE;
   hipLaunchKernelGGL(choose_points_kernel, dim3(B), dim3(kChooseThreads), 0, (hipStream_t)stream, mask, S, N, depth,
                      H, W, frame, rc, K4, depth_scale, seed, stream_id, choose, cloud, xmap, ymap, count);
   return krrn_launch_status();

@@ -63,6 +63,8 @@ from .synthetic import LM_K, rand_rotation
 BORDER_LIST = [-1] + list(range(40, 640, 40)) + [640]
 # measured LineMOD test crop sizes (get_square_bbox over bbox_yolov3_all.json)
 LM_CROP_HIST = {40: 3, 80: 3025, 120: 4889, 160: 3659, 200: 1402, 240: 403, 280: 41, 320: 3}
+# krrn_choose_points takes stream ids 0 .. 65534 (include/krrn_hip.h)
+CHOOSE_STREAMS = 65535
 
 
 def get_square_bbox(bbox, height_px: int = 480, width_px: int = 640) -> Tuple[int, int, int, int]:
@@ -427,6 +429,7 @@ class PoseDataset(torch.utils.data.Dataset):
         self._dev_frames: Dict[str, Dict[str, torch.Tensor]] = {}
         self._dev_mesh: Dict[str, Dict[str, object]] = {}
         self._seed: Dict[str, torch.Tensor] = {}
+        self._seed_epoch: Dict[str, int] = {}  # how far each device's seed stands past its base (_draw_for)
         self._calls = 0
 
     def __len__(self):
@@ -441,7 +444,21 @@ class PoseDataset(torch.utils.data.Dataset):
         if key not in self._seed:
             self._seed[key] = torch.tensor([int(np.random.SeedSequence(len(self)).generate_state(1)[0])],
                                            dtype=torch.int64, device=device)
+            self._seed_epoch[key] = 0
         return self._seed[key]
+
+    def _draw_for(self, device) -> Tuple[torch.Tensor, int]:
+        """(seed tensor, stream_id) of batch number self._calls: krrn_choose_points takes ids 0 .. 65534, so the
+        id is calls % 65535 and the device seed is the base seed plus calls // 65535, advanced by one each
+        time the id wraps: no (seed, stream_id) pair repeats however long the run, and the first 65534 batches
+        draw what they always drew."""
+        seed = self._seed_for(device)
+        key = str(device)
+        epoch, sid = divmod(self._calls, CHOOSE_STREAMS)
+        if epoch != self._seed_epoch[key]:
+            seed += epoch - self._seed_epoch[key]
+            self._seed_epoch[key] = epoch
+        return seed, sid
 
     def frames(self, device) -> Dict[str, torch.Tensor]:
         """Synthetic frames, resident on `device` (all of them: 2.4 MB per 640x480 frame)."""
@@ -560,7 +577,8 @@ class PoseDataset(torch.utils.data.Dataset):
                                torch.tensor([mesh["range"][m[0]] for m in metas], dtype=torch.int32), R64, t64, K4,
                                boxes, torch.stack([mesh["region"][m[0]] for m in metas]),
                                frame_hw=tuple(fr["depth"].shape[1:]))
-        out = build_inputs(fr, fidx, boxes, self.num_point, K4, self._seed_for(device), stream_id=self._calls,
+        seed, sid = self._draw_for(device)
+        out = build_inputs(fr, fidx, boxes, self.num_point, K4, seed, stream_id=sid,
                            obj_mask=maps["cover_frame"] if maps is not None else None)
         info = self.obj_info
         ext = [np.array(info[m[0]]["size"]) / 1000.0 for m in metas]

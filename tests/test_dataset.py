@@ -3,6 +3,7 @@ pinned by the reference's own detection fixture, and the size-bucketed batcher."
 import os
 
 import numpy as np
+import torch
 
 from oracle import inputs_oracle as io
 from pose_estimation_amd.dataset import LM_CROP_HIST, BucketBatcher, get_square_bbox
@@ -100,3 +101,45 @@ def test_linemod_tree_cat_only(tmp_path):
     batches = list(BucketBatcher(ds, 8))
     assert sorted(S for S, _ in batches) == [80, 120]
     assert sorted(i for _, idx in batches for i in idx) == [0, 1, 2, 3]
+
+
+def test_batch_draws_never_repeat_a_seed_and_stream_id(monkeypatch):
+    """PoseDataset.batch numbers its point draws by call. krrn_choose_points takes stream ids 0 .. 65534, so over
+    200 000 calls (three wraps of the id) every id handed to the launch is in range and no (seed, stream_id)
+    pair repeats; the first 65534 calls keep the base seed and the ids 1, 2, ... they always had. The launch
+    is faked: the first and the wrapping calls go through batch() itself, the rest through the method batch()
+    takes its draw from."""
+    from pose_estimation_amd import dataset
+    from pose_estimation_amd.dataset import CHOOSE_STREAMS, PoseDataset
+
+    seen = []
+
+    def fake_build_inputs(frames, frame_idx, boxes, num_point, K4, seed, stream_id=0, **kw):
+        seen.append((int(seed), int(stream_id)))
+        return {}
+
+    monkeypatch.setattr(dataset, "build_inputs", fake_build_inputs)
+    assert CHOOSE_STREAMS == 65535
+    ds = PoseDataset("test", 50, False, None, 0.0, 8, cls_type="cat", num_frames=1, sizes=[40], n_model_pts=8)
+    base = int(ds._seed_for(torch.device("cpu")))
+    ds.batch([0], "cpu")
+    ds.batch([0], "cpu")
+    assert seen == [(base, 1), (base, 2)]
+    ds._calls = CHOOSE_STREAMS - 2
+    for _ in range(3):
+        ds.batch([0], "cpu")
+    assert seen[2:] == [(base, 65534), (base + 1, 0), (base + 1, 1)]
+    # a run restarted from call 0 (the evaluation tests do this) draws the first run's pairs again
+    ds._calls = 0
+    ds.batch([0], "cpu")
+    assert seen[-1] == (base, 1)
+
+    ds._calls = 0
+    pairs = set()
+    for call in range(1, 200001):
+        ds._calls = call
+        seed, sid = ds._draw_for(torch.device("cpu"))
+        assert 0 <= sid <= 65534
+        pairs.add((int(seed), sid))
+    assert len(pairs) == 200000
+    assert {s for s, _ in pairs} == {base, base + 1, base + 2, base + 3}

@@ -1,14 +1,24 @@
 """On-GPU input construction (krrn_crop_inputs_u8, krrn_choose_points) vs the numpy oracle of
 PoseDataset._load_data on identical frames: normalised crop and point mask bit-exact, `choose`
 exact when the mask is small (wrap padding), an order-preserving uniform N-subset of the mask
-pixels when it is large, and cloud / x_map / y_map bit-exact for the chosen pixels."""
+pixels when it is large, and cloud / x_map / y_map bit-exact for the chosen pixels.
+
+The second half calls the two entry points directly with test-made masks and frames, so that each crop's
+pixel count is exact: `choose` equals tests/draws_ref.py's restatement of the radix select element for
+element (ties, wrap padding, empty crops, stream ids), the geometry is bit-exact under frame indirection,
+per-crop intrinsics and a depth scale, every output sits between sentinel guards, and bad arguments are
+refused on the host."""
 import numpy as np
 import pytest
 import torch
 
 from oracle import inputs_oracle as io
 from pose_estimation_amd.dataset import PoseDataset, build_inputs, get_square_bbox, synthetic_frames
+from pose_estimation_amd import _lib
+from pose_estimation_amd._lib import P, stream_ptr
 from pose_estimation_amd.synthetic import LM_K
+from tests import draws_ref as D
+from tests.guarded import Guarded
 
 pytestmark = pytest.mark.gpu
 
@@ -45,6 +55,7 @@ def test_inputs_match_oracle(dev, S, N):
         else:
             cand = m.flatten().nonzero()[0]
             assert len(ch) == N and np.all(np.diff(ch) > 0) and np.isin(ch, cand).all()
+            assert np.array_equal(ch, D.choose(m, N, seed=1234, stream_id=3, crop=b))  # the N smallest keys
         cloud, xm, ym = io.points(ch, fr["depth"][b], rmin, cmin, S, k4f)
         assert np.array_equal(out["cloud"][b].cpu().numpy(), cloud)
         assert np.array_equal(out["x_map_choosed"][b, :, 0].cpu().numpy(), xm)
@@ -85,3 +96,230 @@ def test_pose_dataset_batch(dev):
     assert data["cloud"].shape == (B, 1000, 3) and data["cls_id"].shape == (B, 1)
     item = ds[idx[0]]
     assert item["cloud"].shape == (1000, 3)
+
+
+# ---- the entry points called directly: exact counts, exact subsets ----
+
+EARG, ESHAPE = -1, -2
+
+
+def _scene(F, H, W, seed):
+    """Small frames: random rgb, a positive depth with 5 % holes, a label mask with 20 % zeros."""
+    rng = np.random.default_rng(seed)
+    depth = rng.uniform(0.5, 1.5, size=(F, H, W)).astype(np.float32)
+    depth[rng.random((F, H, W)) < 0.05] = 0.0
+    return {"rgb": rng.integers(0, 256, size=(F, H, W, 3), dtype=np.uint8), "depth": depth,
+            "mask_label": ((rng.random((F, H, W)) < 0.8) * 255).astype(np.uint8)}
+
+
+def _masks(counts, S, seed):
+    """u8 [B][S*S] with exactly counts[b] ones each, scattered differently per crop."""
+    rng = np.random.default_rng(seed)
+    m = np.zeros((len(counts), S * S), np.uint8)
+    for b, c in enumerate(counts):
+        m[b, rng.choice(S * S, c, replace=False)] = 1
+    return m
+
+
+def _k4(B):
+    return np.array([[K4[0] * (1 + 0.01 * b), K4[1] * (1 - 0.02 * b), K4[2] + 3 * b, K4[3] - 5 * b]
+                     for b in range(B)], np.float32)
+
+
+def _dev(dev, a):
+    return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+
+
+def _choose_call(dev, masks, S, N, depth, frame, rc, k4, depth_scale, seed, stream_id):
+    """One krrn_choose_points launch with every output between guards. Returns (status, guarded outputs,
+    keep-alive inputs)."""
+    B = len(masks)
+    F, H, W = depth.shape
+    ins = [_dev(dev, masks), _dev(dev, depth), _dev(dev, np.asarray(frame, np.int32)),
+           _dev(dev, np.asarray(rc, np.int32)), _dev(dev, k4), torch.tensor([seed], dtype=torch.int64, device=dev)]
+    out = {"choose": Guarded(dev, (B, N), torch.int64), "cloud": Guarded(dev, (B, N, 3), torch.float32),
+           "xmap": Guarded(dev, (B, N), torch.float32), "ymap": Guarded(dev, (B, N), torch.float32),
+           "count": Guarded(dev, (B,), torch.int32)}
+    st = _lib.lib().krrn_choose_points(
+        P(ins[0].data_ptr()), B, S, N, P(ins[1].data_ptr()), H, W, P(ins[2].data_ptr()), P(ins[3].data_ptr()),
+        P(ins[4].data_ptr()), float(depth_scale), P(ins[5].data_ptr()), stream_id, P(out["choose"].ptr),
+        P(out["cloud"].ptr), P(out["xmap"].ptr), P(out["ymap"].ptr), P(out["count"].ptr), stream_ptr(dev))
+    return st, out, ins
+
+
+def _choose_exact(dev, masks, S, N, depth, frame, rc, k4, depth_scale=1.0, seed=1234, stream_id=3):
+    """Launch, then hold every output of every crop to the restatement: `choose` and `count` exactly, the maps
+    and the cloud bit for bit (zeros for an empty crop). Returns choose [B][N]."""
+    st, out, _ = _choose_call(dev, masks, S, N, depth, frame, rc, k4, depth_scale, seed, stream_id)
+    assert st == 0
+    torch.cuda.synchronize()
+    got = {k: v.get() for k, v in out.items()}
+    for b in range(len(masks)):
+        cnt = int(masks[b].sum())
+        assert int(got["count"][b]) == cnt, b
+        ref = D.choose(masks[b], N, seed=seed, stream_id=stream_id, crop=b)
+        assert np.array_equal(got["choose"][b], ref), b
+        if cnt == 0:
+            cloud, xm, ym = np.zeros((N, 3), np.float32), np.zeros(N, np.float32), np.zeros(N, np.float32)
+        else:
+            cloud, xm, ym = io.points(ref, depth[frame[b]], rc[b][0], rc[b][1], S, k4[b], depth_scale)
+        assert np.array_equal(got["cloud"][b].view(np.uint32), cloud.view(np.uint32)), b
+        assert np.array_equal(got["xmap"][b], xm) and np.array_equal(got["ymap"][b], ym), b
+    return got["choose"]
+
+
+@pytest.mark.parametrize("S,count,N", [(33, 1089, 1), (33, 700, 699), (95, 9000, 1000)])
+def test_choose_is_the_n_smallest_keys(dev, S, count, N):
+    """count > N: exactly the ranks of the N smallest (key, rank) pairs, three crops whose keys differ by the
+    crop index (and whose masks differ where the count leaves room)."""
+    sc = _scene(3, S + 2, S + 7, seed=S)
+    masks = _masks([count] * 3, S, seed=count)
+    ch = _choose_exact(dev, masks, S, N, sc["depth"], [0, 1, 2], [(1, 2), (0, 7), (2, 0)], _k4(3))
+    # the crop index is in the key: equal ranks are not chosen for all three crops
+    ranks = [np.searchsorted(masks[b].nonzero()[0], ch[b]) for b in range(3)]
+    assert not (np.array_equal(ranks[0], ranks[1]) and np.array_equal(ranks[1], ranks[2]))
+
+
+@pytest.mark.parametrize("seed,crop,pos,ranks", [(185, 0, 791, (1814, 6064)), (59, 1, 4835, (607, 3670))])
+def test_choose_tie_takes_the_lower_rank(dev, seed, crop, pos, ranks):
+    """Two of the crop's 9000 keys are equal (tests/test_draws_ref_host.py asserts the fixture) and sit at sorted
+    positions pos - 1 and pos: N = pos takes the lower rank only, N = pos + 1 both, N = pos - 1 neither.
+    S = 95: 9025 pixels, so the last 1024-pixel chunk of the block's scan is partial."""
+    S, B = 95, crop + 1
+    keys = D.choose_keys(seed, 0, crop, 9000)
+    assert keys[ranks[0]] == keys[ranks[1]]
+    sc = _scene(B, S, S + 1, seed=seed)
+    masks = _masks([9000] * B, S, seed=seed)
+    cand = masks[crop].nonzero()[0]
+    lo, hi = cand[ranks[0]], cand[ranks[1]]
+    for N, want in [(pos, (True, False)), (pos + 1, (True, True)), (pos - 1, (False, False))]:
+        ch = _choose_exact(dev, masks, S, N, sc["depth"], list(range(B)), [(0, 1)] * B, _k4(B), seed=seed,
+                           stream_id=0)[crop]
+        assert (bool(np.isin(lo, ch)), bool(np.isin(hi, ch))) == want, N
+
+
+def test_choose_wrap_and_empty(dev):
+    """count = 1 and 7 (the padding wraps 50 and 7 times), count == N, count == N + 1 (the smallest subset
+    case), and an empty crop between them: that crop is all zeros with count 0, its neighbours unaffected.
+    S*S = 81 < 1024: a single partial chunk."""
+    S, N = 9, 50
+    counts = [1, 7, 50, 0, 51, 20]
+    B = len(counts)
+    sc = _scene(2, S + 4, S + 6, seed=1)
+    masks = _masks(counts, S, seed=2)
+    ch = _choose_exact(dev, masks, S, N, sc["depth"], [0, 1, 0, 1, 0, 1], [(b % 5, b) for b in range(B)], _k4(B))
+    one = masks[0].nonzero()[0]
+    assert (ch[0] == one[0]).all()
+    seven = masks[1].nonzero()[0]
+    assert np.array_equal(ch[1], np.tile(seven, 8)[:N])
+    assert np.array_equal(ch[2], masks[2].nonzero()[0])
+    assert (ch[3] == 0).all()
+    assert len(ch[4]) == N and np.isin(ch[4], masks[4].nonzero()[0]).all() and np.all(np.diff(ch[4]) > 0)
+
+
+def test_choose_geometry(dev):
+    """depth_scale = 1000, a different K4 per crop, frame = [2, 0, 2] (repeated, out of order), the last crop
+    flush with the frame's last row and column; subset, wrap and full crops. Then S = 1."""
+    S, N, H, W = 33, 300, 40, 47
+    sc = _scene(3, H, W, seed=5)
+    depth = (sc["depth"] * 1000).astype(np.float32)
+    masks = _masks([800, 120, 1089], S, seed=6)
+    _choose_exact(dev, masks, S, N, depth, [2, 0, 2], [(0, 0), (3, 9), (H - S, W - S)], _k4(3), depth_scale=1000.0)
+    m1 = np.array([[1], [0], [1]], np.uint8)
+    ch = _choose_exact(dev, m1, 1, 3, depth, [2, 0, 2], [(H - 1, W - 1), (5, 5), (0, 0)], _k4(3), depth_scale=1000.0)
+    assert (ch == 0).all()
+
+
+def test_choose_stream_ids(dev):
+    """Stream ids 0, 1 and 65534 (the range's ends) draw pairwise different subsets, each the restatement's;
+    ids outside 0 .. 65534 are refused before any launch (they would repeat another id's keys)."""
+    S, N = 33, 100
+    sc = _scene(2, S, S, seed=8)
+    masks = _masks([1089, 600], S, seed=9)
+    args = (sc["depth"], [1, 0], [(0, 0), (0, 0)], _k4(2))
+    draws = [_choose_exact(dev, masks, S, N, *args, seed=77, stream_id=sid) for sid in (0, 1, 65534)]
+    for i in range(3):
+        for j in range(i):
+            assert not np.array_equal(draws[i][0], draws[j][0]) and not np.array_equal(draws[i][1], draws[j][1])
+    for sid in (-1, 65535, 65536, 2 ** 31 - 1, -(2 ** 31)):
+        st, out, _ = _choose_call(dev, masks, S, N, *args, 1.0, 77, sid)
+        torch.cuda.synchronize()
+        assert st == ESHAPE and all(o.untouched() for o in out.values()), sid
+
+
+def test_choose_rejects(dev):
+    """Sizes out of range KRRN_ESHAPE, a null pointer KRRN_EARG; nothing is launched, the outputs keep their
+    sentinel."""
+    S, N = 9, 20
+    sc = _scene(1, 12, 14, seed=3)
+    masks = _masks([30], S, seed=4)
+    good = dict(masks=masks, S=S, N=N, depth=sc["depth"], frame=[0], rc=[(0, 0)], k4=_k4(1), depth_scale=1.0,
+                seed=1, stream_id=0)
+    big = _masks([30], 13, seed=4)
+    for change in [dict(masks=big, S=13), dict(masks=_masks([30], 15, seed=4), S=15, depth=_scene(1, 16, 14, 3)["depth"]),
+                   dict(N=0), dict(depth_scale=0.0), dict(S=0)]:
+        st, out, _ = _choose_call(dev, **{**good, **change})
+        torch.cuda.synchronize()
+        assert st == ESHAPE and all(o.untouched() for o in out.values()), change.keys()
+    st, out, ins = _choose_call(dev, **good)
+    torch.cuda.synchronize()
+    assert st == 0
+    fresh = {k: Guarded(dev, v.shape, v.full.dtype) for k, v in out.items()}
+    ptrs = [ins[0].data_ptr(), ins[1].data_ptr(), ins[2].data_ptr(), ins[3].data_ptr(), ins[4].data_ptr(),
+            ins[5].data_ptr(), fresh["choose"].ptr, fresh["cloud"].ptr, fresh["xmap"].ptr, fresh["ymap"].ptr,
+            fresh["count"].ptr]
+    for i in range(len(ptrs)):
+        p = [P(0) if j == i else P(v) for j, v in enumerate(ptrs)]
+        st = _lib.lib().krrn_choose_points(p[0], 1, S, N, p[1], 12, 14, p[2], p[3], p[4], 1.0, p[5], 0, p[6], p[7],
+                                           p[8], p[9], p[10], stream_ptr(dev))
+        assert st == EARG, i
+    torch.cuda.synchronize()
+    assert all(o.untouched() for o in fresh.values())
+
+
+def _crop_call(dev, sc, obj_mask, frame, rc, S, B=None, null=None):
+    F, H, W = sc["depth"].shape
+    B = len(frame) if B is None else B
+    ins = [_dev(dev, sc["rgb"]), _dev(dev, sc["depth"]), _dev(dev, sc["mask_label"]),
+           _dev(dev, obj_mask) if obj_mask is not None else None, _dev(dev, np.asarray(frame, np.int32)),
+           _dev(dev, np.asarray(rc, np.int32))]
+    nb = max(len(frame), 1)
+    img, mask = Guarded(dev, (nb, 3, S, S), torch.float32), Guarded(dev, (nb, S * S), torch.uint8)
+    p = [P(t.data_ptr()) if t is not None else P(0) for t in ins] + [P(img.ptr), P(mask.ptr)]
+    if null is not None:
+        p[null] = P(0)
+    st = _lib.lib().krrn_crop_inputs_u8(p[0], p[1], p[2], p[3], F, H, W, p[4], p[5], B, S, p[6], p[7],
+                                        stream_ptr(dev))
+    torch.cuda.synchronize()
+    return st, img, mask
+
+
+@pytest.mark.parametrize("with_obj", [True, False])
+def test_crop_inputs_indirect_edge_obj_mask(dev, with_obj):
+    """frame = [2, 0, 2], the last crop flush with the frame's last row and column, an obj_mask with zeros inside
+    every crop (or NULL), S*S = 1089 (no multiple of the 256-pixel block): img and mask bit for bit."""
+    S, H, W = 33, 40, 47
+    sc = _scene(3, H, W, seed=11)
+    obj = (np.random.default_rng(12).random((3, H, W)) < 0.7).astype(np.uint8) if with_obj else None
+    frame, rc = [2, 0, 2], [(0, 0), (3, 9), (H - S, W - S)]
+    st, img, mask = _crop_call(dev, sc, obj, frame, rc, S)
+    assert st == 0
+    gi, gm = img.get(), mask.get()
+    for b, (f, (rmin, cmin)) in enumerate(zip(frame, rc)):
+        ri, rm = io.crop_inputs(sc["rgb"][f], sc["depth"][f], sc["mask_label"][f], rmin, cmin, S,
+                                obj_mask=obj[f] if with_obj else None)
+        assert np.array_equal(gi[b].view(np.uint32), ri.view(np.uint32)), b
+        assert np.array_equal(gm[b].reshape(S, S), rm.astype(np.uint8)), b
+        if with_obj:
+            inside = obj[f][rmin:rmin + S, cmin:cmin + S]
+            assert (inside == 0).any() and (rm & (inside == 0)).sum() == 0
+
+
+def test_crop_inputs_rejects(dev):
+    sc = _scene(1, 12, 14, seed=13)
+    for S, B in [(13, None), (15, None), (9, 65536), (0, None), (9, 0)]:
+        st, img, mask = _crop_call(dev, _scene(1, 16, 14, 13) if S == 15 else sc, None, [0], [(0, 0)], S, B=B)
+        assert st == ESHAPE and img.untouched() and mask.untouched(), (S, B)
+    for null in (0, 1, 2, 4, 5, 6, 7):  # obj_mask (3) may be NULL
+        st, img, mask = _crop_call(dev, sc, np.ones((1, 12, 14), np.uint8), [0], [(0, 0)], 9, null=null)
+        assert st == EARG and img.untouched() and mask.untouched(), null
