@@ -623,6 +623,42 @@ int krrn_bop_mssd_mspd_f32(const float* verts, int Vtot, const int* vert_range, 
                            const double* syms, int NStot, const int* sym_range, int B, double* ws, double* mssd,
                            double* mspd, int* sym_idx, void* stream);
 
+/* Pose verification by render-and-compare: C candidate poses per crop scored against the observed depth frame
+ * and the detector's mask, without a ground-truth pose, and the best one selected. verts / faces / face_range /
+ * K4 / depth / frame / depth_scale as krrn_bop_vsd_f32; R f64 [B][C][9], t f64 [B][C][3], 1 <= C <= 8; mask u8
+ * [F][H][W] (optional) the detector's mask frames (any non-zero byte is set); box int32 [B][4] (optional) =
+ * (rmin, rmax, cmin, cmax) of the crop: rows [rmin, rmax), cols [cmin, cmax), clipped to the frame, NULL = the
+ * whole frame; tau f64 [B] metres. For crop b and candidate c over the integer pixels p = (col, row) of the H x W
+ * frame, in f64 without FMA contraction:
+ *   m(p)    = D(p) ray where D(p) > 0, else 0: D the depth of the mesh rendered under (R[b][c], t[b][c]) exactly
+ *             as VSD renders (the same device function, near plane, strict < and lowest-face tie), ray as above
+ *   o(p)    = the observed distance exactly as VSD's obs: 0 for a hole, a non-positive or NaN sample, or a frame
+ *             index outside [0, F)
+ *   evid(p) = mask[frame[b]][row][col] != 0 && o > 0 && p inside the crop's box; a NULL mask gives no evidence
+ *             anywhere. It does not depend on the candidate.
+ *   diff    = m - o, where m > 0 and o > 0
+ *   claim   = m > 0 && o > 0 && !(diff > tau[b])   (the render says the object's surface is seen here; a pixel
+ *             with something more than tau in front of it is occluded and neutral)
+ *   both    = claim && evid;   inter = claim && evid && fabs(diff) <= tau[b]
+ * counts int32 [B][C][6] = #(m > 0) "render", #claim, #evid, #both, #inter, union = claim + evid - both.
+ *   score[b][c] = union > 0 ? (double)inter / (double)union : 0.0   (f64 [B][C]: a depth-aware IoU between what
+ *                 the pose claims is visible and where the detector's mask has depth)
+ *   best[b]     = the lowest c with the largest score (strict > walking c upward); 0 when every score is 0
+ * A NaN or behind-the-camera pose renders nothing and scores 0, so a failed solver never wins against a sane
+ * candidate. R_sel f32 [B][9] / t_sel f32 [B][3] (each optional) = candidate best[b]'s pose rounded to f32. All
+ * sums are integer atomicAdd over the tiles, so the result is deterministic and a (crop, candidate) pair's does
+ * not depend on the batch or on the other candidates, bit for bit. ws: krrn_pose_score_ws(B, C) ints (the
+ * candidates' projected bounding boxes; a tile outside the crop's box and all of them does no work). Host checks,
+ * before any HIP call: null pointer (mask, box, R_sel, t_sel exempt) or overlapping buffers KRRN_EARG; C outside
+ * 1..8, B, Vtot, F, H, W < 1, Ftot < 0, depth_scale not > 0 KRRN_ESHAPE. frame, face_range and box are device
+ * memory and guarded by the kernel as in VSD. */
+int krrn_pose_score_ws(int B, int C, long long* n_ints);
+int krrn_pose_score_f32(const float* verts, int Vtot, const int* faces, int Ftot, const int* face_range,
+                        const double* R, const double* t, int C, const float* K4, const float* depth,
+                        const unsigned char* mask, int F, int H, int W, const int* frame, const int* box,
+                        double depth_scale, const double* tau, int B, int* ws, int* counts, double* score,
+                        int* best, float* R_sel, float* t_sel, void* stream);
+
 /* BPnP forward (lib/network/dnn/BPnP.py:43-44, cv2.solvePnP(SOLVEPNP_ITERATIVE,
  * useExtrinsicGuess=True)): Levenberg-Marquardt on sum_i ||pi(z_i; y) - x_i||^2 per crop, f64,
  * from y_init. pts2d [B][n][2] pixels; pts3d [n][3] shared (z_per_crop = 0) or [B][n][3];

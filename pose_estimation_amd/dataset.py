@@ -23,7 +23,8 @@ mask_label * mask_depth (documented deviation) and the loss keys are absent; wit
 maps are rendered on the GPU from the PLY's faces, the GT pose and K (raster.py), the mask is the
 reference's label * obj * depth, and every batch carries xyz, normal, region, mask, multi_cls_mask,
 mask_obj, region_point, coordinate_choosed and depth_render. `meshes=True` only loads the meshes
-(faces, all vertices, symmetry sets) for the BOP pose errors (bop.py): `batch(idx, device, bop=True)`.
+(faces, all vertices, symmetry sets) for the BOP pose errors (bop.py): `batch(idx, device, bop=True)`, and for
+pose verification (verify.py, pose.select_pose): `batch(idx, device, verify=True)`.
 
 `layout="bop"` reads `root` as a tree in BOP's own layout instead (bop_scene.py: several instances per image, a
 camera matrix and a depth scale per image, models_info.json; LM-O and its kin) and feeds the same kernels:
@@ -536,7 +537,7 @@ class PoseDataset(torch.utils.data.Dataset):
                                    "region_point": region_point}
         return self._dev_mesh[key]
 
-    def batch(self, indices: Sequence[int], device, bop: bool = False) -> Dict[str, torch.Tensor]:
+    def batch(self, indices: Sequence[int], device, bop: bool = False, verify: bool = False) -> Dict[str, torch.Tensor]:
         """The eval keys of batchdataset.py:730-771 for `indices` (one crop size), collated. With gt_maps
         also the per-pixel GT of :755-759 (xyz, normal, region, mask, multi_cls_mask), mask_obj,
         region_point, coordinate_choosed and depth_render: the object's mesh is rendered under the GT pose
@@ -544,9 +545,12 @@ class PoseDataset(torch.utils.data.Dataset):
         raster.finish_maps applies the loader's masking. bop=True (needs meshes; ValueError otherwise) adds
         what bop.bop_errors reads: bop_depth [F, H, W] the observed depth frames (metres), bop_frame int32 [B]
         each crop's frame, bop_face_range / bop_vert_range / bop_sym_range int32 [B, 2] its object's ranges in
-        the dataset's resident meshes and symmetry sets. The other keys are unchanged."""
+        the dataset's resident meshes and symmetry sets. The other keys are unchanged. verify=True implies the
+        bop=True keys and adds verify_mask u8 [F, H, W], the mask_label frames the crops were cut from (the
+        rendered ones with masks="render"), for pose.select_pose; the crop's box is the `bbox` key."""
         device = torch.device(device)
         idx = list(indices)
+        bop = bop or verify
         if bop and not self.meshes:
             raise ValueError("batch(..., bop=True) needs the objects' meshes: build the dataset on a LineMOD tree "
                              "with meshes=True (or gt_maps=True); root=None serves synthetic frames, which have none")
@@ -615,6 +619,8 @@ class PoseDataset(torch.utils.data.Dataset):
             out.update({"bop_depth": fr["depth"], "bop_frame": h2d(torch.tensor(fidx, dtype=torch.int32), device),
                         "bop_face_range": rng("range"), "bop_vert_range": rng("vrange"),
                         "bop_sym_range": rng("srange")})
+        if verify:
+            out["verify_mask"] = fr["mask_label"]
         return out
 
     def __getitem__(self, i: int) -> Dict[str, torch.Tensor]:

@@ -38,7 +38,7 @@ from .dataset import PoseDataset
 from .krrn import KRRN
 from .loss import map_losses
 from .metric import Metric, add_metric, rt_errors
-from .pose import get_pose, get_pose_umeyama, refine_pose_icp
+from .pose import get_pose, get_pose_umeyama, refine_pose_icp, select_pose
 
 ROT_THR_DEG = 5.0     # trainer.py:156
 TRANS_THR_M = 0.05    # trainer.py:157
@@ -51,6 +51,9 @@ REC = ("crop", "cls", "add_b", "r_b", "t_b", "add_f", "r_f", "t_f", "l_xyz", "l_
 _R = {k: i for i, k in enumerate(REC)}
 # per-crop record of eval_records(poses=True) (f64): the scored pose, R row-major, t in metres
 POSE_REC = ("crop",) + tuple(f"r{k}" for k in range(9)) + ("tx", "ty", "tz")
+# per-crop record of eval_records(select="depth") (f64): the candidate that pose.select_pose kept, its score and the
+# two counts the score is made of
+SEL_REC = ("crop", "cand", "score", "inter", "union", "valid")
 # what one evaluated batch leaves on the device until the epoch's single read-back (idx: its crop indices, on
 # the host; pred_t / add_f are None without opt_pose, lc without GT maps)
 _Batch = namedtuple("_Batch", "idx cls_id target_r target_t base_r base_t pred_t fin_r add_b add_f lc")
@@ -66,7 +69,8 @@ def _batches(buckets: Dict[int, List[int]], bs: int):
 @torch.no_grad()
 def eval_records(model: KRRN, dataset: PoseDataset, indices: Dict[int, List[int]], bs: int, device,
                  opt_pose: bool = True, with_loss: bool = True, pose_solver: str = "pnp",
-                 refine: Optional[str] = None, bop: bool = False, poses: bool = False):
+                 refine: Optional[str] = None, bop: bool = False, poses: bool = False,
+                 select: Optional[str] = None):
     """Run the eval path over {S: [crop indices]} in batches of <= bs; returns f64 [n, len(REC)]
     (rows in the order evaluated). Every batch's inputs, forward, pose and ADD(-S) are queued on
     the device without a host round trip; the per-crop records are read back once at the end (the
@@ -95,15 +99,31 @@ def eval_records(model: KRRN, dataset: PoseDataset, indices: Dict[int, List[int]
     poses: also return an f64 [n, len(POSE_REC)] table in the same row order: crop, R row-major and t in metres of
     the pose that test_dis scores (the final pose with opt_pose, else the base pose). It is read back
     in the epoch's single read-back (the tensors are the ones the records are made from). The return value then
-    ends with it: (records, poses) or (records, bop table, poses)."""
+    ends with it: (records, poses) or (records, bop table, poses).
+
+    select: None, or "depth" (needs opt_pose and a dataset with meshes; ValueError otherwise): the final pose is
+    chosen per crop by pose.select_pose (render-and-compare against the observed depth and the crop's mask_label;
+    include/krrn_hip.h: krrn_pose_score_f32) among, in priority order, 0 the pose test_dis scores today (fin_r,
+    pred_t), the ICP-refined one with refine="icp"; 1 the base pose; and with refine="icp" also 2 the unrefined
+    (PnP R, raw pred_t) and 3 the unrefined base pose. The winner replaces the final pose for add_f, r_f / t_f,
+    the BOP errors and the pose table; the base columns are untouched. One more launch per batch on the pose
+    stream, no host round trip. The return value then ends with an f64 [n, len(SEL_REC)] table in the same row
+    order, read back in the epoch's single read-back. With select=None nothing changes."""
     if pose_solver not in ("pnp", "umeyama"):
         raise ValueError(f"pose_solver must be 'pnp' or 'umeyama', got {pose_solver!r}")
     if refine not in (None, "icp"):
         raise ValueError(f"refine must be None or 'icp', got {refine!r}")
+    if select not in (None, "depth"):
+        raise ValueError(f"select must be None or 'depth', got {select!r}")
+    if select and not opt_pose:
+        raise ValueError("select='depth' chooses the final pose: it needs opt_pose=True")
+    if select and not getattr(dataset, "meshes", False):
+        raise ValueError("select='depth' renders the objects' meshes: it needs a dataset with meshes=True")
     solve_pose = get_pose if pose_solver == "pnp" else get_pose_umeyama
     metric = Metric(dataset.sym_obj)
     pending = []
     bop_pending = []   # per batch, with bop: bop_errors' dict of device tensors
+    sel_pending = []   # per batch, with select: select_pose's dict of device tensors
     batches = list(_batches(indices, bs))
     device = torch.device(device)
     dia = torch.tensor(dataset.diameter, dtype=torch.float32).to(device) if refine else None  # [classes], metres
@@ -114,7 +134,10 @@ def eval_records(model: KRRN, dataset: PoseDataset, indices: Dict[int, List[int]
     def build(j):
         side.wait_stream(main)  # the inputs' pinned staging and allocations follow earlier work
         with torch.cuda.stream(side):
-            d = dataset.batch(batches[j][1], device, bop=True) if bop else dataset.batch(batches[j][1], device)
+            if select:
+                d = dataset.batch(batches[j][1], device, verify=True)
+            else:
+                d = dataset.batch(batches[j][1], device, bop=True) if bop else dataset.batch(batches[j][1], device)
             ev = torch.cuda.Event()
             ev.record(side)
         return d, ev
@@ -148,14 +171,21 @@ def eval_records(model: KRRN, dataset: PoseDataset, indices: Dict[int, List[int]
             with torch.cuda.stream(pstr):
                 base_r, base_t = solve_pose({"xyz": xyz}, data)
                 fin_r = base_r
+                r0, t0, raw_t = base_r, base_t, pred_t  # the solver's and TBase's own, before any refinement
                 if refine:
                     d = dia[data["cls_id"].reshape(B)]
-                    r0 = base_r
                     base_r, base_t = refine_pose_icp(r0, base_t.reshape(B, 3), data, diameter=d)
                     if opt_pose:
                         fin_r, pred_t = refine_pose_icp(r0, pred_t, data, diameter=d)
                 add_b = add_metric(base_r, base_t.reshape(B, 3), data["model_points"], data["target"],
                                    data["cls_id"], metric.sys)
+                if select:
+                    cands = [(fin_r, pred_t), (base_r, base_t.reshape(B, 3))]
+                    if refine:
+                        cands += [(r0, raw_t), (r0, t0.reshape(B, 3))]
+                    sel = select_pose(cands, data, dataset)
+                    fin_r, pred_t = sel["R"], sel["t"]
+                    sel_pending.append(sel)
                 add_f = None
                 if opt_pose:
                     # reg = final = (PnP R, TBase t) (trainer.py:198-201)
@@ -170,16 +200,17 @@ def eval_records(model: KRRN, dataset: PoseDataset, indices: Dict[int, List[int]
         model.return_views = views
     main.wait_stream(pstr)
     for p in pending:  # made on the pose stream, read back on the caller's
-        for t in (p.base_r, p.base_t, p.add_b, p.add_f) + ((p.pred_t, p.fin_r) if refine else ()):
+        for t in (p.base_r, p.base_t, p.add_b, p.add_f) + ((p.pred_t, p.fin_r) if refine or select else ()):
             if t is not None:
                 t.record_stream(main)
-    for e in bop_pending:
+    for e in bop_pending + sel_pending:
         for t in e.values():
             t.record_stream(main)
     if not pending:
         empty = (torch.zeros((0, len(REC)), dtype=torch.float64),)
         empty += (torch.zeros((0, len(BOP_REC)), dtype=torch.float64),) if bop else ()
         empty += (torch.zeros((0, len(POSE_REC)), dtype=torch.float64),) if poses else ()
+        empty += (torch.zeros((0, len(SEL_REC)), dtype=torch.float64),) if select else ()
         return empty if len(empty) > 1 else empty[0]
     # one read-back and one vectorised host pass for the whole epoch: per batch, the rotation /
     # translation errors' six small copies and ~60 CPU ops ran after the GPU had drained (a serial
@@ -200,27 +231,37 @@ def eval_records(model: KRRN, dataset: PoseDataset, indices: Dict[int, List[int]
     rec[:, _R["r_b"]], rec[:, _R["t_b"]] = rt_errors(base_r, cat("base_t", 3), tr, tt)
     if opt_pose:
         rec[:, _R["add_f"]] = cat("add_f", 1).reshape(n).cpu().numpy()
-        fin_r = cat("fin_r", 9) if refine else base_r
+        fin_r = cat("fin_r", 9) if refine or select else base_r
         rec[:, _R["r_f"]], rec[:, _R["t_f"]] = rt_errors(fin_r, cat("pred_t", 3), tr, tt)
     prec = None
     if poses:
         prec = np.zeros((n, len(POSE_REC)), dtype=np.float64)
         prec[:, 0] = rec[:, _R["crop"]]
         if opt_pose:
-            prec[:, 1:10] = (cat("fin_r", 9) if refine else base_r).double().cpu().numpy()
+            prec[:, 1:10] = (cat("fin_r", 9) if refine or select else base_r).double().cpu().numpy()
             prec[:, 10:13] = cat("pred_t", 3).double().cpu().numpy()
         else:
             prec[:, 1:10] = base_r.double().cpu().numpy()
             prec[:, 10:13] = cat("base_t", 3).double().cpu().numpy()
+    tail = (torch.from_numpy(prec),) if poses else ()
+    if select:
+        srec = np.zeros((n, len(SEL_REC)), dtype=np.float64)
+        best = torch.cat([e["best"] for e in sel_pending]).cpu().numpy().astype(np.int64)
+        score = np.concatenate([e["score"].cpu().numpy() for e in sel_pending])      # [n, C]: one C per epoch
+        counts = np.concatenate([e["counts"].cpu().numpy() for e in sel_pending])    # [n, C, 6]
+        rows = np.arange(n)
+        srec[:, 0], srec[:, 1], srec[:, 2], srec[:, -1] = rec[:, _R["crop"]], best, score[rows, best], 1.0
+        srec[:, 3], srec[:, 4] = counts[rows, best, 4], counts[rows, best, 5]
+        tail += (torch.from_numpy(srec),)
     if not bop:
-        return (torch.from_numpy(rec), torch.from_numpy(prec)) if poses else torch.from_numpy(rec)
+        return (torch.from_numpy(rec),) + tail if tail else torch.from_numpy(rec)
     T = len(TAUS)
     brec = np.zeros((n, len(BOP_REC)), dtype=np.float64)
     brec[:, 0], brec[:, 1], brec[:, -1] = rec[:, _R["crop"]], rec[:, _R["cls"]], 1.0
     brec[:, 2:2 + T] = torch.cat([e["vsd"] for e in bop_pending]).cpu().numpy()
     brec[:, 2 + T] = torch.cat([e["mssd"] for e in bop_pending]).cpu().numpy()
     brec[:, 3 + T] = torch.cat([e["mspd"] for e in bop_pending]).cpu().numpy()
-    return (torch.from_numpy(rec), torch.from_numpy(brec)) + ((torch.from_numpy(prec),) if poses else ())
+    return (torch.from_numpy(rec), torch.from_numpy(brec)) + tail
 
 
 def fold_records(records: torch.Tensor, objlist: Sequence[int], diameter: Sequence[float], opt_pose: bool,
@@ -295,7 +336,7 @@ def gather_epoch_records(local: torch.Tensor, shard_sizes: Sequence[int], device
 def test_epoch(model: KRRN, dataset: PoseDataset, bs: int = 64, device=None, opt_pose: bool = True,
                criterion=None, world: Optional[int] = None, rank: Optional[int] = None,
                group=None, pose_solver: str = "pnp", refine: Optional[str] = None,
-               bop: bool = False, bop_csv: Optional[str] = None) -> Dict[str, object]:
+               bop: bool = False, bop_csv: Optional[str] = None, select: Optional[str] = None) -> Dict[str, object]:
     """Trainer.test_epoch over `dataset`. world/rank default to the initialised process group
     (1/0 without one). `criterion` enables the per-crop map-loss terms (dis_xyz / dis_mask /
     dis_normal) when the batches carry GT maps, i.e. for a PoseDataset built with gt_maps=True (a
@@ -307,7 +348,11 @@ def test_epoch(model: KRRN, dataset: PoseDataset, bs: int = 64, device=None, opt
     `bop_csv` (needs a dataset with layout="bop": the rows carry its scene and image ids) writes every crop's scored
     pose as BOP's result CSV (bop_scene.write_results; t in millimetres) in crop order. The pose table is gathered
     like the records and only rank 0 writes. score is 1.0 for every row: there is one estimate per target, so
-    nothing ranks on it; time is -1 (not measured per image). The returned dict is unchanged."""
+    nothing ranks on it; time is -1 (not measured per image). The returned dict is unchanged.
+    `select` as in eval_records: "depth" chooses every crop's final pose among the epoch's candidates by
+    render-and-compare, and adds one key, "select": {"picked": {candidate index: crops}, "mean_score": the mean of
+    the kept candidates' scores in crop order}; the final / reg keys, "bop" and the CSV's poses are then the chosen
+    pose's, and the CSV's score column is its score (a confidence in [0, 1]). The base keys do not change."""
     device = torch.device(device) if device is not None else next(model.parameters()).device
     if world is None:
         world = dist.get_world_size(group) if dist.is_initialized() else 1
@@ -321,8 +366,10 @@ def test_epoch(model: KRRN, dataset: PoseDataset, bs: int = 64, device=None, opt
         raise ValueError("bop_csv writes BOP's scene / image ids: it needs a PoseDataset with layout='bop'")
     local = eval_records(model, dataset, mine, bs, device, opt_pose=opt_pose, with_loss=criterion is not None,
                          pose_solver=pose_solver, refine=refine, **({"bop": True} if bop else {}),
-                         **({"poses": True} if bop_csv else {}))
-    local_bop = local_pose = None
+                         **({"poses": True} if bop_csv else {}), **({"select": select} if select else {}))
+    local_bop = local_pose = local_sel = None
+    if select:
+        local, local_sel = (local[:-1] if len(local) > 2 else local[0]), local[-1]
     if bop_csv:
         local, local_pose = local[:-1] if bop else local[0], local[-1]
         # gather_epoch_records marks pad rows by a last column `valid` = 0
@@ -336,6 +383,15 @@ def test_epoch(model: KRRN, dataset: PoseDataset, bs: int = 64, device=None, opt
     if bop:  # a record table of its own, gathered by the same mechanism
         allbop = gather_epoch_records(local_bop, shard_sizes, device, group) if world > 1 else local_bop
         out["bop"] = fold_bop(allbop, dataset.objlist, dataset.diameter, getattr(dataset, "frame_hw", (0, FRAME_W))[1])
+    conf = {}
+    if select:
+        allsel = gather_epoch_records(local_sel, shard_sizes, device, group) if world > 1 else local_sel
+        tab = allsel.numpy()
+        tab = tab[tab[:, -1] > 0]
+        tab = tab[np.argsort(tab[:, 0], kind="stable")]
+        picked = {int(c): int((tab[:, 1] == c).sum()) for c in sorted(set(tab[:, 1].tolist()))}
+        out["select"] = {"picked": picked, "mean_score": float(np.cumsum(tab[:, 2])[-1]) / len(tab) if len(tab) else 0.0}
+        conf = {int(r[0]): float(r[2]) for r in tab}
     if bop_csv:
         allpose = gather_epoch_records(local_pose, shard_sizes, device, group) if world > 1 else local_pose
         if rank == 0:
@@ -345,7 +401,7 @@ def test_epoch(model: KRRN, dataset: PoseDataset, bs: int = 64, device=None, opt
             rows = []
             for row in tab:
                 it = dataset.tree.items[int(row[0])]
-                rows.append({"scene_id": it["scene"], "im_id": it["im"], "obj_id": it["obj"], "score": 1.0,
+                rows.append({"scene_id": it["scene"], "im_id": it["im"], "obj_id": it["obj"], "score": conf.get(int(row[0]), 1.0),
                              "R": row[1:10], "t": row[10:13] * 1000.0, "time": -1.0})
             write_results(bop_csv, rows)
     if world > 1:

@@ -19,7 +19,7 @@ from typing import Dict, Optional
 import torch
 
 from .runtime import Immediate, Plan, RngStream, device_seed, h2d, ptr
-from . import icp, umeyama
+from . import icp, umeyama, verify
 
 NUM_POINTS = 256
 N_HYP = 100
@@ -158,6 +158,30 @@ def refine_pose_icp(R: torch.Tensor, t: torch.Tensor, data, diameter=None, max_d
     cloud = h2d(data["cloud"].reshape(B, -1, 3), dev, torch.float32)
     mp = h2d(data["model_points"].reshape(B, -1, 3), dev, torch.float32)
     return icp.refine(R, t.reshape(B, 3), cloud, mp, max_dist, max_iter, tol, min_pairs, return_info)
+
+
+def select_pose(cands, data, dataset, tau=None):
+    """The best of several pose candidates per crop, by render-and-compare against the observed depth and the
+    detector's mask (verify.score_poses; include/krrn_hip.h: krrn_pose_score_f32). `cands` is a list of 1 .. 8
+    (R [B, 3, 3], t [B, 3]) GPU tensor pairs in priority order (ties keep the earlier one); `data` is
+    dataset.batch(indices, device, verify=True); tau metres (a float or [B]; default verify.TAU). Returns {"R" f32
+    [B, 3, 3], "t" f32 [B, 3]: the winner's pose, "best" int32 [B], "score" f64 [B, C], "counts" int32 [B, C, 6]}.
+    Queued on the current stream, nothing is read back: the candidates may come straight from their solvers."""
+    if "verify_mask" not in data:
+        raise ValueError("select_pose needs a batch made with dataset.batch(indices, device, verify=True)")
+    if not cands:
+        raise ValueError("select_pose needs at least one candidate")
+    dev = cands[0][1].device
+    if dev.type != "cuda":
+        raise RuntimeError("select_pose runs on the HIP path only (GPU tensors)")
+    B = cands[0][1].reshape(-1, 3).shape[0]
+    R = torch.stack([r.reshape(B, 3, 3).to(torch.float64) for r, _ in cands], 1)
+    t = torch.stack([x.reshape(B, 3).to(torch.float64) for _, x in cands], 1)
+    mesh = dataset._mesh_for(dev)
+    out = verify.score_poses(mesh["verts"], mesh["faces"], data["bop_face_range"], R, t, data["intrinsic"],
+                             data["bop_depth"], data["bop_frame"], verify.TAU if tau is None else tau,
+                             mask=data["verify_mask"], box=data["bbox"].to(torch.int32))
+    return {"R": out["R"], "t": out["t"], "best": out["best"], "score": out["score"], "counts": out["counts"]}
 
 
 def add_icp_ops(plan: Plan, R: torch.Tensor, t: torch.Tensor, cloud: torch.Tensor, model: torch.Tensor,
