@@ -29,8 +29,17 @@ import torch
 KORNIA_EPS = 1e-6
 
 
-def angle_axis_to_rotation_matrix(aa: torch.Tensor) -> torch.Tensor:
-    """[B, 3] -> [B, 3, 3] (kornia's published formula, see the module docstring)."""
+def angle_axis_to_rotation_matrix(aa: torch.Tensor, first_order: bool = False) -> torch.Tensor:
+    """[B, 3] -> [B, 3, 3] (kornia's published formula, see the module docstring).
+
+    first_order=True evaluates the first-order branch I + [w]x alone, for every row. Where
+    theta^2 <= 1e-6 that is the blended value (the mask is 0 there) with the same derivatives, but it
+    can be differentiated at w = 0 exactly, where the blend's unused branch gives NaN through the
+    gradient of sqrt at 0 (0 * inf)."""
+    if first_order:
+        rx, ry, rz = aa[:, 0:1], aa[:, 1:2], aa[:, 2:3]
+        one = torch.ones_like(rx)
+        return torch.cat([one, -rz, ry, rz, one, -rx, -ry, rx, one], dim=1).view(-1, 3, 3)
     theta2 = (aa * aa).sum(-1, keepdim=True)
     theta = torch.sqrt(theta2)
     w = aa / (theta + KORNIA_EPS)
@@ -47,35 +56,36 @@ def angle_axis_to_rotation_matrix(aa: torch.Tensor) -> torch.Tensor:
     return (mask * normal + (1.0 - mask) * taylor).view(-1, 3, 3)
 
 
-def batch_project(P6: torch.Tensor, z: torch.Tensor, K: torch.Tensor) -> torch.Tensor:
+def batch_project(P6: torch.Tensor, z: torch.Tensor, K: torch.Tensor, first_order: bool = False) -> torch.Tensor:
     """BPnP.py:144-159: poses [bs, 6], points [n, 3], K [3, 3] -> pixels [bs, n, 2]."""
     bs, n = P6.shape[0], z.shape[0]
     zh = torch.cat([z, torch.ones(n, 1, dtype=z.dtype)], dim=-1)
-    PM = torch.cat([angle_axis_to_rotation_matrix(P6[:, 0:3]), P6[:, 3:6].reshape(bs, 3, 1)], dim=-1)
+    PM = torch.cat([angle_axis_to_rotation_matrix(P6[:, 0:3], first_order), P6[:, 3:6].reshape(bs, 3, 1)], dim=-1)
     q = zh.matmul(PM.transpose(-2, -1)).matmul(K.t())
     return q[:, :, 0:2] / q[:, :, 2:3]
 
 
-def _f(x: torch.Tensor, y: torch.Tensor, z: torch.Tensor, K: torch.Tensor) -> torch.Tensor:
+def _f(x: torch.Tensor, y: torch.Tensor, z: torch.Tensor, K: torch.Tensor, first_order: bool = False) -> torch.Tensor:
     """The six stationarity functions f_j of one crop (BPnP.py:85-100) as one vector; x, z, K
     flattened."""
     n = x.numel() // 2
-    R = angle_axis_to_rotation_matrix(y[0:3].view(1, 3))[0]
+    R = angle_axis_to_rotation_matrix(y[0:3].view(1, 3), first_order)[0]
     P = torch.cat([R, y[3:6].view(3, 1)], dim=-1)
     q = K.view(3, 3).mm(P).mm(torch.cat([z.view(n, 3), torch.ones(n, 1, dtype=z.dtype)], dim=-1).t())  # [3, n]
     r = x.view(n, 2).t() * q[2:3] - q[0:2]                                                                 # [2, n]
     # coefficients c[i, k, j] = -2 d pi_k(z_i) / d y_j with their graph kept (get_coefs)
     yr = y.view(1, 6).repeat(n, 1)
-    proj = batch_project(yr, z.view(n, 3), K.view(3, 3))                                                  # [n, n, 2]
+    proj = batch_project(yr, z.view(n, 3), K.view(3, 3), first_order)                                     # [n, n, 2]
     eye = torch.eye(n, dtype=z.dtype)
     coefs = torch.stack([-2 * torch.autograd.grad(proj[:, :, k], yr, eye, create_graph=True)[0] for k in range(2)],
                         dim=1)                                                                             # [n, 2, 6]
     return torch.stack([(coefs[:, :, j].t() * r).sum() for j in range(6)])
 
 
-def bpnp_backward(pts2d, P6, pts3d, K, grad_out, dtype=torch.float32):
+def bpnp_backward(pts2d, P6, pts3d, K, grad_out, dtype=torch.float32, first_order: bool = False):
     """BPnP.backward: returns (grad_x [bs, n, 2], grad_z [n, 3], grad_K [3, 3]). pts3d may also be
-    [bs, n, 3] (one set per crop; grad_z then [bs, n, 3])."""
+    [bs, n, 3] (one set per crop; grad_z then [bs, n, 3]). first_order: the rotation's first-order
+    branch alone (angle_axis_to_rotation_matrix), for poses with w = 0 exactly."""
     cv = lambda a: torch.as_tensor(np.asarray(a), dtype=dtype)  # noqa: E731
     x_all, y_all, z_all, K, g_all = cv(pts2d), cv(P6), cv(pts3d), cv(K), cv(grad_out)
     bs, n = x_all.shape[0], x_all.shape[1]
@@ -87,7 +97,8 @@ def bpnp_backward(pts2d, P6, pts3d, K, grad_out, dtype=torch.float32):
         z = z_all[b] if per_crop else z_all
         args = (x_all[b].reshape(-1), y_all[b].clone(), z.reshape(-1), K.reshape(-1))
         with torch.enable_grad():
-            J = torch.autograd.functional.jacobian(_f, args)  # d f / d (x, y, z, K)
+            f = lambda *a: _f(*a, first_order=first_order)  # noqa: E731
+            J = torch.autograd.functional.jacobian(f, args)  # d f / d (x, y, z, K)
         J_fx, J_fy, J_fz, J_fK = (j.reshape(6, -1) for j in J)
         v = -(g_all[b].view(1, 6).mm(torch.inverse(J_fy)))  # -g J_fy^-1
         gx[b] = v.mm(J_fx).view(n, 2)

@@ -23,6 +23,7 @@
 #include <math.h>
 
 #include "krrn_common.h"
+#include "krrn_so3.h"
 
 namespace {
 
@@ -488,38 +489,6 @@ __global__ void bpnp_reduce_kernel(const double* __restrict__ gz_part, const dou
   }
 }
 
-// angle-axis of a rotation matrix (log map; theta near pi from the dominant column of R + I)
-__device__ inline void rot_log(const float* Rf, double (&w)[3]) {
-  double R[3][3];
-#pragma unroll
-  for (int a = 0; a < 3; ++a)
-#pragma unroll
-    for (int b = 0; b < 3; ++b) R[a][b] = (double)Rf[3 * a + b];
-  const double c = fmin(1.0, fmax(-1.0, (R[0][0] + R[1][1] + R[2][2] - 1.0) * 0.5));
-  const double th = acos(c), s = sin(th);
-  const double v[3] = {R[2][1] - R[1][2], R[0][2] - R[2][0], R[1][0] - R[0][1]};
-  if (s > 1e-6) {
-    const double f = th / (2.0 * s);
-#pragma unroll
-    for (int a = 0; a < 3; ++a) w[a] = f * v[a];
-  } else if (c > 0.0) {
-#pragma unroll
-    for (int a = 0; a < 3; ++a) w[a] = 0.5 * v[a];
-  } else {
-    int k = 0;
-#pragma unroll
-    for (int a = 1; a < 3; ++a)
-      if (R[a][a] > R[k][k]) k = a;
-    double nv[3];
-    const double nk = sqrt(fmax(0.0, (R[k][k] + 1.0) * 0.5));
-#pragma unroll
-    for (int a = 0; a < 3; ++a) nv[a] = a == k ? nk : (R[a][k] + R[k][a]) / (4.0 * nk);
-    const double sg = (nv[0] * v[0] + nv[1] * v[1] + nv[2] * v[2]) < 0.0 ? -1.0 : 1.0;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) w[a] = sg * th * nv[a];
-  }
-}
-
 // Levenberg-Marquardt on sum_i ||pi(z_i; y) - x_i||^2, one wave per crop.
 __global__ __launch_bounds__(64) void bpnp_solve_kernel(const float* __restrict__ x2, const float* __restrict__ z3,
                                                         long long z_bs, const float* __restrict__ Kp,
@@ -538,7 +507,7 @@ __global__ __launch_bounds__(64) void bpnp_solve_kernel(const float* __restrict_
   for (int j = 0; j < 6; ++j) y[j] = (double)y0[b * 6 + j];
   if (R0) {
     double w[3];
-    rot_log(R0 + b * 9, w);
+    krrn_rot_log(R0 + b * 9, w);  // krrn_so3.h
 #pragma unroll
     for (int a = 0; a < 3; ++a) y[a] = w[a];
   }
