@@ -100,6 +100,22 @@ def test_host_side_errors():
     # pnp: P < 5 -> KRRN_ESHAPE
     assert lib.krrn_pnp_ransac_f32(fake, 16, fake, 10, fake, 4, fake, fake, fake, fake, fake, fake, 10,
                                    ctypes.c_float(1.0), ctypes.c_double(0.9999), fake, fake, fake, fake, N, 1, N) == -2
+    # pnp: every other refusal, each before any launch. Arguments: xyz, HW, choose, N, sel, P, xmap, ymap, K4, extent,
+    # lfborder, subsets, H, thr, conf, workspace, R, t, inliers, inlier_mask, B, stream
+    def pnp(HW=16, N_=10, P_=5, H=10, conf=0.9999, B=1, null=None):
+        a = [fake, HW, fake, N_, fake, P_, fake, fake, fake, fake, fake, fake, H, ctypes.c_float(1.0),
+             ctypes.c_double(conf), fake, fake, fake, fake, N, B, N]
+        if null is not None:
+            assert a[null] is fake
+            a[null] = N
+        return lib.krrn_pnp_ransac_f32(*a)
+    for bad in (dict(P_=4), dict(P_=1025), dict(H=0), dict(H=4096), dict(N_=0), dict(HW=0), dict(B=0),
+                dict(conf=-0.1), dict(conf=1.1), dict(conf=float("nan"))):
+        assert pnp(**bad) == -2, bad
+    required = [0, 2, 4, 6, 7, 8, 9, 10, 11, 15, 16, 17, 18]  # every pointer but inlier_mask (19) and the stream
+    for i in required:
+        assert pnp(null=i) == -1, i
+    assert pnp(null=0, P_=4) == -1  # a null pointer is reported before a bad shape
     # NCHW 1x1 split form: null weights -> KRRN_EARG; N outside (32, 80] or cin != 128 -> KRRN_ESHAPE;
     # misaligned channel offset -> KRRN_EALIGN
     nchw_x3 = lib.krrn_conv1x1_nchw_x3_f32

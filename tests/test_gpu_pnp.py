@@ -4,6 +4,7 @@ import pytest
 import torch
 
 from oracle import pnp as opnp
+from pnp_cases import cv2_select as _cv2_select, update_niters as _update_niters  # noqa: F401
 from pose_estimation_amd import pose
 
 pytestmark = pytest.mark.gpu
@@ -46,29 +47,6 @@ def _scene(B, N, S, seed, outlier_frac=0.1, noise_px=0.0):
             "y_map_choosed": torch.from_numpy(ym), "intrinsic": torch.from_numpy(np.tile(K4, (B, 1))),
             "extent": torch.from_numpy(np.tile(ext, (B, 1))), "lfborder": torch.from_numpy(np.tile(lfb, (B, 1)))}
     return torch.from_numpy(xyz), data, np.stack(Rs), np.stack(ts)
-
-
-def _update_niters(conf, ep, model_points, max_iters):
-    """cv::RANSACUpdateNumIters (ptsetreg.cpp)."""
-    conf, ep = min(max(conf, 0.0), 1.0), min(max(ep, 0.0), 1.0)
-    num = max(1.0 - conf, np.finfo(np.float64).tiny)
-    denom = 1.0 - (1.0 - ep) ** model_points
-    if denom < np.finfo(np.float64).tiny:
-        return 0
-    num, denom = np.log(num), np.log(denom)
-    return max_iters if (denom >= 0 or -num >= max_iters * (-denom)) else int(np.rint(num / denom))
-
-
-def _cv2_select(cnts, P, conf=np.float32(0.9999)):
-    """ptsetreg.cpp's RANSAC loop over already-scored hypotheses: the selected index."""
-    best, best_cnt, niters, h = -1, 0, len(cnts), 0
-    while h < niters:
-        c = int(cnts[h])
-        if c > max(best_cnt, 4):
-            best, best_cnt = h, c
-            niters = _update_niters(float(conf), (P - c) / P, 5, niters)
-        h += 1
-    return best
 
 
 def test_known_pose_recovery(dev):
@@ -118,16 +96,29 @@ def test_matches_oracle_same_subsets(dev, noise_px, cnt_tol, pose_tol):
 
 def test_ransac_failure_identity(dev):
     # pure noise correspondences: no hypothesis reaches 5 inliers -> R = I, t = 0 (cv2 failure)
-    B, N, S = 2, 300, 40
+    B, N, S, P, H = 2, 300, 40, 256, 100
     xyz, data, _, _ = _scene(B, N, S, 2, outlier_frac=1.0)
     data["x_map_choosed"] = torch.rand(B, N, 1) * 640
     data["y_map_choosed"] = torch.rand(B, N, 1) * 480
-    R, t, info = pose.get_pose({"xyz": xyz.to(dev)}, data, return_info=True)
+    # sel and the subsets from a local generator, so that the oracle can say that both crops fail on them
+    g = torch.Generator().manual_seed(77)
+    sel = torch.stack([torch.randperm(N, generator=g)[:P] for _ in range(B)]).to(torch.int32)
+    subsets = torch.stack([torch.stack([torch.randperm(P, generator=g)[:5] for _ in range(H)])
+                           for _ in range(B)]).to(torch.int32)
+    for b in range(B):
+        s_b = sel[b].long()
+        pix = data["choose"][b, 0, s_b]
+        obj = (xyz[b].reshape(3, -1)[:, pix].double().t() * data["extent"][b] + data["lfborder"][b]).float().numpy()
+        img = np.stack([data["x_map_choosed"][b, s_b, 0].numpy(), data["y_map_choosed"][b, s_b, 0].numpy()], 1)
+        _, _, cnt, mask, best = opnp.pnp_ransac(obj, img, K4, subsets[b].numpy(), 1.0)
+        assert cnt == 0 and best == -1 and not mask.any(), (b, cnt, best)
+    R, t, info = pose.get_pose({"xyz": xyz.to(dev)}, data, sel=sel, subsets=subsets, return_info=True)
     torch.cuda.synchronize()
     for b in range(B):
-        if int(info["inliers"][b]) == 0:
-            assert torch.allclose(R[b].cpu(), torch.eye(3))
-            assert torch.all(t[b].cpu() == 0)
+        assert int(info["inliers"][b]) == 0
+        assert not info["mask"][b].any()
+        assert torch.equal(R[b].cpu(), torch.eye(3))
+        assert torch.all(t[b].cpu() == 0)
 
 
 def test_eager_and_plan_are_one_launch(dev):
