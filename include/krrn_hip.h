@@ -393,8 +393,10 @@ int krrn_umeyama_ransac_f32(const float* src, const float* dst, int N, const int
  * definition: the reference has none). R0 [B][9] row-major, t0 [B][3]: the starting pose, model to
  * camera (p = R m + t); cloud f32 [B][N][3] (3 <= N <= 4096), model f32 [B][M][3] (1 <= M <= 4096),
  * max_dist [B] in metres. Pass k = 0 .. max_iter (<= 64): q_i = R^T (p_i - t); the nearest model point
- * j(i) by d^2 = (dx dx + dy dy) + dz dz (the lowest j among equal distances); pair i kept iff
- * d_i^2 < max_dist^2; K pairs, err_k = mean kept d^2. Stop, tested in this order: K < min_pairs
+ * j(i) by d^2 = (dx dx + dy dy) + dz dz (the lowest j among equal distances; a distance that is
+ * NaN never wins, so a non-finite model point pairs with nothing and a non-finite cloud point has no
+ * pair, nn_idx -1); pair i kept iff d_i^2 < max_dist^2 (max_dist 0 keeps nothing, +inf every finite
+ * d^2); K pairs, err_k = mean kept d^2. Stop, tested in this order: K < min_pairs
  * (>= 3) -> status 2 STARVED; k >= 1 and |err_{k-1} - err_k| <= tol err_{k-1} -> 0 CONVERGED;
  * k == max_iter -> 1 MAX_ITER. Otherwise Kabsch on the kept pairs (two-pass covariance, the Jacobi SVD
  * of krrn_umeyama_ransac_f32) gives the next R, t; if that is not finite the pose from before the

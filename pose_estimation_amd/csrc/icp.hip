@@ -35,7 +35,8 @@ constexpr int kIcpRedBytes = kIcpWaves * 9 * (int)sizeof(double);  // block_sum'
 
 enum { ICP_CONVERGED = 0, ICP_MAX_ITER = 1, ICP_STARVED = 2, ICP_DEGENERATE = 3 };
 
-// nearest model point of the thread's first P cloud points q (a NaN q never wins: d^2 = inf, j = -1)
+// nearest model point of the thread's first P cloud points q (a NaN q never wins: d^2 = inf, j = -1; nor does a
+// non-finite model point: its d^2 is NaN or inf, and `<` is strict and false for NaN)
 template <int P>
 __device__ __forceinline__ void icp_nearest(const float* sm, int M, const double (&q)[kIcpSlots][3],
                                             double (&bd)[kIcpSlots], int (&bj)[kIcpSlots]) {

@@ -6,7 +6,8 @@ family the ICP tests share (test infrastructure, like tests/umeyama_ref.py).
     res = icp(R0, t0, cloud, model, max_dist, max_iter=20, tol=1e-4, min_pairs=6)
     res['R'], res['t']                   the refined pose (f64)
     res['passes'], res['pairs'], res['rmse'], res['status'], res['nn_idx']   describe that pose
-    res['margins']  nn_gap / thr_gap / conv_gap; check_conditions(res) asserts their limits
+    res['nn_prev']                       the pairs of the pass before the last (None after one pass)
+    res['margins']  nn_gap / thr_gap / conv_gap / sigma; check_conditions(res) asserts their limits
 
     sc = scene('work')                    # dict: R0, t0, cloud, model (f32), max_dist, kw, R_gt, t_gt
 """
@@ -23,13 +24,16 @@ CONVERGED, MAX_ITER_HIT, STARVED, DEGENERATE = 0, 1, 2, 3
 MIN_NN_GAP = 1e-10      # (second - best) / second over every pass and point (exact duplicates of the best excluded)
 MIN_THR_GAP = 1e-9      # |d^2 - max_dist^2| / max_dist^2 over every pass and point
 MIN_CONV_GAP = 1e-6     # ||err_{k-1} - err_k| - tol err_{k-1}| / (tol err_{k-1}) over every pass k >= 1 that tests it
+MIN_SIGMA_RATIO = 1e-3  # s2 / s1 of the covariance of every Kabsch update that gave a pose (umeyama_ref's limit)
 
 _ROWS = 512  # cloud points per block of the brute-force distance table
 
 
 def nearest(Q, Mo):
     """Brute force: (j, d2, gap) per row of Q [N, 3] against Mo [M, 3]; argmin takes the lowest index
-    among equal distances. gap = (second - best) / second with exact duplicates of the best left out."""
+    among equal distances. gap = (second - best) / second with exact duplicates of the best left out.
+    A NaN distance (a non-finite cloud or model point) counts as +inf, as the kernel's strict `<` has it: a
+    non-finite model point pairs with nothing, a non-finite cloud point has d2 = inf."""
     N = Q.shape[0]
     j = np.zeros(N, np.int64)
     d2 = np.zeros(N)
@@ -40,9 +44,10 @@ def nearest(Q, Mo):
         dy = q[:, None, 1] - Mo[None, :, 1]
         dz = q[:, None, 2] - Mo[None, :, 2]
         D = (dx * dx + dy * dy) + dz * dz
+        D = np.where(np.isnan(D), np.inf, D)  # a NaN distance never wins (numpy's argmin would pick it)
         jj = np.argmin(D, axis=1)
         best = D[np.arange(len(q)), jj]
-        with np.errstate(invalid="ignore"):
+        with np.errstate(invalid="ignore", over="ignore"):
             second = np.where(D > best[:, None], D, np.inf).min(axis=1)
             g = np.where(np.isfinite(second), (second - best) / second, 1.0)
         j[lo:lo + _ROWS], d2[lo:lo + _ROWS], gap[lo:lo + _ROWS] = jj, best, g
@@ -50,8 +55,8 @@ def nearest(Q, Mo):
 
 
 def kabsch(Mk, Pk):
-    """R, t of p ~ R m + t on the pairs (two-pass covariance, R = U diag(1, 1, sign) V^T); None where the
-    pair set has no second direction (the kernel divides by the second singular value: not finite)."""
+    """R, t, s2 / s1 of p ~ R m + t on the pairs (two-pass covariance, R = U diag(1, 1, sign) V^T); None where
+    the pair set has no second direction (the kernel divides by the second singular value: not finite)."""
     K = Mk.shape[0]
     mm, mp = Mk.sum(0) / K, Pk.sum(0) / K
     cov = (Pk - mp).T @ (Mk - mm) / K
@@ -63,7 +68,7 @@ def kabsch(Mk, Pk):
     t = mp - R @ mm
     if not (np.isfinite(R).all() and np.isfinite(t).all()):
         return None
-    return R, t
+    return R, t, float(D[1] / D[0])
 
 
 def icp(R0, t0, cloud, model, max_dist, max_iter=MAX_ITER, tol=TOL, min_pairs=MIN_PAIRS):
@@ -73,17 +78,19 @@ def icp(R0, t0, cloud, model, max_dist, max_iter=MAX_ITER, tol=TOL, min_pairs=MI
     md = float(np.float32(max_dist))
     md2 = md * md
     R, t = R0.astype(np.float64), t0.astype(np.float64)
-    nn_gap = thr_gap = conv_gap = np.inf
-    err_prev = None
+    nn_gap = thr_gap = conv_gap = sigma = np.inf
+    err_prev = nn_prev = None
     for k in range(max_iter + 1):
-        Q = (P - t) @ R  # rows R^T (p - t)
-        with np.errstate(invalid="ignore"):
+        with np.errstate(invalid="ignore", over="ignore"):
+            Q = (P - t) @ R  # rows R^T (p - t)
             j, d2, gap = nearest(Q, Mo)
             keep = d2 < md2
         fin = np.isfinite(d2)
         if fin.any():
             nn_gap = min(nn_gap, float(gap[fin].min()))
-            thr_gap = min(thr_gap, float((np.abs(d2[fin] - md2) / md2).min()))
+            # max_dist 0 (d2 < 0: never) and +inf (a finite d2 < inf: always) are decided without rounding
+            if 0.0 < md2 < np.inf:
+                thr_gap = min(thr_gap, float((np.abs(d2[fin] - md2) / md2).min()))
         K = int(keep.sum())
         err = float(d2[keep].sum() / K) if K else np.nan
         status = None
@@ -104,10 +111,12 @@ def icp(R0, t0, cloud, model, max_dist, max_iter=MAX_ITER, tol=TOL, min_pairs=MI
                 status = DEGENERATE
         if status is not None:
             return dict(R=R, t=t, passes=k + 1, pairs=K, rmse=float(np.sqrt(err)) if K else np.inf, status=status,
-                        nn_idx=np.where(keep, j, -1).astype(np.int32),
-                        margins=dict(nn_gap=nn_gap, thr_gap=thr_gap, conv_gap=conv_gap))
-        R, t = new
+                        nn_idx=np.where(keep, j, -1).astype(np.int32), nn_prev=nn_prev,
+                        margins=dict(nn_gap=nn_gap, thr_gap=thr_gap, conv_gap=conv_gap, sigma=sigma))
+        R, t = new[:2]
+        sigma = min(sigma, new[2])
         err_prev = err
+        nn_prev = np.where(keep, j, -1).astype(np.int32)
     raise AssertionError("unreachable: pass max_iter always stops")
 
 
@@ -116,6 +125,7 @@ def check_conditions(res):
     assert m["nn_gap"] >= MIN_NN_GAP, m
     assert m["thr_gap"] >= MIN_THR_GAP, m
     assert m["conv_gap"] >= MIN_CONV_GAP, m
+    assert m["sigma"] >= MIN_SIGMA_RATIO, m
 
 
 def add(R, t, Rg, tg, model):
@@ -144,17 +154,17 @@ def make_model(rng, M):
     return (u * r[:, None] * np.array([0.06, 0.04, 0.03])).astype(np.float32)
 
 
-def make_scene(seed, N, M, noise=1e-3, rot_deg=5.0, dt=0.01, out_frac=0.0, shift=0.0, model=None):
+def make_scene(seed, N, M, noise=1e-3, rot_deg=5.0, dt=0.01, out_frac=0.0, shift=0.0, model=None, half=True):
     """A model, a ground-truth pose at about (0.05, -0.03, 0.8) m, a cloud of N points drawn from the half
     of the model nearest the camera (Gaussian noise, an out_frac share displaced by +-0.2 m per axis, the
-    whole cloud moved by `shift` m along z) and a start pose: the ground truth turned by rot_deg about a
-    random axis and moved by N(0, dt)."""
+    whole cloud moved by `shift` m along z; half=False draws from the whole model) and a start pose: the ground
+    truth turned by rot_deg about a random axis and moved by N(0, dt)."""
     rng = np.random.default_rng(seed)
     model = make_model(rng, M) if model is None else np.asarray(model, np.float32)
     Rg = rodrigues(rng.normal(size=3), rng.uniform(0.0, 360.0))
     tg = np.array([0.05, -0.03, 0.8]) + rng.normal(scale=0.01, size=3)
     pc = model.astype(np.float64) @ Rg.T + tg
-    near = np.argsort(pc[:, 2], kind="stable")[:max(model.shape[0] // 2, 1)]
+    near = np.argsort(pc[:, 2], kind="stable")[:max(model.shape[0] // 2, 1) if half else model.shape[0]]
     pick = rng.choice(near, N, replace=True)
     c = pc[pick] + (rng.normal(scale=noise, size=(N, 3)) if noise else 0.0)
     out = rng.random(N) < out_frac

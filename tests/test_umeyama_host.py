@@ -62,15 +62,21 @@ def test_host_side_errors():
     D = ctypes.c_double
     ume = lib.krrn_umeyama_ransac_f32
 
-    def call(src=fake, n=64, h=128, b=1, counts=fake):
-        return ume(src, fake, n, fake, h, D(0.1), D(0.99), D(0.1), counts, fake, fake, fake, fake, N, N, b, N)
+    names = ("src", "dst", "subsets", "hyp_counts", "scale", "R", "t", "inliers")
 
-    assert call(src=N) == -1
-    assert call(counts=N) == -1
+    def call(n=64, h=128, b=1, **null):
+        p = {k: (N if k in null else fake) for k in names}
+        return ume(p["src"], p["dst"], n, p["subsets"], h, D(0.1), D(0.99), D(0.1), p["hyp_counts"], p["scale"], p["R"],
+                   p["t"], p["inliers"], N, N, b, N)
+
+    for k in names:  # every required pointer; best_hyp and inlier_mask are optional (null in every call here)
+        assert call(**{k: True}) == -1, k
     assert call(n=4) == -2
     assert call(n=4097) == -2
     assert call(h=0) == -2
+    assert call(h=8193) == -2
     assert call(b=0) == -2
+    assert call(n=4, src=True) == -1  # pointers are checked first
     mp = lib.krrn_model_points_f32
     assert mp(N, 16, fake, 8, fake, fake, fake, 1, N) == -1
     assert mp(fake, 16, fake, 8, fake, fake, N, 1, N) == -1
