@@ -605,6 +605,25 @@ int krrn_bop_visib_u8(const float* verts, int Vtot, const int* faces, int Ftot, 
                       unsigned char* mask, unsigned char* mask_visib, int* info, double* visib_fract,
                       void* stream);
 
+/* Decode n run-length encoded masks (COCO RLE, the `segmentation` of BOP's detection files) into u8 planes.
+ * counts int32: the run lengths of the n masks, concatenated; offs int32 [n + 1] (device memory): mask i owns
+ * runs offs[i] .. offs[i + 1] - 1. COCO's semantics: pixels are numbered column-major, p = x H + y; the first run
+ * is zeros and the runs alternate; a run may have length 0. With ends = the inclusive prefix sums of mask i's runs,
+ *   mask[i][y][x] = 1 iff #{k : ends[k] <= p} is odd, else 0
+ * which needs no special case for a zero-length run, and gives a pixel at or past the runs' total the parity of
+ * the run count. mask u8 [n][H][W] row-major at any byte address: every byte of it is written by the call (no
+ * memset by the caller or the entry point). info int32 [n][5] = (pixel count, x, y, w, h): the number of set
+ * pixels and their tight box in BOP's convention w = x_max - x_min, h = y_max - y_min; a mask without a set pixel
+ * gives 0, 0, 0, 0, 0. The entry point writes every info row itself. ends: int32 workspace of offs[n] elements
+ * (the prefix sums, saturated at H W so that they never wrap). Integer work without atomics: the result is
+ * deterministic and a mask's does not depend on the rest of the batch. For any counts (a negative one counts as 0)
+ * the kernels read counts / ends only inside [offs[i], offs[i + 1]) and write only mask i's plane and info row;
+ * a range that is negative, reversed or past offs[n] is an empty one (an all-zero mask). Host checks, before any
+ * HIP call: null counts / offs / ends / mask / info KRRN_EARG; n < 0, H <= 0, W <= 0 or H W > INT32_MAX
+ * KRRN_ESHAPE; n == 0 returns 0 and launches nothing. */
+int krrn_rle_decode_u8(const int* counts, const int* offs, int n, int H, int W, int* ends, unsigned char* mask,
+                       int* info, void* stream);
+
 /* MSSD / MSPD, the maximum symmetry-aware surface / projection distance. verts f32 [Vtot][3] (all mesh
  * vertices), vert_range int32 [B][2] = first vertex, count of crop b; syms f64 [NStot][12] = row-major R
  * then t (metres, model frame), sym_range int32 [B][2] (each object's set begins with the identity). Per

@@ -19,14 +19,15 @@ Drop-in API (the reference's names):
     bop.vsd / bop.mssd_mspd / test_epoch(bop=True)  the BOP-19 pose errors and average recalls (no reference counterpart)
     verify.score_poses / select_pose / test_epoch(select="depth")  pose candidates scored against the observed depth,
                                           the best kept (render-and-compare; this project's own)
+    rle.decode / PoseDataset(detections=...)  crops and masks from BOP detection files, RLE masks decoded on the GPU
 """
 from .config import CONFIG, Cfg, make_config  # noqa: F401
 from .krrn import KRRN  # noqa: F401
 from . import bpnp, dataset, fps  # noqa: F401
 from .loss import KRRNLoss  # noqa: F401
-from . import bop, icp, raster, verify  # noqa: F401
+from . import bop, icp, raster, rle, verify  # noqa: F401
 from .pose import add_icp_ops, add_umeyama_ops, get_pose, get_pose_umeyama, refine_pose_icp, select_pose  # noqa: F401
 from .umeyama import estimateSimilarityTransform  # noqa: F401
 
 __all__ = ["KRRN", "KRRNLoss", "get_pose", "get_pose_umeyama", "add_umeyama_ops", "estimateSimilarityTransform",
-           "bop", "icp", "raster", "verify", "refine_pose_icp", "select_pose", "add_icp_ops", "make_config", "CONFIG", "Cfg"]
+           "bop", "icp", "raster", "rle", "verify", "refine_pose_icp", "select_pose", "add_icp_ops", "make_config", "CONFIG", "Cfg"]

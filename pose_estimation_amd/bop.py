@@ -221,10 +221,14 @@ def bop_errors(pred_r: torch.Tensor, pred_t: torch.Tensor, data: Dict[str, torch
     return {"vsd": v["e_vsd"], "mssd": m["mssd"], "mspd": m["mspd"]}
 
 
-def _recalls(rec: np.ndarray, dia: np.ndarray, width: float) -> Dict[str, float]:
-    n = len(rec)
-    if n == 0:
-        return {"AR_VSD": 0.0, "AR_MSSD": 0.0, "AR_MSPD": 0.0, "AR": 0.0, "count": 0}
+def _recalls(rec: np.ndarray, dia: np.ndarray, width: float, missed: Optional[int] = None) -> Dict[str, float]:
+    """missed: None (recall over the estimates), or the number of targets without an estimate, added to every
+    recall's denominator and reported as "targets" = count + missed."""
+    count = len(rec)
+    n = count + (missed or 0)
+    extra = {} if missed is None else {"targets": int(n)}
+    if n == 0 or count == 0:
+        return {"AR_VSD": 0.0, "AR_MSSD": 0.0, "AR_MSPD": 0.0, "AR": 0.0, "count": int(count), **extra}
     T = len(TAUS)
     e = rec[:, _B["vsd_0"]:_B["vsd_0"] + T]
     th = np.asarray(THETAS)
@@ -232,10 +236,11 @@ def _recalls(rec: np.ndarray, dia: np.ndarray, width: float) -> Dict[str, float]
     ar_mssd = float(np.mean([(rec[:, _B["mssd"]] < t * dia).sum() / n for t in th]))
     ar_mspd = float(np.mean([(rec[:, _B["mspd"]] < t * (width / 640.0)).sum() / n for t in THETAS_PX]))
     return {"AR_VSD": ar_vsd, "AR_MSSD": ar_mssd, "AR_MSPD": ar_mspd, "AR": (ar_vsd + ar_mssd + ar_mspd) / 3.0,
-            "count": int(n)}
+            "count": int(count), **extra}
 
 
-def fold_bop(records, objlist: Sequence[int], diameter: Sequence[float], width: float = FRAME_W) -> Dict[str, object]:
+def fold_bop(records, objlist: Sequence[int], diameter: Sequence[float], width: float = FRAME_W,
+             missed: Optional[Dict[int, int]] = None) -> Dict[str, object]:
     """The BOP-19 average recalls over per-crop BOP_REC records (any order, pad rows valid = 0), folded in
     global crop order like evaluate.fold_records. An estimate is correct w.r.t. an error when the error is
     strictly below the threshold; recall = correct / targets (one estimate per target).
@@ -244,14 +249,28 @@ def fold_bop(records, objlist: Sequence[int], diameter: Sequence[float], width: 
       AR_MSPD  mean over thresholds 5 .. 50 px x (width / 640)
       AR       the mean of the three
     Returns {"AR_VSD", "AR_MSSD", "AR_MSPD", "AR", "count"} over all crops pooled, plus "per_obj": {obj id:
-    the same five keys} for the objects that occur."""
+    the same five keys} for the objects that occur.
+    missed: None, or {obj id: count} of targets that have no estimate (a detector missed them). They are added to
+    every recall's denominator, per object and pooled: "count" stays the number of estimates and a sixth key
+    "targets" = count + missed appears beside it; an object with missed targets only occurs in per_obj with recall
+    0. With missed=None nothing changes."""
     rec = records.numpy() if isinstance(records, torch.Tensor) else np.asarray(records, np.float64)
     rec = rec.reshape(-1, len(BOP_REC))
     rec = rec[rec[:, _B["valid"]] > 0]
     rec = rec[np.argsort(rec[:, _B["crop"]], kind="stable")]
     cls = rec[:, _B["cls"]].astype(np.int64)
     dia = np.asarray(diameter, np.float64)[cls] if len(rec) else np.zeros((0,))
-    out = _recalls(rec, dia, float(width))
-    out["per_obj"] = {objlist[int(c)]: _recalls(rec[cls == c], dia[cls == c], float(width))
-                      for c in dict.fromkeys(cls.tolist())}
+    if missed is None:
+        out = _recalls(rec, dia, float(width))
+        out["per_obj"] = {objlist[int(c)]: _recalls(rec[cls == c], dia[cls == c], float(width))
+                          for c in dict.fromkeys(cls.tolist())}
+        return out
+    miss = {int(o): int(m) for o, m in missed.items() if int(m) > 0}
+    out = _recalls(rec, dia, float(width), sum(miss.values()))
+    objs = [objlist[int(c)] for c in dict.fromkeys(cls.tolist())]
+    objs += [o for o in sorted(miss) if o not in objs]
+    out["per_obj"] = {}
+    for o in objs:
+        sel = cls == (list(objlist).index(o) if o in objlist else -1)
+        out["per_obj"][o] = _recalls(rec[sel], dia[sel], float(width), miss.get(o, 0))
     return out

@@ -15,9 +15,19 @@ PLY only; a binary PLY (what some BOP datasets ship) keeps raising their ValueEr
 (per instance `visib_fract`, `px_count_visib`, `bbox_visib`, ...); images `rgb/%06d.png` (or .jpg),
 `depth/%06d.png` (uint16) and the per-instance `mask_visib/%06d_%06d.png` (image id, GT index).
 
+Detections. BOP distributes detectors' output, and a user's own detector writes, a JSON list of {scene_id, image_id,
+category_id, score, bbox = [x, y, w, h], optional segmentation = {"counts": run list or COCO's compressed string,
+"size": [H, W]}, optional time} (read_detections / write_detections). BopTree(..., detections=path or rows) pairs
+every kept GT instance with the best-scoring detection of its (scene, image, object) and takes the crop box and the
+mask from it instead of bbox_visib / mask_visib (the runs are decoded on the GPU per batch: rle.decode);
+gt_detections(tree) writes a tree's own ground truth as detections, an upper-bound run.
+
+    rows = read_detections("/data/lmo/detections.json"); write_detections("mine.json", rows)
+    tree = BopTree("/data/lmo", targets=..., detections="/data/lmo/detections.json", det_min_score=0.1)
+
 Out of scope: matching several estimates to several instances of one object in an image (a target's
-`inst_count` > 1: every kept GT instance is one item with one estimate), binary PLY, and detector boxes / masks
-in BOP's detection format (the crops come from `bbox_visib`)."""
+`inst_count` > 1: every kept GT instance is one item with one estimate; with detections such a target is refused)
+and binary PLY."""
 from __future__ import annotations
 
 import json
@@ -27,7 +37,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from . import bop
+from . import bop, rle
 
 INFO_KEYS = ("bbox_obj", "bbox_visib", "px_count_all", "px_count_valid", "px_count_visib", "visib_fract")  # BOP's six
 
@@ -83,12 +93,24 @@ class BopTree:
     targets: the path of a test_targets_bop19.json-style list ({scene_id, im_id, obj_id, inst_count}); only its
     (scene, image, object) triples are kept. Instances with visib_fract < min_visib or px_count_visib == 0 are
     dropped: BOP-19's rule for which GT instances count. objlist: the objects to keep; default the sorted ids
-    that remain. A scene without scene_gt_info.json raises FileNotFoundError naming write_gt_info."""
+    that remain. A scene without scene_gt_info.json raises FileNotFoundError naming write_gt_info.
+
+    detections: None, or a detection file's path or rows (module doc). The items are still the GT instances kept
+    above, each paired with one detection: among the rows whose (scene_id, image_id, category_id) are the item's and
+    whose score >= det_min_score, the highest score, ties to the earliest row. Rows without a set mask pixel or with
+    w <= 0 or h <= 0 are dropped before pairing. A paired item's "bbox" is the detection's, and it gains "score",
+    "det" (the row's index) and "rle" (the mask's run list; the filled box's runs for a row without segmentation).
+    A kept target without a detection yields no item and is listed in `missed` as (scene, im, obj); `objlist` stays
+    the kept targets'. `det_stats` = {"rows", "used", "unused", "dropped"}: all rows, those paired, those not chosen
+    for any kept target, those dropped before pairing. ValueError: a segmentation whose size is not the tree's frame
+    size or whose runs do not fill it, and two or more kept instances of one object in one image."""
 
     def __init__(self, root: str, split: str = "test", targets: Optional[str] = None,
                  objlist: Optional[Sequence[int]] = None, n_model_pts: int = 2600, seed: int = 0, meshes: bool = False,
-                 min_visib: float = 0.1):
+                 min_visib: float = 0.1, detections=None, det_min_score: float = 0.0):
         self.root, self.split = root, split
+        self.missed: List[Tuple[int, int, int]] = []
+        self.det_stats: Optional[Dict[str, int]] = None
         want = None
         if targets is not None:
             with open(targets) as f:
@@ -127,6 +149,8 @@ class BopTree:
             from PIL import Image
             with Image.open(os.path.join(root, split, f"{int(it['scene']):06d}", "depth", f"{int(it['im']):06d}.png")) as di:
                 self.frame_hw = (di.size[1], di.size[0])
+        if detections is not None:
+            self._pair(detections, float(det_min_score))
         self.info, mesh = load_models(root, self.objlist, faces=meshes)
         self.mesh: Dict[int, Tuple[np.ndarray, np.ndarray]] = mesh if meshes else {}
         self.symmetries: Dict[int, np.ndarray] = {}
@@ -142,6 +166,52 @@ class BopTree:
             if len(pts) > n_model_pts:
                 pts = pts[np.sort(rng.choice(len(pts), n_model_pts, replace=False))]
             self.model_points[obj] = pts.astype(np.float32)
+
+    def _pair(self, detections, min_score: float) -> None:
+        """Pair the kept GT instances with detection rows (class doc)."""
+        rows = read_detections(detections) if isinstance(detections, (str, os.PathLike)) else _check_rows(detections, "rows")
+        seen = set()
+        for it in self.items:
+            key = (int(it["scene"]), int(it["im"]), int(it["obj"]))
+            if key in seen:
+                raise ValueError(f"target (scene {key[0]}, image {key[1]}, object {key[2]}) has more than one kept GT "
+                                 "instance (inst_count > 1): matching several estimates to several instances is out of "
+                                 "scope with detections")
+            seen.add(key)
+        best: Dict[Tuple[int, int, int], int] = {}
+        dropped = 0
+        for j, r in enumerate(rows):
+            seg = r.get("segmentation")
+            if r["bbox"][2] <= 0 or r["bbox"][3] <= 0 or (seg is not None and sum(seg["counts"][1::2]) <= 0):
+                dropped += 1
+                continue
+            key = (r["scene_id"], r["image_id"], r["category_id"])
+            if key not in seen or r["score"] < min_score:
+                continue
+            if key not in best or r["score"] > rows[best[key]]["score"]:     # a tie keeps the earlier row
+                best[key] = j
+        H, W = self.frame_hw if self.frame_hw else (0, 0)
+        items = []
+        for it in self.items:
+            key = (int(it["scene"]), int(it["im"]), int(it["obj"]))
+            if key not in best:
+                self.missed.append(key)
+                continue
+            r = rows[best[key]]
+            seg = r.get("segmentation")
+            if seg is None:
+                runs = rle.box_counts(*r["bbox"], H, W)
+            else:
+                if tuple(seg["size"]) != (H, W):
+                    raise ValueError(f"detection {best[key]}: segmentation.size {list(seg['size'])} is not the tree's "
+                                     f"frame size {[H, W]}")
+                runs = list(seg["counts"])
+                if min(runs) < 0 or sum(runs) != H * W:
+                    raise ValueError(f"detection {best[key]}: its runs do not fill the {H} x {W} frame")
+            items.append(dict(it, bbox=[float(v) for v in r["bbox"]], score=float(r["score"]), det=best[key], rle=runs))
+        self.items = items
+        self.det_stats = {"rows": len(rows), "used": len(best), "unused": len(rows) - len(best) - dropped,
+                          "dropped": dropped}
 
     def has_symmetry(self, obj: int) -> bool:
         oi = self.info.get(obj, {})
@@ -169,6 +239,74 @@ class BopTree:
         it = self.items[i]
         rgb, depth = self.read_image(int(it["scene"]), int(it["im"]), float(it["depth_scale"]))
         return rgb, depth, self.read_mask(i)
+
+
+DET_KEYS = ("scene_id", "image_id", "category_id", "score", "bbox")
+
+
+def _check_rows(rows, where: str) -> List[Dict[str, object]]:
+    """Detection rows in this module's normal form: ints, a float score, bbox as 4 floats, segmentation (if any)
+    as {"counts": run list, "size": [H, W]} (a compressed string is decoded here), time (if any) a float.
+    ValueError with the entry's index for a missing required key, a bbox that is not 4 numbers, or a segmentation
+    without both keys."""
+    if not isinstance(rows, (list, tuple)):
+        raise ValueError(f"{where}: a list of detections expected, got {type(rows).__name__}")
+    out = []
+    for j, r in enumerate(rows):
+        if not isinstance(r, dict):
+            raise ValueError(f"{where}: entry {j} is not an object")
+        for k in DET_KEYS:
+            if k not in r:
+                raise ValueError(f"{where}: entry {j} has no '{k}'")
+        bb = r["bbox"]
+        if not isinstance(bb, (list, tuple)) or len(bb) != 4 or not all(
+                isinstance(v, (int, float)) and not isinstance(v, bool) for v in bb):
+            raise ValueError(f"{where}: entry {j}: bbox must be 4 numbers [x, y, w, h], got {bb!r}")
+        e = {"scene_id": int(r["scene_id"]), "image_id": int(r["image_id"]), "category_id": int(r["category_id"]),
+             "score": float(r["score"]), "bbox": [float(v) for v in bb]}
+        seg = r.get("segmentation")
+        if seg is not None:
+            if not isinstance(seg, dict) or "counts" not in seg or "size" not in seg:
+                raise ValueError(f"{where}: entry {j}: segmentation needs both 'counts' and 'size'")
+            c = seg["counts"]
+            try:
+                runs = rle.counts_from_string(c) if isinstance(c, str) else [int(v) for v in c]
+                size = [int(v) for v in seg["size"]]
+            except (TypeError, ValueError) as err:
+                raise ValueError(f"{where}: entry {j}: bad segmentation ({err})") from None
+            if len(size) != 2:
+                raise ValueError(f"{where}: entry {j}: segmentation.size must be [H, W], got {seg['size']!r}")
+            e["segmentation"] = {"counts": runs, "size": size}
+        if "time" in r:
+            e["time"] = float(r["time"])
+        out.append(e)
+    return out
+
+
+def read_detections(path) -> List[Dict[str, object]]:
+    """A file in BOP's detection / segmentation result format (module doc) as rows in _check_rows' normal form."""
+    with open(path) as f:
+        return _check_rows(json.load(f), str(path))
+
+
+def write_detections(path, rows) -> None:
+    """The same format, masks as run lists; read_detections returns what was written."""
+    with open(path, "w") as f:
+        json.dump(_check_rows(rows, "rows"), f)
+
+
+def gt_detections(tree: "BopTree") -> List[Dict[str, object]]:
+    """Oracle detections of a tree built without detections: one row per item, from its bbox_visib and its
+    mask_visib PNG, with score 1.0. A dataset built on them equals the tree's own PNG mode (an upper-bound run)."""
+    if tree.det_stats is not None:
+        raise ValueError("gt_detections reads bbox_visib: build the tree without detections")
+    rows = []
+    for i, it in enumerate(tree.items):
+        m = tree.read_mask(i)
+        rows.append({"scene_id": int(it["scene"]), "image_id": int(it["im"]), "category_id": int(it["obj"]),
+                     "score": 1.0, "bbox": [float(v) for v in it["bbox"]],
+                     "segmentation": {"counts": rle.encode(m), "size": [int(m.shape[0]), int(m.shape[1])]}})
+    return rows
 
 
 def _save_json(path: str, content: Dict[int, object]) -> None:

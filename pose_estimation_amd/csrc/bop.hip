@@ -165,12 +165,6 @@ __global__ __launch_bounds__(kRastThreads) void bop_visib_box_kernel(
   bop_project_box(cam, verts, Vtot, faces, Ftot, face_range, b, s_box, o);
 }
 
-// 16 flag bits -> 16 bytes of 0 / 1 (bit i to byte i)
-__device__ __forceinline__ uint4 bop_row_bytes(unsigned bits) {
-  auto four = [](unsigned n) { return ((n & 0xfu) * 0x00204081u) & 0x01010101u; };  // the shifted copies do not overlap
-  return make_uint4(four(bits), four(bits >> 4), four(bits >> 8), four(bits >> 12));
-}
-
 // one plane's stores and one box's bounds for one wave: bal = the wave's ballot of the pixel flag
 __device__ __forceinline__ void bop_visib_emit(unsigned long long bal, bool flag, bool inside, bool row_fast,
                                                unsigned char* __restrict__ plane, size_t pix, int lane, int lx,
@@ -178,7 +172,7 @@ __device__ __forceinline__ void bop_visib_emit(unsigned long long bal, bool flag
   if (plane) {
     if (row_fast) {
       if ((lane & 15) == 0 && inside)
-        *reinterpret_cast<uint4*>(plane + pix) = bop_row_bytes((unsigned)(bal >> lane) & 0xffffu);
+        *reinterpret_cast<uint4*>(plane + pix) = krrn_row_bytes((unsigned)(bal >> lane) & 0xffffu);
     } else if (inside) {
       plane[pix] = flag ? 1 : 0;
     }

@@ -53,6 +53,7 @@ import torch
 
 from . import _lib
 from . import bop as _bop
+from . import rle as _rle
 from .bop import symmetry_set
 from .bop_scene import BopTree
 from .config import CONFIG, LM_OBJLIST, OBJ_DICT, SYM_OBJ, models_info
@@ -374,19 +375,31 @@ class PoseDataset(torch.utils.data.Dataset):
     Linemod_preprocessed's coordinates), sym_obj holds the classes whose entry there has a symmetry key, and the
     crop boxes are snapped inside the tree's own frame size. masks="png" (default) takes mask_label from the
     tree's mask_visib PNGs; masks="render" (needs meshes=True) takes it from bop.visibility of the GT pose
-    against the observed depth, for trees that ship none. layout="linemod" (default) changes nothing."""
+    against the observed depth, for trees that ship none. layout="linemod" (default) changes nothing.
+
+    detections (a BOP detection file's path or rows; needs layout="bop", refused with masks="render") and
+    det_min_score: every kept GT instance is paired with its best detection (bop_scene.BopTree), the crop is snapped
+    from the detection's bbox, no mask PNG is read, and batch() decodes the batch's run-length encoded masks into
+    mask_label with one rle.decode on the input stream; everything downstream reads that mask_label unchanged. A
+    batch then also carries det_score f32 [B] and det_info int32 [B, 5] (rle.decode's info); the GT keys remain the
+    paired instance's. Targets without a detection are in tree.missed and yield no item."""
 
     def __init__(self, mode: str = "test", num_point: int = 1000, add_noise: bool = False, root: Optional[str] = None,
                  noise_trans: float = 0.0, num_kps: int = 8, cls_type: Optional[str] = None, cfg=CONFIG,
                  num_frames: int = 256, seed: int = 0, sizes: Optional[Sequence[int]] = None,
                  n_model_pts: int = 2600, io_threads: int = 8, gt_maps: bool = False, meshes: bool = False,
                  layout: str = "linemod", split: str = "test", targets: Optional[str] = None, min_visib: float = 0.1,
-                 masks: str = "png"):
+                 masks: str = "png", detections=None, det_min_score: float = 0.0):
         if layout not in ("linemod", "bop"):
             raise ValueError(f"layout must be 'linemod' or 'bop', got {layout!r}")
         if masks not in ("png", "render"):
             raise ValueError(f"masks must be 'png' or 'render', got {masks!r}")
+        if detections is not None and layout != "bop":
+            raise ValueError("detections are BOP detection files: they need layout='bop'")
+        if detections is not None and masks == "render":
+            raise ValueError("detections bring their own masks: they cannot be combined with masks='render'")
         self.layout, self.masks = layout, masks
+        self.detections = detections is not None
         self.mode, self.num_point, self.cfg, self.root = mode, num_point, cfg, root
         self.gt_maps = bool(gt_maps)
         self.meshes = bool(meshes) or self.gt_maps
@@ -410,7 +423,8 @@ class PoseDataset(torch.utils.data.Dataset):
         if layout == "bop":
             self.tree = BopTree(root, split=split, targets=targets,
                                 objlist=None if cls_type in (None, "all") else self.objlist, n_model_pts=n_model_pts,
-                                seed=seed, meshes=self.meshes, min_visib=min_visib)
+                                seed=seed, meshes=self.meshes, min_visib=min_visib, detections=detections,
+                                det_min_score=det_min_score)
             self.objlist = list(self.tree.objlist)
             self.obj_info = {o: {"min": [e["min_x"], e["min_y"], e["min_z"]], "size": [e["size_x"], e["size_y"], e["size_z"]],
                                  "diameter": e["diameter"]} for o, e in ((o, self.tree.info[o]) for o in self.objlist)}
@@ -478,7 +492,7 @@ class PoseDataset(torch.utils.data.Dataset):
                 its = [self.tree.items[i] for i in idx]
                 keys = list(dict.fromkeys((int(it["scene"]), int(it["im"]), float(it["depth_scale"])) for it in its))
                 img = dict(zip(keys, ex.map(lambda k: self.tree.read_image(*k), keys)))
-                if self.masks == "render":
+                if self.masks == "render" or self.detections:
                     ml = [None] * len(idx)
                 else:
                     ml = list(ex.map(self.tree.read_mask, idx))
@@ -487,7 +501,7 @@ class PoseDataset(torch.utils.data.Dataset):
                 fr = list(ex.map(self.tree.read, idx))
         out = {"rgb": h2d(torch.from_numpy(np.stack([f[0] for f in fr])), device),
                "depth": h2d(torch.from_numpy(np.stack([f[1] for f in fr])), device)}
-        if fr[0][2] is not None:  # masks="render": batch() renders mask_label on the device
+        if fr[0][2] is not None:  # masks="render" / detections: batch() makes mask_label on the device
             out["mask_label"] = h2d(torch.from_numpy(np.stack([f[2] for f in fr])), device)
         return out
 
@@ -569,6 +583,12 @@ class PoseDataset(torch.utils.data.Dataset):
         metas = [self._meta(i) for i in idx]
         R64 = torch.from_numpy(np.stack([m[1] for m in metas]))
         t64 = torch.from_numpy(np.stack([m[2] for m in metas]))
+        det = None
+        if self.detections:  # the detections' masks: one decode of the batch's runs, on this (the input) stream
+            runs = [self.tree.items[i]["rle"] for i in idx]
+            det = _rle.decode(np.concatenate([np.asarray(r, np.int64) for r in runs]),
+                              np.cumsum([0] + [len(r) for r in runs]), *fr["depth"].shape[1:], device)
+            fr["mask_label"] = det["mask"]
         if "mask_label" not in fr:  # masks="render": the visible mask of the GT pose against the observed depth
             mesh = self._mesh_for(device)
             fr["mask_label"] = _bop.visibility(
@@ -621,6 +641,9 @@ class PoseDataset(torch.utils.data.Dataset):
                         "bop_sym_range": rng("srange")})
         if verify:
             out["verify_mask"] = fr["mask_label"]
+        if det is not None:
+            out["det_score"] = h2d(torch.tensor([self.tree.items[i]["score"] for i in idx], dtype=torch.float32), device)
+            out["det_info"] = det["info"]
         return out
 
     def __getitem__(self, i: int) -> Dict[str, torch.Tensor]:

@@ -352,7 +352,12 @@ def test_epoch(model: KRRN, dataset: PoseDataset, bs: int = 64, device=None, opt
     `select` as in eval_records: "depth" chooses every crop's final pose among the epoch's candidates by
     render-and-compare, and adds one key, "select": {"picked": {candidate index: crops}, "mean_score": the mean of
     the kept candidates' scores in crop order}; the final / reg keys, "bop" and the CSV's poses are then the chosen
-    pose's, and the CSV's score column is its score (a confidence in [0, 1]). The base keys do not change."""
+    pose's, and the CSV's score column is its score (a confidence in [0, 1]). The base keys do not change.
+    A dataset built with detections (PoseDataset(..., detections=...)) adds one key, "detections": {"targets" the
+    kept GT targets, "estimated" those with a detection (the crops evaluated), "missed" those without, and the
+    detection file's "rows", "unused", "dropped" (BopTree.det_stats)}; the missed targets enter every BOP recall's
+    denominator (bop.fold_bop(missed=...): "bop" gains "targets"), and the CSV's score column is the detection's
+    score unless `select` puts the verification score there. Every other key is computed as before."""
     device = torch.device(device) if device is not None else next(model.parameters()).device
     if world is None:
         world = dist.get_world_size(group) if dist.is_initialized() else 1
@@ -380,10 +385,21 @@ def test_epoch(model: KRRN, dataset: PoseDataset, bs: int = 64, device=None, opt
     allrec = gather_epoch_records(local, shard_sizes, device, group) if world > 1 else local
     metric = Metric(dataset.sym_obj)
     out = fold_records(allrec, dataset.objlist, dataset.diameter, opt_pose, metric)
+    det = bool(getattr(dataset, "detections", False))  # a detection-mode dataset: targets without an estimate count
+    missed: Dict[int, int] = {}
+    for _, _, obj in (dataset.tree.missed if det else ()):
+        missed[obj] = missed.get(obj, 0) + 1
     if bop:  # a record table of its own, gathered by the same mechanism
         allbop = gather_epoch_records(local_bop, shard_sizes, device, group) if world > 1 else local_bop
-        out["bop"] = fold_bop(allbop, dataset.objlist, dataset.diameter, getattr(dataset, "frame_hw", (0, FRAME_W))[1])
+        out["bop"] = fold_bop(allbop, dataset.objlist, dataset.diameter, getattr(dataset, "frame_hw", (0, FRAME_W))[1],
+                              **({"missed": missed} if det else {}))
     conf = {}
+    if det:
+        st = dataset.tree.det_stats
+        out["detections"] = {"targets": len(dataset) + len(dataset.tree.missed), "estimated": len(dataset),
+                             "missed": len(dataset.tree.missed), "rows": st["rows"], "unused": st["unused"],
+                             "dropped": st["dropped"]}
+        conf = {i: float(it["score"]) for i, it in enumerate(dataset.tree.items)}
     if select:
         allsel = gather_epoch_records(local_sel, shard_sizes, device, group) if world > 1 else local_sel
         tab = allsel.numpy()
