@@ -680,6 +680,46 @@ int krrn_pose_score_f32(const float* verts, int Vtot, const int* faces, int Ftot
                         double depth_scale, const double* tau, int B, int* ws, int* counts, double* score,
                         int* best, float* R_sel, float* t_sel, void* stream);
 
+/* Render-based point-to-plane pose refinement on the depth frame, batched (this project's own definition: the
+ * reference has none; tests/depth_refine_ref.py restates it in numpy f64). verts / faces / face_range / K4 / depth /
+ * mask / frame / depth_scale as krrn_pose_score_f32; R0 f32 [B][9] row-major, t0 f32 [B][3]: the starting pose,
+ * model to camera; max_dist f64 [B] metres; radius f64 [B] = rho, metres. Per crop, R, t = R0, t0 (f64 from there
+ * on, without FMA contraction); pass k = 0, 1, ...:
+ *   render   the crop's faces under (R, t) and K4 over the whole frame exactly as VSD renders (the same device
+ *            function): depth z and winning face per pixel; n = the face's camera-frame normal as
+ *            krrn_raster_maps_f32 defines it ((c1 - c0) x (c2 - c0) normalised, negated if n . c0 > 0; a zero or
+ *            non-finite normal contributes nothing)
+ *   observe  d = depth[frame][y][x] / depth_scale (no sample for a frame index outside [0, F)); a pixel is kept iff
+ *            it is covered, d > 0, |d - z| < max_dist, and mask[frame][y][x] != 0 when mask is given
+ *   points   xn = (x - cx) / fx, yn = (y - cy) / fy; p = z (xn, yn, 1), o = d (xn, yn, 1), r = n . (o - p)
+ *   counts   K = kept pixels, err_k = sum r^2 / K
+ *   stop, tested in this order (R, t as they stand are the result; rmse = sqrt(err_k), +inf for K = 0):
+ *            K < min_pairs -> status 2 STARVED; k >= 1 and |err_{k-1} - err_k| <= tol err_{k-1} -> 0 CONVERGED;
+ *            k == max_iter -> 1 MAX_ITER
+ *   update   one damped Gauss-Newton step in a twist about the object's own centre t, rotation scaled by rho:
+ *            J = [((p - t) / rho) x n, n], A = sum J J^T, b = sum J r, A += damp trace(A) / 6 I, 6 x 6 Cholesky;
+ *            a non-positive or non-finite pivot or a non-finite solution keeps the pose from before the update
+ *            and stops with 3 DEGENERATE; otherwise xi = (w, v): R <- exp(w / rho) R (Rodrigues), t <- t + v
+ * Outputs: R f32 [B][9], t f32 [B][3] (a stop in pass 0 returns R0, t0 bit for bit), passes [B] = the k at the
+ * stop, pairs [B] = the last K, rmse f32 [B], status [B] (the codes of krrn_icp_refine_f32). Per pass three
+ * launches: the projected box of the crop's vertices; one block per 16 x 16 tile of the frame and crop, which
+ * returns at once outside the box or for a finished crop, and otherwise writes its partial sums (21 + 6 + 1 f64 and
+ * the count, reduced in a fixed order) to its own slot of ws; one block per crop that adds the box's slots in
+ * row-major tile order, tests, solves and updates. max_iter + 1 rounds are enqueued whatever the data: nothing is
+ * read back, no atomics, no block waits for another, and a crop's outputs do not depend on the rest of the batch,
+ * bit for bit. NaN or inf in a pose, in K4 or in a depth sample ends in STARVED or DEGENERATE. ws:
+ * krrn_pose_refine_depth_ws(B, H, W) bytes, 8-byte aligned. Host checks, before any HIP call: null pointer (mask
+ * exempt) or overlapping buffers KRRN_EARG; B outside 1..65535, H, W, Vtot, F < 1, Ftot < 0, max_iter outside
+ * 0..32, min_pairs < 6, tol or damp negative or not finite, depth_scale not > 0 KRRN_ESHAPE. frame and face_range
+ * are device memory and guarded by the kernel as in VSD. */
+int krrn_pose_refine_depth_ws(int B, int H, int W, long long* n_bytes);
+int krrn_pose_refine_depth_f32(const float* verts, int Vtot, const int* faces, int Ftot, const int* face_range,
+                               const float* R0, const float* t0, const float* K4, const float* depth,
+                               const unsigned char* mask, int F, int H, int W, const int* frame, double depth_scale,
+                               const double* max_dist, const double* radius, int max_iter, double tol, int min_pairs,
+                               double damp, int B, void* ws, float* R, float* t, int* passes, int* pairs, float* rmse,
+                               int* status, void* stream);
+
 /* BPnP forward (lib/network/dnn/BPnP.py:43-44, cv2.solvePnP(SOLVEPNP_ITERATIVE,
  * useExtrinsicGuess=True)): Levenberg-Marquardt on sum_i ||pi(z_i; y) - x_i||^2 per crop, f64,
  * from y_init. pts2d [B][n][2] pixels; pts3d [n][3] shared (z_per_crop = 0) or [B][n][3];

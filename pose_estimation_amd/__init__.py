@@ -8,6 +8,8 @@ Drop-in API (the reference's names):
     estimateSimilarityTransform(src, dst) lib/transform/umeyama.py:8-98 (Umeyama-RANSAC, batched)
     get_pose_umeyama(pred, data)          tools/script/eval.py:128,151 (the depth-based pose)
     refine_pose_icp(R, t, data, diameter) ICP polish against the depth cloud (icp.py; this project's own)
+    refine_pose_depth(R, t, data, dataset, diameter)  render-based point-to-plane polish on the depth frame
+                                          (depth_refine.py; this project's own)
     PoseDataset / make_batch              dataset/linemod/batchdataset.py (synthetic frames)
     Metric                                lib/utils/metric.py
     KRRNLoss                              lib/network/loss.py (eval-time terms)
@@ -25,9 +27,11 @@ from .config import CONFIG, Cfg, make_config  # noqa: F401
 from .krrn import KRRN  # noqa: F401
 from . import bpnp, dataset, fps  # noqa: F401
 from .loss import KRRNLoss  # noqa: F401
-from . import bop, icp, raster, rle, verify  # noqa: F401
-from .pose import add_icp_ops, add_umeyama_ops, get_pose, get_pose_umeyama, refine_pose_icp, select_pose  # noqa: F401
+from . import bop, depth_refine, icp, raster, rle, verify  # noqa: F401
+from .pose import (add_icp_ops, add_umeyama_ops, get_pose, get_pose_umeyama, refine_pose_depth,  # noqa: F401
+                   refine_pose_icp, select_pose)
 from .umeyama import estimateSimilarityTransform  # noqa: F401
 
 __all__ = ["KRRN", "KRRNLoss", "get_pose", "get_pose_umeyama", "add_umeyama_ops", "estimateSimilarityTransform",
-           "bop", "icp", "raster", "rle", "verify", "refine_pose_icp", "select_pose", "add_icp_ops", "make_config", "CONFIG", "Cfg"]
+           "bop", "depth_refine", "icp", "raster", "rle", "verify", "refine_pose_depth", "refine_pose_icp", "select_pose",
+           "add_icp_ops", "make_config", "CONFIG", "Cfg"]

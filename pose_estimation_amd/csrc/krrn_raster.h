@@ -136,6 +136,28 @@ __device__ __forceinline__ void rast_depth_walk(const RastCam& cam, const float*
   }
 }
 
+// The camera-frame normal of the face with vertex indices fv[0..2] (all inside [0, Vtot): a face the walk kept),
+// as raster.hip defines it: (c1 - c0) x (c2 - c0), normalised, negated if n . c0 > 0 (towards the camera). False,
+// and n = 0, for a zero or non-finite cross product.
+__device__ __forceinline__ bool rast_face_normal(const RastCam& cam, const float* __restrict__ verts, const int* fv,
+                                                 double (&n)[3]) {
+  double c0[3], c1[3], c2[3];
+  rast_camera(cam, verts + (size_t)fv[0] * 3, c0);
+  rast_camera(cam, verts + (size_t)fv[1] * 3, c1);
+  rast_camera(cam, verts + (size_t)fv[2] * 3, c2);
+  const double e1[3] = {c1[0] - c0[0], c1[1] - c0[1], c1[2] - c0[2]};
+  const double e2[3] = {c2[0] - c0[0], c2[1] - c0[1], c2[2] - c0[2]};
+  n[0] = e1[1] * e2[2] - e1[2] * e2[1];
+  n[1] = e1[2] * e2[0] - e1[0] * e2[2];
+  n[2] = e1[0] * e2[1] - e1[1] * e2[0];
+  const double len = sqrt((n[0] * n[0] + n[1] * n[1]) + n[2] * n[2]);
+  const bool ok = len > 0.0 && isfinite(len);
+  for (int k = 0; k < 3; ++k) n[k] = ok ? n[k] / len : 0.0;
+  if ((n[0] * c0[0] + n[1] * c0[1]) + n[2] * c0[2] > 0.0)
+    for (int k = 0; k < 3; ++k) n[k] = -n[k];
+  return ok;
+}
+
 struct Span {
   const void* p;
   size_t n;

@@ -38,7 +38,7 @@ from .dataset import PoseDataset
 from .krrn import KRRN
 from .loss import map_losses
 from .metric import Metric, add_metric, rt_errors
-from .pose import get_pose, get_pose_umeyama, refine_pose_icp, select_pose
+from .pose import get_pose, get_pose_umeyama, refine_pose_depth, refine_pose_icp, select_pose
 
 ROT_THR_DEG = 5.0     # trainer.py:156
 TRANS_THR_M = 0.05    # trainer.py:157
@@ -89,7 +89,11 @@ def eval_records(model: KRRN, dataset: PoseDataset, indices: Dict[int, List[int]
     refine: None (the reference's loop), or "icp": the base pose (base_r, base_t) and, with opt_pose, the
     final pose (base_r, pred_t) are each polished by pose.refine_pose_icp against the crop's cloud on the
     pose stream before their ADD(-S) and rotation / translation errors (two more launches per batch; the
-    final pose then carries its own refined R). max_dist = icp.DIST_FRAC x the object's diameter.
+    final pose then carries its own refined R). max_dist = icp.DIST_FRAC x the object's diameter. "depth" polishes
+    the same two poses by pose.refine_pose_depth instead: render-based point-to-plane refinement against the observed
+    depth frame (include/krrn_hip.h: krrn_pose_refine_depth_f32), with max_dist = depth_refine.DIST_FRAC x the
+    diameter and the twist's radius = diameter / 2. It needs a dataset with meshes (ValueError otherwise) and builds
+    its batches with verify=True.
 
     bop: also the BOP-19 errors (bop.bop_errors: VSD, MSSD, MSPD) of the final pose, i.e. (fin_r, pred_t) with
     opt_pose and the base pose without, as test_dis chooses; queued on the pose stream after add_metric and
@@ -104,21 +108,23 @@ def eval_records(model: KRRN, dataset: PoseDataset, indices: Dict[int, List[int]
     select: None, or "depth" (needs opt_pose and a dataset with meshes; ValueError otherwise): the final pose is
     chosen per crop by pose.select_pose (render-and-compare against the observed depth and the crop's mask_label;
     include/krrn_hip.h: krrn_pose_score_f32) among, in priority order, 0 the pose test_dis scores today (fin_r,
-    pred_t), the ICP-refined one with refine="icp"; 1 the base pose; and with refine="icp" also 2 the unrefined
+    pred_t), the refined one with refine="icp" / "depth"; 1 the base pose; and with a refiner also 2 the unrefined
     (PnP R, raw pred_t) and 3 the unrefined base pose. The winner replaces the final pose for add_f, r_f / t_f,
     the BOP errors and the pose table; the base columns are untouched. One more launch per batch on the pose
     stream, no host round trip. The return value then ends with an f64 [n, len(SEL_REC)] table in the same row
     order, read back in the epoch's single read-back. With select=None nothing changes."""
     if pose_solver not in ("pnp", "umeyama"):
         raise ValueError(f"pose_solver must be 'pnp' or 'umeyama', got {pose_solver!r}")
-    if refine not in (None, "icp"):
-        raise ValueError(f"refine must be None or 'icp', got {refine!r}")
+    if refine not in (None, "icp", "depth"):
+        raise ValueError(f"refine must be None, 'icp' or 'depth', got {refine!r}")
     if select not in (None, "depth"):
         raise ValueError(f"select must be None or 'depth', got {select!r}")
     if select and not opt_pose:
         raise ValueError("select='depth' chooses the final pose: it needs opt_pose=True")
     if select and not getattr(dataset, "meshes", False):
         raise ValueError("select='depth' renders the objects' meshes: it needs a dataset with meshes=True")
+    if refine == "depth" and not getattr(dataset, "meshes", False):
+        raise ValueError("refine='depth' renders the objects' meshes: it needs a dataset with meshes=True")
     solve_pose = get_pose if pose_solver == "pnp" else get_pose_umeyama
     metric = Metric(dataset.sym_obj)
     pending = []
@@ -134,7 +140,7 @@ def eval_records(model: KRRN, dataset: PoseDataset, indices: Dict[int, List[int]
     def build(j):
         side.wait_stream(main)  # the inputs' pinned staging and allocations follow earlier work
         with torch.cuda.stream(side):
-            if select:
+            if select or refine == "depth":
                 d = dataset.batch(batches[j][1], device, verify=True)
             else:
                 d = dataset.batch(batches[j][1], device, bop=True) if bop else dataset.batch(batches[j][1], device)
@@ -174,9 +180,11 @@ def eval_records(model: KRRN, dataset: PoseDataset, indices: Dict[int, List[int]
                 r0, t0, raw_t = base_r, base_t, pred_t  # the solver's and TBase's own, before any refinement
                 if refine:
                     d = dia[data["cls_id"].reshape(B)]
-                    base_r, base_t = refine_pose_icp(r0, base_t.reshape(B, 3), data, diameter=d)
+                    polish = ((lambda r, t: refine_pose_icp(r, t, data, diameter=d)) if refine == "icp" else
+                              (lambda r, t: refine_pose_depth(r, t, data, dataset, d)))
+                    base_r, base_t = polish(r0, base_t.reshape(B, 3))
                     if opt_pose:
-                        fin_r, pred_t = refine_pose_icp(r0, pred_t, data, diameter=d)
+                        fin_r, pred_t = polish(r0, pred_t)
                 add_b = add_metric(base_r, base_t.reshape(B, 3), data["model_points"], data["target"],
                                    data["cls_id"], metric.sys)
                 if select:

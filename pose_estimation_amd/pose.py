@@ -19,7 +19,7 @@ from typing import Dict, Optional
 import torch
 
 from .runtime import Immediate, Plan, RngStream, device_seed, h2d, ptr
-from . import icp, umeyama, verify
+from . import depth_refine, icp, umeyama, verify
 
 NUM_POINTS = 256
 N_HYP = 100
@@ -182,6 +182,34 @@ def select_pose(cands, data, dataset, tau=None):
                              data["bop_depth"], data["bop_frame"], verify.TAU if tau is None else tau,
                              mask=data["verify_mask"], box=data["bbox"].to(torch.int32))
     return {"R": out["R"], "t": out["t"], "best": out["best"], "score": out["score"], "counts": out["counts"]}
+
+
+def refine_pose_depth(R: torch.Tensor, t: torch.Tensor, data, dataset, diameter, use_mask: bool = False,
+                      max_dist=None, radius=None, max_iter: int = depth_refine.MAX_ITER,
+                      tol: float = depth_refine.TOL, min_pairs: int = depth_refine.MIN_PAIRS,
+                      damp: float = depth_refine.DAMP, return_info: bool = False):
+    """(R [B, 3, 3], t [B, 3]) polished by render-based point-to-plane refinement on the observed depth frame
+    (depth_refine.refine; include/krrn_hip.h: krrn_pose_refine_depth_f32). `data` is dataset.batch(indices, device,
+    verify=True); `diameter` per crop (a float or a [B] tensor, metres) gives max_dist = depth_refine.DIST_FRAC x
+    diameter and the twist's radius = diameter / 2 unless they are given. use_mask keeps only pixels of the crop's
+    mask_label frame. Queued on the current stream, nothing is read back. The reference has no such step: the
+    defaults are this project's choices (depth_refine.py)."""
+    if "verify_mask" not in data or "bop_depth" not in data:
+        raise ValueError("refine_pose_depth needs a batch made with dataset.batch(indices, device, verify=True)")
+    if not (isinstance(R, torch.Tensor) and isinstance(t, torch.Tensor) and R.is_cuda and t.is_cuda):
+        raise RuntimeError("refine_pose_depth runs on the HIP path only (R / t must be GPU tensors)")
+    dia = diameter.to(torch.float64) if isinstance(diameter, torch.Tensor) else float(diameter)
+    if max_dist is None:
+        max_dist = depth_refine.DIST_FRAC * dia
+    if radius is None:
+        radius = depth_refine.RADIUS_FRAC * dia
+    dev = R.device
+    B = R.shape[0]
+    mesh = dataset._mesh_for(dev)
+    return depth_refine.refine(mesh["verts"], mesh["faces"], data["bop_face_range"], R, t.reshape(B, 3),
+                               data["intrinsic"], data["bop_depth"], data["bop_frame"], max_dist, radius,
+                               mask=data["verify_mask"] if use_mask else None, max_iter=max_iter, tol=tol,
+                               min_pairs=min_pairs, damp=damp, return_info=return_info)
 
 
 def add_icp_ops(plan: Plan, R: torch.Tensor, t: torch.Tensor, cloud: torch.Tensor, model: torch.Tensor,
