@@ -644,6 +644,36 @@ int krrn_bop_mssd_mspd_f32(const float* verts, int Vtot, const int* vert_range, 
                            const double* syms, int NStot, const int* sym_range, int B, double* ws, double* mssd,
                            double* mspd, int* sym_idx, void* stream);
 
+/* Matching estimates to ground-truth instances, the BOP toolkit's match_poses (greedy, not an optimal
+ * assignment), for G groups at once; a group is one (scene, image, object) target. score f64 [Etot] the
+ * estimates' confidences; est_range int32 [G][2] = (first estimate, n_est) into score; gt_range int32 [G][2] =
+ * (first instance, n_gt) into the instance axis of `match`; pair_off int32 [G] = the group's first row in err f64
+ * [Ptot][C]: a group owns n_est n_gt rows, estimate-major, row(e, j) = pair_off + e n_gt + j. The C columns are the
+ * error functions (T VSD taus, then MSSD, then MSPD: 3 <= C <= 18); thr f64 [G][C][NT] the thresholds of
+ * correctness, 1 <= NT <= 16, per group because MSSD's scale with the object's diameter; n_top int32 [G]: only the
+ * n_top best-scored estimates of the group take part, a value <= 0 means all of them. Each cell (g, c, k) is matched
+ * on its own:
+ *   order the group's estimates by score descending, ties to the lower index, a NaN score as -inf; keep the first
+ *   n_top; for each estimate e in that order, among the group's still unmatched instances j with
+ *   err[row(e, j)][c] < thr[g][c][k] (strict; a NaN error never matches) take the one with the lowest error, ties
+ *   to the lowest j, and mark it matched.
+ * Outputs, every element written by the call, for empty groups as well: match int32 [GTtot][C][NT] = the global
+ * index (into score) of the estimate matched to that instance, or -1; tp int32 [G][C][NT] = the number of matched
+ * instances. The groups' instance ranges must not overlap; an instance that no group owns keeps what the buffer
+ * held. Limits: n_est <= max_est <= 128 and n_gt <= max_gt <= 128, which the caller states because the ranges are
+ * device memory. The kernel honours them: a group with n_est > max_est, n_gt > max_gt, a negative range, estimates
+ * past Etot or pair rows past Ptot is matched as a group without estimates (tp 0, its instances -1), and an
+ * instance range that leaves [0, GTtot) owns no instance; nothing outside the buffers is read or written.
+ * Comparisons only (no arithmetic on errors or scores), no atomics, one block per group: the result is
+ * bit-reproducible and a group's outputs do not depend on the rest of the batch. Host checks, before any HIP call:
+ * null est_range / gt_range / pair_off / thr / n_top / tp, null score with Etot > 0, err with Ptot > 0 or match with
+ * GTtot > 0 KRRN_EARG; G, Etot, GTtot or Ptot < 0, Ptot > INT32_MAX, C outside 3..18, NT outside 1..16, max_est or
+ * max_gt outside 0..128 KRRN_ESHAPE; G == 0 returns 0 and launches nothing. */
+int krrn_bop_match_f64(const double* score, int Etot, const double* err, long long Ptot, int C,
+                       const int* est_range, const int* gt_range, const int* pair_off, const double* thr, int NT,
+                       const int* n_top, int G, int GTtot, int max_est, int max_gt, int* match, int* tp,
+                       void* stream);
+
 /* Pose verification by render-and-compare: C candidate poses per crop scored against the observed depth frame
  * and the detector's mask, without a ground-truth pose, and the best one selected. verts / faces / face_range /
  * K4 / depth / frame / depth_scale as krrn_bop_vsd_f32; R f64 [B][C][9], t f64 [B][C][3], 1 <= C <= 8; mask u8

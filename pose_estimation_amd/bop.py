@@ -18,8 +18,13 @@ departure: pixels are sampled at their integer coordinates, this project's raste
 rule. Its two stated departures from those scripts: bbox_obj is clipped to the frame (BOP renders the silhouette
 into a 3 x larger window), and pixels are sampled at their integer coordinates, as everywhere in this project.
 
-Multi-instance matching is out of scope: LineMOD's eval has one estimate per target, so recall is
-correct / targets.
+fold_bop scores one estimate per target against the GT pose it was cropped from (LineMOD's eval: recall is
+correct / targets). match_poses is the BOP toolkit's greedy match_poses for many targets at once: it matches a
+target's estimates to its GT instances per error function and threshold (krrn_bop_match_f64), and
+bop_scene.eval_results builds the protocol's recalls for a result file on it.
+
+    m = match_poses(score, err, est_range, gt_range, pair_off, thr, n_top, n_inst)
+    # -> {"match": int32 [n_inst, C, NT] (estimate index or -1), "tp": int32 [G, C, NT]}
 """
 from __future__ import annotations
 
@@ -154,6 +159,47 @@ def mssd_mspd(verts: torch.Tensor, vert_range: torch.Tensor, R_est: torch.Tensor
     return out
 
 
+MATCH_MAX = 128                                         # kMatchMax of csrc/bop_match.hip: estimates / instances per group
+MAX_NT = 16                                             # kMatchMaxNT: thresholds of correctness per error function
+
+
+def match_poses(score: torch.Tensor, err: torch.Tensor, est_range: torch.Tensor, gt_range: torch.Tensor,
+                pair_off: torch.Tensor, thr: torch.Tensor, n_top: torch.Tensor, n_inst: int, device=None,
+                max_est: int = MATCH_MAX, max_gt: int = MATCH_MAX) -> Dict[str, torch.Tensor]:
+    """krrn_bop_match_f64 for G groups (include/krrn_hip.h states the matching): score [Etot], err [Ptot, C],
+    est_range / gt_range [G, 2], pair_off [G], thr [G, C, NT] and n_top [G] may be host or GPU tensors (staged
+    here); n_inst = the length of the instance axis. `device` is needed only when every operand is a host tensor.
+    max_est / max_gt are the limits that the caller states for the ranges (they are device memory to the entry
+    point); a group that breaks them is matched as one without estimates. Returns {"match": int32 [n_inst, C, NT]
+    (the matched estimate's index into score, or -1), "tp": int32 [G, C, NT]} on the device. Nothing is read back.
+    ValueError: more than 2^31 - 1 pair rows, or shapes that do not fit together."""
+    if device is None:
+        device = next((x.device for x in (err, score, thr) if x.is_cuda), None)
+    if device is None or torch.device(device).type != "cuda":
+        raise RuntimeError("match_poses runs on the HIP path only (a GPU tensor or device= is needed)")
+    dev = torch.device(device)
+    if err.dim() != 2 or thr.dim() != 3 or thr.shape[1] != err.shape[1]:
+        raise ValueError(f"err must be [Ptot, C] and thr [G, C, NT], got {tuple(err.shape)} and {tuple(thr.shape)}")
+    P, C = int(err.shape[0]), int(err.shape[1])
+    G, NT = int(thr.shape[0]), int(thr.shape[2])
+    if P > 2 ** 31 - 1:
+        raise ValueError(f"{P} pair rows do not fit int32: match fewer groups per call")
+    if not (est_range.numel() == 2 * G and gt_range.numel() == 2 * G and pair_off.numel() == G and n_top.numel() == G):
+        raise ValueError(f"est_range / gt_range must be [{G}, 2] and pair_off / n_top [{G}]")
+    sc = h2d(score.reshape(-1), dev, torch.float64)
+    er = h2d(err, dev, torch.float64)
+    e_r = h2d(est_range.reshape(G, 2), dev, torch.int32)
+    g_r = h2d(gt_range.reshape(G, 2), dev, torch.int32)
+    po = h2d(pair_off.reshape(G), dev, torch.int32)
+    th = h2d(thr, dev, torch.float64)
+    nt = h2d(n_top.reshape(G), dev, torch.int32)
+    out = {"match": torch.empty((int(n_inst), C, NT), dtype=torch.int32, device=dev),
+           "tp": torch.empty((G, C, NT), dtype=torch.int32, device=dev)}
+    _lib.call("krrn_bop_match_f64", ptr(sc), sc.shape[0], ptr(er), P, C, ptr(e_r), ptr(g_r), ptr(po), ptr(th), NT,
+              ptr(nt), G, int(n_inst), int(max_est), int(max_gt), ptr(out["match"]), ptr(out["tp"]), stream_ptr(dev))
+    return out
+
+
 def _axis_rotation(axis, angle: float) -> np.ndarray:
     a = np.asarray(axis, np.float64).reshape(3)
     a = a / np.linalg.norm(a)
@@ -237,6 +283,21 @@ def _recalls(rec: np.ndarray, dia: np.ndarray, width: float, missed: Optional[in
     ar_mspd = float(np.mean([(rec[:, _B["mspd"]] < t * (width / 640.0)).sum() / n for t in THETAS_PX]))
     return {"AR_VSD": ar_vsd, "AR_MSSD": ar_mssd, "AR_MSPD": ar_mspd, "AR": (ar_vsd + ar_mssd + ar_mspd) / 3.0,
             "count": int(count), **extra}
+
+
+def recalls_from_tp(tp: np.ndarray, targets: int, count: int) -> Dict[str, float]:
+    """_recalls' six keys (with "targets") from matched-instance counts instead of records: tp integer [T + 2, NT] =
+    the instances matched per error function (T VSD taus, MSSD, MSPD) and threshold of correctness, summed over the
+    targets (bop_scene.eval_results). The averages are taken in _recalls' order, so that one estimate per target
+    gives the same floats."""
+    n, T = int(targets), tp.shape[0] - 2
+    if n == 0 or count == 0:
+        return {"AR_VSD": 0.0, "AR_MSSD": 0.0, "AR_MSPD": 0.0, "AR": 0.0, "count": int(count), "targets": n}
+    ar_vsd = float(np.mean([tp[:T, k].sum() / (n * T) for k in range(tp.shape[1])]))
+    ar_mssd = float(np.mean([tp[T, k] / n for k in range(tp.shape[1])]))
+    ar_mspd = float(np.mean([tp[T + 1, k] / n for k in range(tp.shape[1])]))
+    return {"AR_VSD": ar_vsd, "AR_MSSD": ar_mssd, "AR_MSPD": ar_mspd, "AR": (ar_vsd + ar_mssd + ar_mspd) / 3.0,
+            "count": int(count), "targets": n}
 
 
 def fold_bop(records, objlist: Sequence[int], diameter: Sequence[float], width: float = FRAME_W,

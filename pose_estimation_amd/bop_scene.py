@@ -25,9 +25,17 @@ gt_detections(tree) writes a tree's own ground truth as detections, an upper-bou
     rows = read_detections("/data/lmo/detections.json"); write_detections("mine.json", rows)
     tree = BopTree("/data/lmo", targets=..., detections="/data/lmo/detections.json", det_min_score=0.1)
 
-Out of scope: matching several estimates to several instances of one object in an image (a target's
-`inst_count` > 1: every kept GT instance is one item with one estimate; with detections such a target is refused)
-and binary PLY."""
+Scoring a result file. eval_results(dataset, rows, device) is the counterpart of the BOP toolkit's
+eval_bop19_pose: per (scene, image, object) target the `inst_count` best-scored rows are greedily matched to the
+target's kept GT instances (bop.match_poses, on the GPU, once per error function and threshold of correctness)
+and recall is matched instances over kept instances, so a target may hold an object several times and a file may
+hold several rows per target. BopTree(..., det_per_target="inst_count") makes one item of each of a target's
+`inst_count` best detections, which is how such a file comes out of evaluate.test_epoch(..., match=True).
+
+    ds = PoseDataset("test", 1000, False, "/data/tless", layout="bop", targets=..., meshes=True)
+    res = eval_results(ds, read_results("krrn_tless-test.csv"), "cuda:0")     # AR_VSD / AR_MSSD / AR_MSPD / AR, ...
+
+Out of scope: binary PLY."""
 from __future__ import annotations
 
 import json
@@ -103,18 +111,37 @@ class BopTree:
     A kept target without a detection yields no item and is listed in `missed` as (scene, im, obj); `objlist` stays
     the kept targets'. `det_stats` = {"rows", "used", "unused", "dropped"}: all rows, those paired, those not chosen
     for any kept target, those dropped before pairing. ValueError: a segmentation whose size is not the tree's frame
-    size or whose runs do not fill it, and two or more kept instances of one object in one image."""
+    size or whose runs do not fill it, and two or more kept instances of one object in one image.
+
+    Whatever the detection mode, `instances` holds the kept GT instances (what `items` is without detections) and
+    `inst_count` = {(scene, im, obj): n} the kept targets' instance counts: the targets file's own `inst_count` where
+    a file is given, else the number of kept instances. eval_results matches against these.
+
+    det_per_target: "best" (the pairing above, its refusal of multi-instance targets included) or "inst_count". With
+    "inst_count" every kept target contributes one item per detection among its `inst_count` best rows (the same
+    qualifying rule, score descending, ties to the earlier row); the items stand target by target in the order of
+    `instances`, each target's by rank, with the crop box, score and runs of their row as above. An item still needs
+    GT keys for the per-crop ADD records and the map losses: it takes those of the target's kept instance whose
+    bbox_visib has the highest IoU with the detection's box (ties to the lowest GT index; two items may take the
+    same instance). That association is provisional: it feeds only those columns, and no BOP recall reads it
+    (eval_results matches estimates to instances by their pose errors). A target with fewer qualifying rows than
+    `inst_count` adds its key to `missed` once per missing estimate, so len(items) + len(missed) is the sum of
+    `inst_count`; `det_stats` keeps its meaning ("used" = the rows that became items)."""
 
     def __init__(self, root: str, split: str = "test", targets: Optional[str] = None,
                  objlist: Optional[Sequence[int]] = None, n_model_pts: int = 2600, seed: int = 0, meshes: bool = False,
-                 min_visib: float = 0.1, detections=None, det_min_score: float = 0.0):
+                 min_visib: float = 0.1, detections=None, det_min_score: float = 0.0, det_per_target: str = "best"):
+        if det_per_target not in ("best", "inst_count"):
+            raise ValueError(f"det_per_target must be 'best' or 'inst_count', got {det_per_target!r}")
         self.root, self.split = root, split
+        self.det_per_target = det_per_target
         self.missed: List[Tuple[int, int, int]] = []
         self.det_stats: Optional[Dict[str, int]] = None
         want = None
         if targets is not None:
             with open(targets) as f:
-                want = {(int(e["scene_id"]), int(e["im_id"]), int(e["obj_id"])) for e in json.load(f)}
+                want = {(int(e["scene_id"]), int(e["im_id"]), int(e["obj_id"])): int(e.get("inst_count", 0))
+                        for e in json.load(f)}
         keep_obj = None if objlist is None else {int(o) for o in objlist}
         self.items: List[Dict[str, object]] = []
         self.frame_hw: Optional[Tuple[int, int]] = None
@@ -149,7 +176,16 @@ class BopTree:
             from PIL import Image
             with Image.open(os.path.join(root, split, f"{int(it['scene']):06d}", "depth", f"{int(it['im']):06d}.png")) as di:
                 self.frame_hw = (di.size[1], di.size[0])
-        if detections is not None:
+        self.instances: List[Dict[str, object]] = list(self.items)
+        self.inst_count: Dict[Tuple[int, int, int], int] = {}
+        for it in self.instances:
+            key = (int(it["scene"]), int(it["im"]), int(it["obj"]))
+            self.inst_count[key] = self.inst_count.get(key, 0) + 1
+        if want is not None:  # the targets file's own count, where it states one
+            self.inst_count = {k: (want[k] if want[k] > 0 else n) for k, n in self.inst_count.items()}
+        if detections is not None and det_per_target == "inst_count":
+            self._pair_counted(detections, float(det_min_score))
+        elif detections is not None:
             self._pair(detections, float(det_min_score))
         self.info, mesh = load_models(root, self.objlist, faces=meshes)
         self.mesh: Dict[int, Tuple[np.ndarray, np.ndarray]] = mesh if meshes else {}
@@ -197,21 +233,54 @@ class BopTree:
             if key not in best:
                 self.missed.append(key)
                 continue
-            r = rows[best[key]]
-            seg = r.get("segmentation")
-            if seg is None:
-                runs = rle.box_counts(*r["bbox"], H, W)
-            else:
-                if tuple(seg["size"]) != (H, W):
-                    raise ValueError(f"detection {best[key]}: segmentation.size {list(seg['size'])} is not the tree's "
-                                     f"frame size {[H, W]}")
-                runs = list(seg["counts"])
-                if min(runs) < 0 or sum(runs) != H * W:
-                    raise ValueError(f"detection {best[key]}: its runs do not fill the {H} x {W} frame")
-            items.append(dict(it, bbox=[float(v) for v in r["bbox"]], score=float(r["score"]), det=best[key], rle=runs))
+            items.append(self._det_item(it, rows, best[key]))
         self.items = items
         self.det_stats = {"rows": len(rows), "used": len(best), "unused": len(rows) - len(best) - dropped,
                           "dropped": dropped}
+
+    def _det_item(self, it, rows, j: int) -> Dict[str, object]:
+        """The GT instance `it` as an item whose box, score and mask runs are detection row j's."""
+        H, W = self.frame_hw if self.frame_hw else (0, 0)
+        r = rows[j]
+        seg = r.get("segmentation")
+        if seg is None:
+            runs = rle.box_counts(*r["bbox"], H, W)
+        else:
+            if tuple(seg["size"]) != (H, W):
+                raise ValueError(f"detection {j}: segmentation.size {list(seg['size'])} is not the tree's "
+                                 f"frame size {[H, W]}")
+            runs = list(seg["counts"])
+            if min(runs) < 0 or sum(runs) != H * W:
+                raise ValueError(f"detection {j}: its runs do not fill the {H} x {W} frame")
+        return dict(it, bbox=[float(v) for v in r["bbox"]], score=float(r["score"]), det=j, rle=runs)
+
+    def _pair_counted(self, detections, min_score: float) -> None:
+        """det_per_target="inst_count" (class doc): per kept target its inst_count best rows, one item each."""
+        rows = read_detections(detections) if isinstance(detections, (str, os.PathLike)) else _check_rows(detections, "rows")
+        groups: Dict[Tuple[int, int, int], List[Dict[str, object]]] = {}
+        for it in self.instances:
+            groups.setdefault((int(it["scene"]), int(it["im"]), int(it["obj"])), []).append(it)
+        cand: Dict[Tuple[int, int, int], List[int]] = {k: [] for k in groups}
+        dropped = 0
+        for j, r in enumerate(rows):
+            seg = r.get("segmentation")
+            if r["bbox"][2] <= 0 or r["bbox"][3] <= 0 or (seg is not None and sum(seg["counts"][1::2]) <= 0):
+                dropped += 1
+                continue
+            key = (r["scene_id"], r["image_id"], r["category_id"])
+            if key in cand and r["score"] >= min_score:
+                cand[key].append(j)
+        items, used = [], 0
+        for key, inst in groups.items():
+            n = self.inst_count[key]
+            top = sorted(cand[key], key=lambda j: -rows[j]["score"])[:n]     # stable: a tie keeps the earlier row
+            for j in top:
+                ious = [_box_iou(it["bbox"], rows[j]["bbox"]) for it in inst]
+                items.append(self._det_item(inst[int(np.argmax(ious))], rows, j))   # argmax: the lowest GT index on ties
+            used += len(top)
+            self.missed += [key] * (n - len(top))
+        self.items = items
+        self.det_stats = {"rows": len(rows), "used": used, "unused": len(rows) - used - dropped, "dropped": dropped}
 
     def has_symmetry(self, obj: int) -> bool:
         oi = self.info.get(obj, {})
@@ -239,6 +308,17 @@ class BopTree:
         it = self.items[i]
         rgb, depth = self.read_image(int(it["scene"]), int(it["im"]), float(it["depth_scale"]))
         return rgb, depth, self.read_mask(i)
+
+
+def _box_iou(a, b) -> float:
+    """Intersection over union of two (x, y, w, h) boxes as plain rectangles; 0.0 without a union."""
+    ax, ay, aw, ah = (float(v) for v in a)
+    bx, by, bw, bh = (float(v) for v in b)
+    iw = max(0.0, min(ax + aw, bx + bw) - max(ax, bx))
+    ih = max(0.0, min(ay + ah, by + bh) - max(ay, by))
+    inter = iw * ih
+    union = max(aw, 0.0) * max(ah, 0.0) + max(bw, 0.0) * max(bh, 0.0) - inter
+    return inter / union if union > 0.0 else 0.0
 
 
 DET_KEYS = ("scene_id", "image_id", "category_id", "score", "bbox")
@@ -417,3 +497,123 @@ def read_results(path: str) -> List[Dict[str, object]]:
         rows.append({"scene_id": int(tok[0]), "im_id": int(tok[1]), "obj_id": int(tok[2]), "score": float(tok[3]),
                      "R": R.reshape(3, 3), "t": t, "time": float(tok[6])})
     return rows
+
+
+def _rank(scores: Sequence[float]) -> List[int]:
+    """Indices by score descending, ties to the lower index, a NaN score as -inf (krrn_bop_match_f64's order)."""
+    key = [float("-inf") if s != s else float(s) for s in scores]
+    return sorted(range(len(key)), key=lambda i: (-key[i], i))
+
+
+def eval_results(dataset, rows, device, chunk_images: int = 32, delta: float = bop.DELTA,
+                 taus: Sequence[float] = bop.TAUS) -> Dict[str, object]:
+    """Score result rows against a tree the way the BOP-19 protocol does (the toolkit's eval_bop19_pose): per
+    (scene, image, object) target the `inst_count` best-scored estimates are greedily matched to the target's GT
+    instances, once per error function and threshold of correctness, and recall = matched instances / kept
+    instances. `dataset` is a PoseDataset(layout="bop", meshes=True); `rows` are result rows as read_results
+    returns them (several per target allowed, t in millimetres).
+
+    The targets are the tree's kept GT instances (BopTree.instances) grouped by (scene, image, object); n_top is
+    BopTree.inst_count. Per chunk of at most `chunk_images` distinct images the depth frames are read once, every
+    group is expanded into its n_est x n_gt (estimate, instance) pairs, bop.vsd and bop.mssd_mspd give the pairs'
+    errors, and bop.match_poses matches every group at the thresholds bop.THETAS (VSD), THETAS x the object's
+    diameter (MSSD) and THETAS_PX x width / 640 (MSPD); the matched counts are summed per object as integers on the
+    device and read back once at the end. A row whose key is no kept target is ignored and counted in "ignored"; a
+    target without rows still counts in the denominator. A target with more than bop.MATCH_MAX rows keeps its
+    MATCH_MAX best-scored ones (the kernel's order), one with more instances than that raises ValueError.
+
+    Returns bop.fold_bop's dict with `missed` (AR_VSD, AR_MSSD, AR_MSPD, AR, "count" = the estimates that took part,
+    "targets" = the kept instances, "per_obj"), plus "ignored" and "matches": per kept instance, in
+    BopTree.instances order, the index in `rows` of the estimate matched to it at the loosest MSSD threshold, or -1.
+    Where every target has one instance and one row this equals fold_bop(..., missed=...) on the same poses."""
+    from .runtime import h2d
+    device = torch.device(device)
+    tree = dataset.tree
+    if getattr(dataset, "layout", "linemod") != "bop" or not getattr(dataset, "meshes", False):
+        raise ValueError("eval_results needs a PoseDataset with layout='bop' and meshes=True")
+    mesh = dataset._mesh_for(device)
+    T, NT, C = len(taus), len(bop.THETAS), len(taus) + 2
+    width = float((tree.frame_hw or (0, bop.FRAME_W))[1])
+    groups: Dict[Tuple[int, int, int], List[int]] = {}
+    for i, it in enumerate(tree.instances):
+        groups.setdefault((int(it["scene"]), int(it["im"]), int(it["obj"])), []).append(i)
+    est: Dict[Tuple[int, int, int], List[int]] = {k: [] for k in groups}
+    ignored = 0
+    for r, row in enumerate(rows):
+        key = (int(row["scene_id"]), int(row["im_id"]), int(row["obj_id"]))
+        if key in est:
+            est[key].append(r)
+        else:
+            ignored += 1
+    count = 0
+    for key, inst in groups.items():
+        if len(inst) > bop.MATCH_MAX:
+            raise ValueError(f"target {key} has {len(inst)} kept instances > {bop.MATCH_MAX}")
+        if len(est[key]) > bop.MATCH_MAX:
+            order = _rank([float(rows[r]["score"]) for r in est[key]])[:bop.MATCH_MAX]
+            est[key] = [est[key][a] for a in sorted(order)]
+        n_top = tree.inst_count[key]
+        count += len(est[key]) if n_top <= 0 else min(n_top, len(est[key]))
+    objs = list(dict.fromkeys(k[2] for k in groups))
+    tp_obj = torch.zeros((max(1, len(objs)), C, NT), dtype=torch.int64, device=device)
+    images = list(dict.fromkeys(k[:2] for k in groups))
+    scale = {(int(it["scene"]), int(it["im"])): float(it["depth_scale"]) for it in tree.instances}
+    th, th_px = np.asarray(bop.THETAS), np.asarray(bop.THETAS_PX)
+    pending = []                                             # per chunk: (instance indices, row indices, match column)
+    step = max(1, int(chunk_images))
+    for lo in range(0, len(images), step):
+        ims = images[lo:lo + step]
+        frame = {im: f for f, im in enumerate(ims)}
+        keys = [k for k in groups if k[:2] in frame]
+        depth = np.stack([tree.read_image(sc, im, scale[(sc, im)])[1] for sc, im in ims])
+        slots, erows, er, gr, po, nt, thr, gobj = [], [], [], [], [], [], [], []
+        Re, te, Rg, tg, K4, fi, fr, vr, sr, dia = [], [], [], [], [], [], [], [], [], []
+        for key in keys:
+            inst, rws, obj = groups[key], est[key], key[2]
+            d = float(tree.info[obj]["diameter"]) / 1000.0
+            er.append((len(erows), len(rws)))
+            gr.append((len(slots), len(inst)))
+            po.append(len(fi))
+            nt.append(tree.inst_count[key])
+            gobj.append(objs.index(obj))
+            thr.append(np.stack([th] * T + [np.array([t * d for t in th]), np.array([t * (width / 640.0) for t in th_px])]))
+            for r in rws:
+                R = np.asarray(rows[r]["R"], np.float64).reshape(9)
+                t = np.asarray(rows[r]["t"], np.float64).reshape(3) / 1000.0
+                for i in inst:
+                    it = tree.instances[i]
+                    Re.append(R), te.append(t), Rg.append(it["R"].reshape(9)), tg.append(it["t"])
+                    K4.append(it["K4"]), fi.append(frame[key[:2]]), dia.append(d)
+                    fr.append(mesh["range"][obj]), vr.append(mesh["vrange"][obj]), sr.append(mesh["srange"][obj])
+            erows += rws
+            slots += inst
+        P = len(fi)
+        if P:
+            f64 = lambda a: torch.from_numpy(np.asarray(a, np.float64))      # noqa: E731
+            i32 = lambda a: torch.tensor(a, dtype=torch.int32)               # noqa: E731
+            Kt = torch.tensor(K4, dtype=torch.float32)
+            pose = (f64(Re), f64(te), f64(Rg), f64(tg))
+            v = bop.vsd(mesh["verts"], mesh["faces"], i32(fr), *pose, Kt, h2d(torch.from_numpy(depth), device), i32(fi),
+                        f64(dia), 1.0, delta, taus)
+            m = bop.mssd_mspd(mesh["verts"], i32(vr), *pose, Kt, mesh["syms"], i32(sr))
+            err = torch.cat([v["e_vsd"], m["mssd"][:, None], m["mspd"][:, None]], 1)
+        else:
+            err = torch.zeros((0, C), dtype=torch.float64, device=device)
+        score = torch.tensor([float(rows[r]["score"]) for r in erows], dtype=torch.float64)
+        res = bop.match_poses(score, err, torch.tensor(er, dtype=torch.int32), torch.tensor(gr, dtype=torch.int32),
+                              torch.tensor(po, dtype=torch.int32), torch.from_numpy(np.stack(thr)),
+                              torch.tensor(nt, dtype=torch.int32), len(slots), device)
+        tp_obj.index_add_(0, h2d(torch.tensor(gobj, dtype=torch.int64), device), res["tp"].to(torch.int64))
+        pending.append((slots, erows, res["match"][:, T, NT - 1]))
+    tp = tp_obj.cpu().numpy()                                # the one read-back of the counts
+    matches = [-1] * len(tree.instances)
+    for slots, erows, col in pending:
+        for i, x in zip(slots, col.cpu().tolist()):
+            matches[i] = erows[x] if x >= 0 else -1
+    n_obj = {o: sum(len(v) for k, v in groups.items() if k[2] == o) for o in objs}
+    c_obj = {o: sum(len(est[k]) if tree.inst_count[k] <= 0 else min(tree.inst_count[k], len(est[k]))
+                    for k in groups if k[2] == o) for o in objs}
+    out: Dict[str, object] = bop.recalls_from_tp(tp[:len(objs)].sum(0), len(tree.instances), count)
+    out["per_obj"] = {o: bop.recalls_from_tp(tp[a], n_obj[o], c_obj[o]) for a, o in enumerate(objs)}
+    out["ignored"], out["matches"] = ignored, matches
+    return out

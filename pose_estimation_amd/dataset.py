@@ -382,14 +382,18 @@ class PoseDataset(torch.utils.data.Dataset):
     from the detection's bbox, no mask PNG is read, and batch() decodes the batch's run-length encoded masks into
     mask_label with one rle.decode on the input stream; everything downstream reads that mask_label unchanged. A
     batch then also carries det_score f32 [B] and det_info int32 [B, 5] (rle.decode's info); the GT keys remain the
-    paired instance's. Targets without a detection are in tree.missed and yield no item."""
+    paired instance's. Targets without a detection are in tree.missed and yield no item.
+    det_per_target="inst_count" (default "best": the above) makes one item of each of a target's `inst_count` best
+    detections instead, so that an image may hold an object several times (bop_scene.BopTree). An item's GT keys are
+    then a provisional association by box IoU: they feed the per-crop ADD records and the map losses only, and no
+    BOP recall reads them (evaluate.test_epoch(..., bop=True) asks for match=True on such a dataset)."""
 
     def __init__(self, mode: str = "test", num_point: int = 1000, add_noise: bool = False, root: Optional[str] = None,
                  noise_trans: float = 0.0, num_kps: int = 8, cls_type: Optional[str] = None, cfg=CONFIG,
                  num_frames: int = 256, seed: int = 0, sizes: Optional[Sequence[int]] = None,
                  n_model_pts: int = 2600, io_threads: int = 8, gt_maps: bool = False, meshes: bool = False,
                  layout: str = "linemod", split: str = "test", targets: Optional[str] = None, min_visib: float = 0.1,
-                 masks: str = "png", detections=None, det_min_score: float = 0.0):
+                 masks: str = "png", detections=None, det_min_score: float = 0.0, det_per_target: str = "best"):
         if layout not in ("linemod", "bop"):
             raise ValueError(f"layout must be 'linemod' or 'bop', got {layout!r}")
         if masks not in ("png", "render"):
@@ -424,7 +428,7 @@ class PoseDataset(torch.utils.data.Dataset):
             self.tree = BopTree(root, split=split, targets=targets,
                                 objlist=None if cls_type in (None, "all") else self.objlist, n_model_pts=n_model_pts,
                                 seed=seed, meshes=self.meshes, min_visib=min_visib, detections=detections,
-                                det_min_score=det_min_score)
+                                det_min_score=det_min_score, det_per_target=det_per_target)
             self.objlist = list(self.tree.objlist)
             self.obj_info = {o: {"min": [e["min_x"], e["min_y"], e["min_z"]], "size": [e["size_x"], e["size_y"], e["size_z"]],
                                  "diameter": e["diameter"]} for o, e in ((o, self.tree.info[o]) for o in self.objlist)}

@@ -33,7 +33,7 @@ import torch.distributed as dist
 
 from . import distributed as kd
 from .bop import BOP_REC, FRAME_W, TAUS, bop_errors, fold_bop
-from .bop_scene import write_results
+from .bop_scene import eval_results, write_results
 from .dataset import PoseDataset
 from .krrn import KRRN
 from .loss import map_losses
@@ -344,7 +344,8 @@ def gather_epoch_records(local: torch.Tensor, shard_sizes: Sequence[int], device
 def test_epoch(model: KRRN, dataset: PoseDataset, bs: int = 64, device=None, opt_pose: bool = True,
                criterion=None, world: Optional[int] = None, rank: Optional[int] = None,
                group=None, pose_solver: str = "pnp", refine: Optional[str] = None,
-               bop: bool = False, bop_csv: Optional[str] = None, select: Optional[str] = None) -> Dict[str, object]:
+               bop: bool = False, bop_csv: Optional[str] = None, select: Optional[str] = None,
+               match: bool = False) -> Dict[str, object]:
     """Trainer.test_epoch over `dataset`. world/rank default to the initialised process group
     (1/0 without one). `criterion` enables the per-crop map-loss terms (dis_xyz / dis_mask /
     dis_normal) when the batches carry GT maps, i.e. for a PoseDataset built with gt_maps=True (a
@@ -365,8 +366,21 @@ def test_epoch(model: KRRN, dataset: PoseDataset, bs: int = 64, device=None, opt
     kept GT targets, "estimated" those with a detection (the crops evaluated), "missed" those without, and the
     detection file's "rows", "unused", "dropped" (BopTree.det_stats)}; the missed targets enter every BOP recall's
     denominator (bop.fold_bop(missed=...): "bop" gains "targets"), and the CSV's score column is the detection's
-    score unless `select` puts the verification score there. Every other key is computed as before."""
+    score unless `select` puts the verification score there. Every other key is computed as before.
+    `match` (off by default: nothing changes; needs bop=True and a dataset with layout="bop") computes "bop" the way the
+    BOP-19 protocol does instead of one estimate against the GT pose it was cropped from: the epoch's poses become
+    result rows exactly as `bop_csv` writes them, and "bop" = bop_scene.eval_results(dataset, rows, device), which
+    matches each target's `inst_count` best rows to its GT instances; every other key is as before. A dataset built
+    with det_per_target="inst_count" has only a provisional crop-to-instance association, so bop=True without
+    match=True raises ValueError on it. With world > 1 rank 0 evaluates the gathered rows and broadcasts the dict
+    (dist.broadcast_object_list)."""
     device = torch.device(device) if device is not None else next(model.parameters()).device
+    if match and not (bop and getattr(dataset, "layout", "linemod") == "bop"):
+        raise ValueError("match=True scores result rows against a BOP tree: it needs bop=True and a PoseDataset with "
+                         "layout='bop'")
+    if bop and not match and getattr(getattr(dataset, "tree", None), "det_per_target", "best") == "inst_count":
+        raise ValueError("a dataset built with det_per_target='inst_count' pairs crops with GT instances only "
+                         "provisionally: bop=True needs match=True on it")
     if world is None:
         world = dist.get_world_size(group) if dist.is_initialized() else 1
     if rank is None:
@@ -379,11 +393,11 @@ def test_epoch(model: KRRN, dataset: PoseDataset, bs: int = 64, device=None, opt
         raise ValueError("bop_csv writes BOP's scene / image ids: it needs a PoseDataset with layout='bop'")
     local = eval_records(model, dataset, mine, bs, device, opt_pose=opt_pose, with_loss=criterion is not None,
                          pose_solver=pose_solver, refine=refine, **({"bop": True} if bop else {}),
-                         **({"poses": True} if bop_csv else {}), **({"select": select} if select else {}))
+                         **({"poses": True} if bop_csv or match else {}), **({"select": select} if select else {}))
     local_bop = local_pose = local_sel = None
     if select:
         local, local_sel = (local[:-1] if len(local) > 2 else local[0]), local[-1]
-    if bop_csv:
+    if bop_csv or match:
         local, local_pose = local[:-1] if bop else local[0], local[-1]
         # gather_epoch_records marks pad rows by a last column `valid` = 0
         local_pose = torch.cat([local_pose, torch.ones((local_pose.shape[0], 1), dtype=torch.float64)], 1)
@@ -416,7 +430,7 @@ def test_epoch(model: KRRN, dataset: PoseDataset, bs: int = 64, device=None, opt
         picked = {int(c): int((tab[:, 1] == c).sum()) for c in sorted(set(tab[:, 1].tolist()))}
         out["select"] = {"picked": picked, "mean_score": float(np.cumsum(tab[:, 2])[-1]) / len(tab) if len(tab) else 0.0}
         conf = {int(r[0]): float(r[2]) for r in tab}
-    if bop_csv:
+    if bop_csv or match:
         allpose = gather_epoch_records(local_pose, shard_sizes, device, group) if world > 1 else local_pose
         if rank == 0:
             tab = allpose.numpy()
@@ -427,7 +441,13 @@ def test_epoch(model: KRRN, dataset: PoseDataset, bs: int = 64, device=None, opt
                 it = dataset.tree.items[int(row[0])]
                 rows.append({"scene_id": it["scene"], "im_id": it["im"], "obj_id": it["obj"], "score": conf.get(int(row[0]), 1.0),
                              "R": row[1:10], "t": row[10:13] * 1000.0, "time": -1.0})
-            write_results(bop_csv, rows)
+            if bop_csv:
+                write_results(bop_csv, rows)
+        if match:  # the protocol's recalls over the rows, in place of the 1 : 1 fold above
+            res = [eval_results(dataset, rows, device)] if rank == 0 else [None]
+            if world > 1:
+                dist.broadcast_object_list(res, src=0, group=group)
+            out["bop"] = res[0]
     if world > 1:
         # the ranks' own crop / success tallies, summed, must equal the gathered table's
         key = "add_f" if opt_pose else "add_b"
