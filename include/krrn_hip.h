@@ -624,6 +624,28 @@ int krrn_bop_visib_u8(const float* verts, int Vtot, const int* faces, int Ftot, 
 int krrn_rle_decode_u8(const int* counts, const int* offs, int n, int H, int W, int* ends, unsigned char* mask,
                        int* info, void* stream);
 
+/* Encode n u8 planes as run-length encoded masks (COCO RLE): the inverse of krrn_rle_decode_u8, and what the host's
+ * rle.encode returns. mask u8 [n][H][W] row-major at any byte address; any non-zero byte is a set pixel. Pixels are
+ * numbered column-major, p = x H + y; v(p) = 1 for a set pixel and v(-1) = 0. The transitions are the p in [0, H W)
+ * with v(p) != v(p - 1), in increasing order t_0 .. t_{T-1}, and the runs are
+ *   t_0, t_1 - t_0, .., t_{T-1} - t_{T-2}, H W - t_{T-1}        (T + 1 of them; the one run H W when T = 0)
+ * so a set pixel (0, 0) gives a leading 0, and set pixels at the bottom of column x and the top of column x + 1 are
+ * one run. Outputs: n_runs int32 [n] = T + 1, always the true count (INT32_MAX where T + 1 would pass it); counts
+ * int32 [n][max_runs]: mask i's runs k < min(n_runs[i], max_runs) in counts[i][k], and 0 in the elements from
+ * n_runs[i] to max_runs, so every element of
+ * counts is written by the call and nothing is written past a mask's slot (a mask with n_runs[i] > max_runs holds the
+ * first max_runs runs: encode again with a larger slot); info int32 [n][5] = (pixel count, x, y, w, h) exactly as
+ * krrn_rle_decode_u8 defines it (w = x_max - x_min, h = y_max - y_min; five zeros for an empty mask). ws: int32
+ * workspace of krrn_rle_encode_ws(n, W) elements (per mask and column: the transitions, set pixels, lowest / highest
+ * set row and last transition of the column, then the index of its first run and the last transition before it).
+ * Integer work without atomics, and no block waits for another: the result is deterministic and a mask's does not
+ * depend on the rest of the batch, bit for bit. Nothing is read back (the call can be captured in a graph). Host
+ * checks, before any HIP call: null mask / ws / counts / n_runs / info (n_ints for _ws) KRRN_EARG; n < 0, H <= 0,
+ * W <= 0, H W > INT32_MAX or max_runs < 1 KRRN_ESHAPE; n == 0 returns 0 and launches nothing. */
+int krrn_rle_encode_ws(int n, int W, long long* n_ints);
+int krrn_rle_encode_u8(const unsigned char* mask, int n, int H, int W, int max_runs, int* ws, int* counts,
+                       int* n_runs, int* info, void* stream);
+
 /* MSSD / MSPD, the maximum symmetry-aware surface / projection distance. verts f32 [Vtot][3] (all mesh
  * vertices), vert_range int32 [B][2] = first vertex, count of crop b; syms f64 [NStot][12] = row-major R
  * then t (metres, model frame), sym_range int32 [B][2] (each object's set begins with the identity). Per

@@ -22,6 +22,8 @@ Drop-in API (the reference's names):
     verify.score_poses / select_pose / test_epoch(select="depth")  pose candidates scored against the observed depth,
                                           the best kept (render-and-compare; this project's own)
     rle.decode / PoseDataset(detections=...)  crops and masks from BOP detection files, RLE masks decoded on the GPU
+    rle.encode_planes / bop_scene.write_gt_coco / test_epoch(seg_json=...)  masks encoded to RLE on the GPU: COCO
+                                          ground truth, and the estimates' masks as a detection file
 """
 from .config import CONFIG, Cfg, make_config  # noqa: F401
 from .krrn import KRRN  # noqa: F401

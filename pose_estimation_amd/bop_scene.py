@@ -4,6 +4,7 @@ calc_gt_masks / calc_gt_info scripts, and BOP's result CSV.
 
     tree = BopTree("/data/lmo", split="test", targets="/data/lmo/test_targets_bop19.json", meshes=True)
     write_gt_info("/data/mine", "test", device, masks=True)      # for a tree that ships no scene_gt_info.json
+    write_gt_coco("/data/mine", "test", device)                  # scene_gt_coco.json: COCO ground truth, RLE masks
     write_results("krrn_lmo-test.csv", rows); rows = read_results("krrn_lmo-test.csv")
 
 A tree is read as follows. `models/models_info.json` (millimetres): per object `diameter`, `min_x/y/z`,
@@ -34,6 +35,10 @@ hold several rows per target. BopTree(..., det_per_target="inst_count") makes on
 
     ds = PoseDataset("test", 1000, False, "/data/tless", layout="bop", targets=..., meshes=True)
     res = eval_results(ds, read_results("krrn_tless-test.csv"), "cuda:0")     # AR_VSD / AR_MSSD / AR_MSPD / AR, ...
+
+Masks of a result file. write_result_masks(path, dataset, rows, device) renders every estimate's visible mask against
+the observed depth (bop.visibility under the estimated pose), encodes it on the GPU (rle.encode_planes) and writes
+the rows in the detection format above: a segmentation result file, which BopTree(..., detections=path) reads back.
 
 Out of scope: binary PLY."""
 from __future__ import annotations
@@ -394,19 +399,10 @@ def _save_json(path: str, content: Dict[int, object]) -> None:
         json.dump({str(k): v for k, v in sorted(content.items())}, f, indent=1)
 
 
-def write_gt_info(root: str, split: str, device, masks: bool = False, delta: float = bop.DELTA, batch: int = 64,
-                  overwrite: bool = False) -> Dict[int, Dict[int, List[Dict[str, object]]]]:
-    """The GPU counterpart of BOP's calc_gt_info / calc_gt_masks for every scene of `root`/`split`:
-    bop.visibility over the scene's GT instances in batches of `batch` (each batch decodes its distinct images
-    once), written as scene_gt_info.json with BOP's six keys (INFO_KEYS) and, with masks=True, the
-    mask/%06d_%06d.png and mask_visib/%06d_%06d.png images (0 / 255). Refuses to overwrite an existing
-    scene_gt_info.json or mask file unless overwrite=True (FileExistsError, before anything is computed for that
-    scene). Returns {scene: {image: [entry per instance]}}. The two departures from BOP's scripts that
-    bop.visibility states apply: bbox_obj is clipped to the frame, and pixels are sampled at integer coordinates."""
-    from PIL import Image
+def _gt_scenes(root: str, split: str, device):
+    """What the ground-truth writers share: (scene ids, {scene: its scene_gt.json}, the objects they name, their
+    meshes concatenated on `device` as (verts, faces), {obj: (first face, faces)})."""
     from .runtime import h2d
-    device = torch.device(device)
-    out = {}
     scenes = scene_ids(root, split)
     objs = set()
     gts = {}
@@ -425,6 +421,44 @@ def write_gt_info(root: str, split: str, device, masks: bool = False, delta: flo
         v0, f0 = v0 + len(v), f0 + len(f)
     verts = h2d(torch.from_numpy(np.concatenate(vs)), device)
     faces = h2d(torch.from_numpy(np.concatenate(fs).astype(np.int32)), device)
+    return scenes, gts, objs, verts, faces, frange
+
+
+def _gt_visibility(sdir: str, cam, part, verts, faces, frange, device, delta: float, masks: bool):
+    """bop.visibility of one batch `part` = [(image, GT index, scene_gt entry)] of a scene: its distinct images'
+    depth frames are read once."""
+    from .runtime import h2d
+    ims = list(dict.fromkeys(im for im, _, _ in part))
+    depth = np.stack([read_depth(sdir, im, float(cam[im].get("depth_scale", 1.0))) for im in ims])
+    K = [[float(k) for k in cam[im]["cam_K"]] for im, _, _ in part]
+    return bop.visibility(
+        verts, faces, torch.tensor([frange[int(e["obj_id"])] for _, _, e in part], dtype=torch.int32),
+        torch.tensor(np.stack([np.array(e["cam_R_m2c"], np.float64).reshape(3, 3) for _, _, e in part])),
+        torch.tensor(np.stack([np.array(e["cam_t_m2c"], np.float64) / 1000.0 for _, _, e in part])),
+        torch.tensor([[k[0], k[4], k[2], k[5]] for k in K], dtype=torch.float32),
+        h2d(torch.from_numpy(depth), device), torch.tensor([ims.index(im) for im, _, _ in part], dtype=torch.int32),
+        1.0, delta, masks=masks)
+
+
+def _info_entry(q: Sequence[int], fract: float) -> Dict[str, object]:
+    """One scene_gt_info.json entry from a row of bop.visibility's info (ints) and its visib_fract."""
+    return {"bbox_obj": q[3:7], "bbox_visib": q[7:11], "px_count_all": q[0], "px_count_valid": q[1],
+            "px_count_visib": q[2], "visib_fract": float(fract)}
+
+
+def write_gt_info(root: str, split: str, device, masks: bool = False, delta: float = bop.DELTA, batch: int = 64,
+                  overwrite: bool = False) -> Dict[int, Dict[int, List[Dict[str, object]]]]:
+    """The GPU counterpart of BOP's calc_gt_info / calc_gt_masks for every scene of `root`/`split`:
+    bop.visibility over the scene's GT instances in batches of `batch` (each batch decodes its distinct images
+    once), written as scene_gt_info.json with BOP's six keys (INFO_KEYS) and, with masks=True, the
+    mask/%06d_%06d.png and mask_visib/%06d_%06d.png images (0 / 255). Refuses to overwrite an existing
+    scene_gt_info.json or mask file unless overwrite=True (FileExistsError, before anything is computed for that
+    scene). Returns {scene: {image: [entry per instance]}}. The two departures from BOP's scripts that
+    bop.visibility states apply: bbox_obj is clipped to the frame, and pixels are sampled at integer coordinates."""
+    from PIL import Image
+    device = torch.device(device)
+    out = {}
+    scenes, gts, _, verts, faces, frange = _gt_scenes(root, split, device)
     for sc in scenes:
         sdir = os.path.join(root, split, f"{sc:06d}")
         ipath = os.path.join(sdir, "scene_gt_info.json")
@@ -442,27 +476,139 @@ def write_gt_info(root: str, split: str, device, masks: bool = False, delta: flo
         entries = {im: [None] * len(gts[sc][im]) for im in gts[sc]}
         for lo in range(0, len(inst), max(1, int(batch))):
             part = inst[lo:lo + max(1, int(batch))]
-            ims = list(dict.fromkeys(im for im, _, _ in part))
-            depth = np.stack([read_depth(sdir, im, float(cam[im].get("depth_scale", 1.0))) for im in ims])
-            K = [[float(k) for k in cam[im]["cam_K"]] for im, _, _ in part]
-            res = bop.visibility(
-                verts, faces, torch.tensor([frange[int(e["obj_id"])] for _, _, e in part], dtype=torch.int32),
-                torch.tensor(np.stack([np.array(e["cam_R_m2c"], np.float64).reshape(3, 3) for _, _, e in part])),
-                torch.tensor(np.stack([np.array(e["cam_t_m2c"], np.float64) / 1000.0 for _, _, e in part])),
-                torch.tensor([[k[0], k[4], k[2], k[5]] for k in K], dtype=torch.float32),
-                h2d(torch.from_numpy(depth), device), torch.tensor([ims.index(im) for im, _, _ in part], dtype=torch.int32),
-                1.0, delta, masks=masks)
+            res = _gt_visibility(sdir, cam, part, verts, faces, frange, device, delta, masks)
             info, fract = res["info"].cpu().numpy(), res["visib_fract"].cpu().numpy()   # one read-back per batch
             planes = {k: res[k].cpu().numpy() for k in ("mask", "mask_visib")} if masks else {}
             for j, (im, g, _) in enumerate(part):
-                q = [int(x) for x in info[j]]
-                entries[im][g] = {"bbox_obj": q[3:7], "bbox_visib": q[7:11], "px_count_all": q[0], "px_count_valid": q[1],
-                                  "px_count_visib": q[2], "visib_fract": float(fract[j])}
+                entries[im][g] = _info_entry([int(x) for x in info[j]], fract[j])
                 for sub, pl in planes.items():
                     Image.fromarray(pl[j] * np.uint8(255)).save(os.path.join(sdir, sub, f"{im:06d}_{g:06d}.png"))
         _save_json(ipath, entries)
         out[sc] = entries
     return out
+
+
+def write_gt_coco(root: str, split: str, device, visib: bool = True, min_visib: float = 0.1, batch: int = 64,
+                  overwrite: bool = False) -> Dict[int, Dict[str, object]]:
+    """The GPU counterpart of BOP's calc_gt_coco for every scene of `root`/`split`: COCO ground truth with the
+    instances' masks as compressed RLE. Per scene bop.visibility over the GT instances in batches of `batch`, as
+    write_gt_info runs it, then rle.encode_planes of the batch's mask_visib planes (visib=False: the full
+    silhouettes `mask`), so only the runs leave the device. Written as scene_gt_coco.json:
+      "images"       id = the image id, file_name relative to the scene directory (rgb/%06d.png, or .jpg where the
+                     tree holds that), width, height
+      "annotations"  id (1, 2, .. in image and GT order), image_id, category_id = obj_id, iscrowd 0, area = the
+                     plane's pixel count, bbox = the instance's bbox_visib (bbox_obj with visib=False) as write_gt_info
+                     gives it, segmentation = {"counts": COCO's compressed string, "size": [H, W]}, ignore =
+                     visib_fract < min_visib
+      "categories"   id, name "%d" for every object of the split's ground truth
+    Refuses to overwrite an existing scene_gt_coco.json unless overwrite=True (FileExistsError, before anything is
+    computed for that scene). Returns {scene: that dict}. The layout is written from the published COCO / BOP
+    formats and is not checked against the BOP toolkit's own output (the toolkit is not a dependency). The two
+    departures from BOP's scripts that bop.visibility states apply: bbox_obj is clipped to the frame, and pixels are
+    sampled at integer coordinates."""
+    device = torch.device(device)
+    out = {}
+    scenes, gts, objs, verts, faces, frange = _gt_scenes(root, split, device)
+    plane, px, box = ("mask_visib", 2, slice(7, 11)) if visib else ("mask", 0, slice(3, 7))
+    for sc in scenes:
+        sdir = os.path.join(root, split, f"{sc:06d}")
+        cpath = os.path.join(sdir, "scene_gt_coco.json")
+        if os.path.exists(cpath) and not overwrite:
+            raise FileExistsError(f"{cpath} exists (overwrite=True replaces it)")
+        cam = _load_json(os.path.join(sdir, "scene_camera.json"))
+        inst = [(im, g, e) for im in sorted(gts[sc]) for g, e in enumerate(gts[sc][im])]
+        images, annotations = {}, []
+        for lo in range(0, len(inst), max(1, int(batch))):
+            part = inst[lo:lo + max(1, int(batch))]
+            res = _gt_visibility(sdir, cam, part, verts, faces, frange, device, bop.DELTA, True)
+            H, W = (int(v) for v in res[plane].shape[1:])
+            runs = rle.encode_planes(res[plane])
+            info, fract = res["info"].cpu().numpy(), res["visib_fract"].cpu().numpy()
+            for j, (im, g, e) in enumerate(part):
+                if im not in images:
+                    jpg = not os.path.exists(os.path.join(sdir, "rgb", f"{im:06d}.png")) and os.path.exists(
+                        os.path.join(sdir, "rgb", f"{im:06d}.jpg"))
+                    images[im] = {"id": im, "file_name": f"rgb/{im:06d}{'.jpg' if jpg else '.png'}", "width": W, "height": H}
+                q = [int(x) for x in info[j]]
+                annotations.append({"id": len(annotations) + 1, "image_id": im, "category_id": int(e["obj_id"]),
+                                    "iscrowd": 0, "area": q[px], "bbox": q[box],
+                                    "segmentation": {"counts": rle.counts_to_string(runs[j]), "size": [H, W]},
+                                    "ignore": bool(float(fract[j]) < min_visib)})
+        coco = {"images": [images[im] for im in sorted(images)], "annotations": annotations,
+                "categories": [{"id": obj, "name": "%d" % obj} for obj in objs]}
+        with open(cpath, "w") as f:
+            json.dump(coco, f)
+        out[sc] = coco
+    return out
+
+
+def result_masks(dataset, rows, device, chunk_images: int = 32, delta: float = bop.DELTA):
+    """The visible masks of estimated poses as detection rows: result rows as read_results returns them (t in
+    millimetres) become rows in _check_rows' normal form, BOP's detection / segmentation result format, so a pose
+    result file yields a segmentation result file, and PoseDataset(layout="bop", detections=...) can crop and mask a
+    second pass from a first pass's poses. `dataset` is a PoseDataset(layout="bop", meshes=True).
+
+    Per chunk of at most `chunk_images` distinct images, as in eval_results, the depth frames are read once; the
+    chunk's estimates go through bop.visibility under their own poses, 64 at a time, and rle.encode_planes of
+    mask_visib brings back the runs alone. Each estimate with a visible pixel gives {scene_id, image_id, category_id,
+    score = the row's, bbox = the estimate's bbox_visib, segmentation = {"counts": run list, "size": [H, W]}, time =
+    the row's}, in the order of `rows`. Returns (rows, {"empty": the estimates without a visible pixel (behind the
+    camera, outside the frame, hidden), which give no row, "ignored": the rows whose image or object the tree does
+    not hold})."""
+    from .runtime import h2d
+    device = torch.device(device)
+    tree = dataset.tree
+    if getattr(dataset, "layout", "linemod") != "bop" or not getattr(dataset, "meshes", False):
+        raise ValueError("result_masks needs a PoseDataset with layout='bop' and meshes=True")
+    mesh = dataset._mesh_for(device)
+    cams = {(int(it["scene"]), int(it["im"])): (it["K4"], float(it["depth_scale"])) for it in tree.instances}
+    by_image: Dict[Tuple[int, int], List[int]] = {}
+    ignored = 0
+    for r, row in enumerate(rows):
+        key = (int(row["scene_id"]), int(row["im_id"]))
+        if key in cams and int(row["obj_id"]) in mesh["range"]:
+            by_image.setdefault(key, []).append(r)
+        else:
+            ignored += 1
+    out: List[Optional[Dict[str, object]]] = [None] * len(rows)
+    images = list(by_image)
+    empty = 0
+    step = max(1, int(chunk_images))
+    for lo in range(0, len(images), step):
+        ims = images[lo:lo + step]
+        depth = h2d(torch.from_numpy(np.stack([
+            read_depth(os.path.join(tree.root, tree.split, f"{sc:06d}"), im, cams[(sc, im)][1]) for sc, im in ims])), device)
+        H, W = int(depth.shape[1]), int(depth.shape[2])
+        est = [(r, f) for f, key in enumerate(ims) for r in by_image[key]]
+        for b0 in range(0, len(est), 64):                # write_gt_info's batch: 2 x 64 planes at a time
+            part = est[b0:b0 + 64]
+            res = bop.visibility(
+                mesh["verts"], mesh["faces"],
+                torch.tensor([mesh["range"][int(rows[r]["obj_id"])] for r, _ in part], dtype=torch.int32),
+                torch.from_numpy(np.stack([np.asarray(rows[r]["R"], np.float64).reshape(3, 3) for r, _ in part])),
+                torch.from_numpy(np.stack([np.asarray(rows[r]["t"], np.float64).reshape(3) / 1000.0 for r, _ in part])),
+                torch.tensor([cams[ims[f]][0] for _, f in part], dtype=torch.float32), depth,
+                torch.tensor([f for _, f in part], dtype=torch.int32), 1.0, delta)
+            runs = rle.encode_planes(res["mask_visib"])
+            info = res["info"].cpu().numpy()
+            for j, (r, _) in enumerate(part):
+                q = [int(x) for x in info[j]]
+                if q[2] == 0:
+                    empty += 1
+                    continue
+                row = rows[r]
+                out[r] = {"scene_id": int(row["scene_id"]), "image_id": int(row["im_id"]), "category_id": int(row["obj_id"]),
+                          "score": float(row["score"]), "bbox": [float(v) for v in q[7:11]],
+                          "segmentation": {"counts": runs[j], "size": [H, W]}, "time": float(row["time"])}
+    return [e for e in out if e is not None], {"empty": empty, "ignored": ignored}
+
+
+def write_result_masks(path, dataset, rows, device, chunk_images: int = 32, delta: float = bop.DELTA):
+    """result_masks followed by write_detections(path, ...): a pose result file's segmentation result file. Returns
+    what result_masks returns."""
+    det, stats = result_masks(dataset, rows, device, chunk_images, delta)
+    write_detections(path, det)
+    return det, stats
 
 
 RESULT_HEADER = "scene_id,im_id,obj_id,score,R,t,time"

@@ -33,7 +33,7 @@ import torch.distributed as dist
 
 from . import distributed as kd
 from .bop import BOP_REC, FRAME_W, TAUS, bop_errors, fold_bop
-from .bop_scene import eval_results, write_results
+from .bop_scene import eval_results, write_result_masks, write_results
 from .dataset import PoseDataset
 from .krrn import KRRN
 from .loss import map_losses
@@ -345,7 +345,7 @@ def test_epoch(model: KRRN, dataset: PoseDataset, bs: int = 64, device=None, opt
                criterion=None, world: Optional[int] = None, rank: Optional[int] = None,
                group=None, pose_solver: str = "pnp", refine: Optional[str] = None,
                bop: bool = False, bop_csv: Optional[str] = None, select: Optional[str] = None,
-               match: bool = False) -> Dict[str, object]:
+               match: bool = False, seg_json: Optional[str] = None) -> Dict[str, object]:
     """Trainer.test_epoch over `dataset`. world/rank default to the initialised process group
     (1/0 without one). `criterion` enables the per-crop map-loss terms (dis_xyz / dis_mask /
     dis_normal) when the batches carry GT maps, i.e. for a PoseDataset built with gt_maps=True (a
@@ -373,8 +373,17 @@ def test_epoch(model: KRRN, dataset: PoseDataset, bs: int = 64, device=None, opt
     matches each target's `inst_count` best rows to its GT instances; every other key is as before. A dataset built
     with det_per_target="inst_count" has only a provisional crop-to-instance association, so bop=True without
     match=True raises ValueError on it. With world > 1 rank 0 evaluates the gathered rows and broadcasts the dict
-    (dist.broadcast_object_list)."""
+    (dist.broadcast_object_list).
+    `seg_json` (off by default: nothing changes; needs a dataset with layout="bop" and meshes=True, else ValueError)
+    writes the estimates' masks as a segmentation result file: rank 0 builds the result rows exactly as `bop_csv`
+    writes them and calls bop_scene.write_result_masks(seg_json, dataset, rows, device), which renders each pose's
+    visible mask against the observed depth and encodes it on the GPU. The file is in the detection format, so
+    PoseDataset(layout="bop", detections=seg_json) crops and masks a second pass from this pass's poses. One key is
+    added, "seg": {"rows": the rows written, "empty": the estimates without a visible pixel}; no other key changes."""
     device = torch.device(device) if device is not None else next(model.parameters()).device
+    if seg_json and not (getattr(dataset, "layout", "linemod") == "bop" and getattr(dataset, "meshes", False)):
+        raise ValueError("seg_json renders the estimates' masks on a BOP tree: it needs a PoseDataset with layout='bop' "
+                         "and meshes=True")
     if match and not (bop and getattr(dataset, "layout", "linemod") == "bop"):
         raise ValueError("match=True scores result rows against a BOP tree: it needs bop=True and a PoseDataset with "
                          "layout='bop'")
@@ -393,11 +402,11 @@ def test_epoch(model: KRRN, dataset: PoseDataset, bs: int = 64, device=None, opt
         raise ValueError("bop_csv writes BOP's scene / image ids: it needs a PoseDataset with layout='bop'")
     local = eval_records(model, dataset, mine, bs, device, opt_pose=opt_pose, with_loss=criterion is not None,
                          pose_solver=pose_solver, refine=refine, **({"bop": True} if bop else {}),
-                         **({"poses": True} if bop_csv or match else {}), **({"select": select} if select else {}))
+                         **({"poses": True} if bop_csv or match or seg_json else {}), **({"select": select} if select else {}))
     local_bop = local_pose = local_sel = None
     if select:
         local, local_sel = (local[:-1] if len(local) > 2 else local[0]), local[-1]
-    if bop_csv or match:
+    if bop_csv or match or seg_json:
         local, local_pose = local[:-1] if bop else local[0], local[-1]
         # gather_epoch_records marks pad rows by a last column `valid` = 0
         local_pose = torch.cat([local_pose, torch.ones((local_pose.shape[0], 1), dtype=torch.float64)], 1)
@@ -430,7 +439,7 @@ def test_epoch(model: KRRN, dataset: PoseDataset, bs: int = 64, device=None, opt
         picked = {int(c): int((tab[:, 1] == c).sum()) for c in sorted(set(tab[:, 1].tolist()))}
         out["select"] = {"picked": picked, "mean_score": float(np.cumsum(tab[:, 2])[-1]) / len(tab) if len(tab) else 0.0}
         conf = {int(r[0]): float(r[2]) for r in tab}
-    if bop_csv or match:
+    if bop_csv or match or seg_json:
         allpose = gather_epoch_records(local_pose, shard_sizes, device, group) if world > 1 else local_pose
         if rank == 0:
             tab = allpose.numpy()
@@ -443,6 +452,14 @@ def test_epoch(model: KRRN, dataset: PoseDataset, bs: int = 64, device=None, opt
                              "R": row[1:10], "t": row[10:13] * 1000.0, "time": -1.0})
             if bop_csv:
                 write_results(bop_csv, rows)
+        if seg_json:
+            res = [None]
+            if rank == 0:
+                det, st = write_result_masks(seg_json, dataset, rows, device)
+                res = [{"rows": len(det), "empty": st["empty"]}]
+            if world > 1:
+                dist.broadcast_object_list(res, src=0, group=group)
+            out["seg"] = res[0]
         if match:  # the protocol's recalls over the rows, in place of the 1 : 1 fold above
             res = [eval_results(dataset, rows, device)] if rank == 0 else [None]
             if world > 1:

@@ -1,10 +1,13 @@
 """COCO run-length encoded masks, the `segmentation` of BOP's detection files: the string codec, an encoder and a
-box's runs on the host, and the decoder on the GPU (krrn_rle_decode_u8; include/krrn_hip.h states the definition).
+box's runs on the host, and the decoder and the encoder on the GPU (krrn_rle_decode_u8 / krrn_rle_encode_u8;
+include/krrn_hip.h states the definitions).
 
     runs = counts_from_string("61X13mN000`0")           # [6, 1, 40, 4, 5, 4, 5, 4, 21]; counts_to_string inverts it
     runs = encode(mask)                                 # host u8 / bool [H, W] -> run list
     runs = box_counts(x, y, w, h, H, W)                 # a filled box, for a detection without `segmentation`
     out = decode(counts, offs, H, W, device)            # {"mask": u8 [n, H, W] of 0 / 1, "info": int32 [n, 5]}
+    enc = encode_gpu(planes)                            # GPU u8 / bool [n, H, W] -> {"counts", "n_runs", "info"}
+    runs = encode_planes(planes)                        # the same as n run lists: [encode(m) for m in planes.cpu()]
 
 Run semantics are COCO's: pixels are numbered column-major (p = x * H + y), the first run is zeros, the runs
 alternate, and a run may have length 0 (the first one when pixel (0, 0) is set). `info` = (pixel count, x, y, w, h):
@@ -14,6 +17,7 @@ character above '0', bit 0x20 = another character follows, the last character's 
 fourth value on the value two places back is added."""
 from __future__ import annotations
 
+import ctypes
 from typing import Dict, List, Optional, Sequence
 
 import numpy as np
@@ -133,3 +137,54 @@ def decode(counts, offs, H: int, W: int, device, out: Optional[torch.Tensor] = N
     ends = torch.empty((len(c64),), dtype=torch.int32, device=device)
     _lib.call("krrn_rle_decode_u8", ptr(cd), ptr(od), n, H, W, ptr(ends), ptr(out), ptr(info), stream_ptr(device))
     return {"mask": out, "info": info}
+
+
+def encode_gpu(mask: torch.Tensor, max_runs: Optional[int] = None) -> Dict[str, torch.Tensor]:
+    """krrn_rle_encode_u8 for the n planes of `mask`, a u8 or bool GPU tensor [n, H, W] or [H, W] (any non-zero
+    element is set; contiguous, at any byte address). Returns {"counts": int32 [n, max_runs], "n_runs": int32 [n],
+    "info": int32 [n, 5]}: mask i's runs are counts[i, :n_runs[i]] (what `encode` returns for the plane) and the rest
+    of its slot is 0; n_runs is the true count even where it exceeds max_runs, and the slot then holds the first
+    max_runs runs. max_runs defaults to min(H W + 1, 8 W + 1): room for any mask whose columns change value 8 times
+    on average. A mask of another dtype or rank, a non-contiguous one or max_runs < 1 raises ValueError, a CPU tensor
+    RuntimeError, before anything is launched. Queued on the current stream; nothing is read back."""
+    if not isinstance(mask, torch.Tensor) or mask.dtype not in (torch.uint8, torch.bool) or mask.dim() not in (2, 3):
+        what = f"{mask.dtype} {tuple(mask.shape)}" if isinstance(mask, torch.Tensor) else type(mask).__name__
+        raise ValueError(f"mask must be a u8 or bool [n, H, W] or [H, W] tensor, got {what}")
+    if not mask.is_contiguous():
+        raise ValueError("mask must be contiguous")
+    m = mask.view(torch.uint8) if mask.dtype == torch.bool else mask
+    m = m[None] if m.dim() == 2 else m
+    n, H, W = (int(v) for v in m.shape)
+    if H <= 0 or W <= 0 or H * W > 0x7fffffff:
+        raise ValueError(f"frame {H} x {W}: H and W must be positive and H * W fit an int32")
+    max_runs = min(H * W + 1, 8 * W + 1) if max_runs is None else int(max_runs)
+    if max_runs < 1:
+        raise ValueError(f"max_runs must be >= 1, got {max_runs}")
+    if not mask.is_cuda:
+        raise RuntimeError("rle.encode_gpu runs on the HIP path only (a GPU tensor)")
+    dev = m.device
+    counts = torch.empty((n, max_runs), dtype=torch.int32, device=dev)
+    n_runs = torch.empty((n,), dtype=torch.int32, device=dev)
+    info = torch.empty((n, 5), dtype=torch.int32, device=dev)
+    if n == 0:
+        return {"counts": counts, "n_runs": n_runs, "info": info}
+    n_ints = ctypes.c_longlong(0)
+    _lib.call("krrn_rle_encode_ws", n, W, ctypes.byref(n_ints))
+    ws = torch.empty((n_ints.value,), dtype=torch.int32, device=dev)
+    _lib.call("krrn_rle_encode_u8", ptr(m), n, H, W, max_runs, ptr(ws), ptr(counts), ptr(n_runs), ptr(info),
+              stream_ptr(dev))
+    return {"counts": counts, "n_runs": n_runs, "info": info}
+
+
+def encode_planes(mask: torch.Tensor, max_runs: Optional[int] = None) -> List[List[int]]:
+    """The run lists of the n planes of a GPU mask (as encode_gpu takes it), python ints: equal to [encode(m) for m
+    in mask.cpu()], but only the runs cross the bus. One read-back of n_runs and counts; if a mask has more than
+    max_runs runs, one more call with max_runs = n_runs.max()."""
+    res = encode_gpu(mask, max_runs)
+    nr = res["n_runs"].cpu().numpy()
+    cap = int(res["counts"].shape[1])
+    if len(nr) and int(nr.max()) > cap:
+        res = encode_gpu(mask, int(nr.max()))
+    top = int(nr.max()) if len(nr) else 0
+    counts = res["counts"][:, :top].cpu().numpy()        # the slots' zero tails past the longest list stay behind
+    return [counts[i, :int(k)].tolist() for i, k in enumerate(nr)]
