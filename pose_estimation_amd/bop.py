@@ -29,7 +29,7 @@ bop_scene.eval_results builds the protocol's recalls for a result file on it.
 from __future__ import annotations
 
 import math
-from typing import Dict, Optional, Sequence
+from typing import Dict, NamedTuple, Optional, Sequence, Union
 
 import numpy as np
 import torch
@@ -55,6 +55,52 @@ def _poses(dev, B, R_est, t_est, R_gt, t_gt):
             for x, w in ((R_est, 9), (t_est, 3), (R_gt, 9), (t_gt, 3))]
 
 
+class Scene(NamedTuple):
+    """stage_scene's result: the operands every render-versus-depth entry point takes, as the kernels read them."""
+    v: torch.Tensor                 # verts f32 [Vtot, 3]
+    f: torch.Tensor                 # faces int32 [Ftot, 3]
+    d: torch.Tensor                 # depth f32 [F, H, W]
+    m: Optional[torch.Tensor]       # mask u8 [F, H, W], or None
+    fr: torch.Tensor                # face_range int32 [B, 2]
+    K: torch.Tensor                 # K4 f32 [B, 4]
+    fi: torch.Tensor                # frame int32 [B]
+    B: int
+    F: int
+    H: int
+    W: int
+
+
+def stage_scene(name: str, verts, faces, face_range, K4, depth, frame, *mask) -> Scene:
+    """What vsd, visibility, verify.score_poses and depth_refine.refine share: verts / faces / depth (and the optional
+    u8 mask of depth's shape, for the callers that pass one) must be GPU tensors (RuntimeError naming `name`), depth
+    [F, H, W] (ValueError); they are converted to the kernels' types, and face_range [B, 2], K4 [B, 4] and frame [B]
+    are staged on verts' device. The caller keeps the returned Scene bound until its launch is enqueued
+    (metric.add_metric's rule): a converted operand that nothing holds would be freed under the kernel."""
+    m = mask[0] if mask else None
+    if not (verts.is_cuda and faces.is_cuda and depth.is_cuda and (m is None or m.is_cuda)):
+        raise RuntimeError(f"{name} runs on the HIP path only (verts / faces / depth{' / mask' if mask else ''} must be "
+                           "GPU tensors)")
+    dev = verts.device
+    B = int(face_range.reshape(-1, 2).shape[0])
+    if depth.dim() != 3:
+        raise ValueError(f"depth must be [F, H, W], got {tuple(depth.shape)}")
+    if m is not None and (m.dtype != torch.uint8 or tuple(m.shape) != tuple(depth.shape)):
+        raise ValueError(f"mask must be uint8 {tuple(depth.shape)}, got {m.dtype} {tuple(m.shape)}")
+    return Scene(verts.to(torch.float32).contiguous(), faces.to(torch.int32).contiguous(),
+                 depth.to(torch.float32).contiguous(), m.contiguous() if m is not None else None,
+                 h2d(face_range.reshape(B, 2), dev, torch.int32), h2d(K4.reshape(B, 4), dev, torch.float32),
+                 h2d(frame.reshape(B), dev, torch.int32), B, *(int(x) for x in depth.shape))
+
+
+def per_crop(x: Union[float, torch.Tensor], B: int, device, name: str) -> torch.Tensor:
+    """A float or a [B] tensor (host or GPU) as f64 [B] on `device`."""
+    if isinstance(x, torch.Tensor):
+        if x.numel() != B:
+            raise ValueError(f"{name} must be a float or a [B] tensor with B = {B}, got {tuple(x.shape)}")
+        return h2d(x.reshape(B), device, torch.float64)
+    return h2d(torch.full((B,), float(x), dtype=torch.float64), device)
+
+
 def vsd(verts: torch.Tensor, faces: torch.Tensor, face_range: torch.Tensor, R_est: torch.Tensor, t_est: torch.Tensor,
         R_gt: torch.Tensor, t_gt: torch.Tensor, K4: torch.Tensor, depth: torch.Tensor, frame: torch.Tensor,
         diameter: torch.Tensor, depth_scale: float = 1.0, delta: float = DELTA,
@@ -62,31 +108,19 @@ def vsd(verts: torch.Tensor, faces: torch.Tensor, face_range: torch.Tensor, R_es
     """krrn_bop_vsd_f32 for B crops (module doc). verts [Vtot, 3] / faces [Ftot, 3] / depth [F, H, W] are GPU
     tensors; face_range [B, 2], the poses, K4 [B, 4], frame [B] and diameter [B] (metres) may be host tensors
     (staged here). Nothing is read back: the poses may come straight from a solver's launch."""
-    if not (verts.is_cuda and faces.is_cuda and depth.is_cuda):
-        raise RuntimeError("vsd runs on the HIP path only (verts / faces / depth must be GPU tensors)")
-    dev = verts.device
-    B, T = int(face_range.reshape(-1, 2).shape[0]), len(taus)
+    s = stage_scene("vsd", verts, faces, face_range, K4, depth, frame)
+    dev, B, T = verts.device, s.B, len(taus)
     if not 1 <= T <= MAX_T:
         raise ValueError(f"1 .. {MAX_T} taus, got {T}")
-    if depth.dim() != 3:
-        raise ValueError(f"depth must be [F, H, W], got {tuple(depth.shape)}")
-    # every converted operand stays bound until the launch is enqueued (metric.add_metric's rule)
-    v = verts.to(torch.float32).contiguous()
-    f = faces.to(torch.int32).contiguous()
-    d = depth.to(torch.float32).contiguous()
-    fr = h2d(face_range.reshape(B, 2), dev, torch.int32)
     Re, te, Rg, tg = _poses(dev, B, R_est, t_est, R_gt, t_gt)
-    K = h2d(K4.reshape(B, 4), dev, torch.float32)
-    fi = h2d(frame.reshape(B), dev, torch.int32)
     dia = h2d(diameter.reshape(B), dev, torch.float64)
     tau = h2d(torch.tensor(list(taus), dtype=torch.float64), dev)
     ws = torch.empty((B, 8), dtype=torch.int32, device=dev)       # krrn_bop_vsd_ws(B)
     counts = torch.empty((B, 2 + T), dtype=torch.int32, device=dev)
     e = torch.empty((B, T), dtype=torch.float64, device=dev)
-    F, H, W = d.shape
-    _lib.call("krrn_bop_vsd_f32", ptr(v), v.shape[0], ptr(f), f.shape[0], ptr(fr), ptr(Re), ptr(te), ptr(Rg), ptr(tg),
-              ptr(K), ptr(d), F, H, W, ptr(fi), float(depth_scale), ptr(dia), float(delta), ptr(tau), T, B, ptr(ws),
-              ptr(counts), ptr(e), stream_ptr(dev))
+    _lib.call("krrn_bop_vsd_f32", ptr(s.v), s.v.shape[0], ptr(s.f), s.f.shape[0], ptr(s.fr), ptr(Re), ptr(te), ptr(Rg),
+              ptr(tg), ptr(s.K), ptr(s.d), s.F, s.H, s.W, ptr(s.fi), float(depth_scale), ptr(dia), float(delta), ptr(tau),
+              T, B, ptr(ws), ptr(counts), ptr(e), stream_ptr(dev))
     return {"counts": counts, "e_vsd": e}
 
 
@@ -105,22 +139,10 @@ def visibility(verts: torch.Tensor, faces: torch.Tensor, face_range: torch.Tenso
     BOP's w = x_max - x_min, h = y_max - y_min, or four -1 without a pixel. Two stated departures from BOP's
     scripts: bbox_obj is clipped to the frame (BOP renders the silhouette into a 3 x larger window), and pixels
     are sampled at their integer coordinates. Nothing is read back."""
-    if not (verts.is_cuda and faces.is_cuda and depth.is_cuda):
-        raise RuntimeError("visibility runs on the HIP path only (verts / faces / depth must be GPU tensors)")
-    dev = verts.device
-    B = int(face_range.reshape(-1, 2).shape[0])
-    if depth.dim() != 3:
-        raise ValueError(f"depth must be [F, H, W], got {tuple(depth.shape)}")
-    # every converted operand stays bound until the launch is enqueued (metric.add_metric's rule)
-    v = verts.to(torch.float32).contiguous()
-    f = faces.to(torch.int32).contiguous()
-    d = depth.to(torch.float32).contiguous()
-    fr = h2d(face_range.reshape(B, 2), dev, torch.int32)
+    s = stage_scene("visibility", verts, faces, face_range, K4, depth, frame)
+    dev, B, H, W = verts.device, s.B, s.H, s.W
     Rd = h2d(R, dev, torch.float64).reshape(B, 9).contiguous()
     td = h2d(t, dev, torch.float64).reshape(B, 3).contiguous()
-    K = h2d(K4.reshape(B, 4), dev, torch.float32)
-    fi = h2d(frame.reshape(B), dev, torch.int32)
-    F, H, W = d.shape
     ws = torch.empty((B, VISIB_WS), dtype=torch.int32, device=dev)    # krrn_bop_visib_ws(B)
     out = {}
     if masks:
@@ -128,8 +150,8 @@ def visibility(verts: torch.Tensor, faces: torch.Tensor, face_range: torch.Tenso
         out["mask_visib"] = torch.empty((B, H, W), dtype=torch.uint8, device=dev)
     out["info"] = torch.empty((B, 11), dtype=torch.int32, device=dev)
     out["visib_fract"] = torch.empty((B,), dtype=torch.float64, device=dev)
-    _lib.call("krrn_bop_visib_u8", ptr(v), v.shape[0], ptr(f), f.shape[0], ptr(fr), ptr(Rd), ptr(td), ptr(K), ptr(d), F,
-              H, W, ptr(fi), float(depth_scale), float(delta), B, ptr(ws), ptr(out.get("mask")),
+    _lib.call("krrn_bop_visib_u8", ptr(s.v), s.v.shape[0], ptr(s.f), s.f.shape[0], ptr(s.fr), ptr(Rd), ptr(td), ptr(s.K),
+              ptr(s.d), s.F, H, W, ptr(s.fi), float(depth_scale), float(delta), B, ptr(ws), ptr(out.get("mask")),
               ptr(out.get("mask_visib")), ptr(out["info"]), ptr(out["visib_fract"]), stream_ptr(dev))
     return out
 
@@ -300,6 +322,15 @@ def recalls_from_tp(tp: np.ndarray, targets: int, count: int) -> Dict[str, float
             "count": int(count), "targets": n}
 
 
+def valid_by_crop(table) -> np.ndarray:
+    """A (gathered) epoch table's rows without the pad rows, which evaluate.gather_epoch_records marks by a last column
+    `valid` = 0, stably sorted by their first column `crop`: global crop order, however the crops were batched or
+    sharded."""
+    tab = table.numpy() if isinstance(table, torch.Tensor) else np.asarray(table)
+    tab = tab[tab[:, -1] > 0]
+    return tab[np.argsort(tab[:, 0], kind="stable")]
+
+
 def fold_bop(records, objlist: Sequence[int], diameter: Sequence[float], width: float = FRAME_W,
              missed: Optional[Dict[int, int]] = None) -> Dict[str, object]:
     """The BOP-19 average recalls over per-crop BOP_REC records (any order, pad rows valid = 0), folded in
@@ -316,9 +347,7 @@ def fold_bop(records, objlist: Sequence[int], diameter: Sequence[float], width: 
     "targets" = count + missed appears beside it; an object with missed targets only occurs in per_obj with recall
     0. With missed=None nothing changes."""
     rec = records.numpy() if isinstance(records, torch.Tensor) else np.asarray(records, np.float64)
-    rec = rec.reshape(-1, len(BOP_REC))
-    rec = rec[rec[:, _B["valid"]] > 0]
-    rec = rec[np.argsort(rec[:, _B["crop"]], kind="stable")]
+    rec = valid_by_crop(rec.reshape(-1, len(BOP_REC)))
     cls = rec[:, _B["cls"]].astype(np.int64)
     dia = np.asarray(diameter, np.float64)[cls] if len(rec) else np.zeros((0,))
     if missed is None:

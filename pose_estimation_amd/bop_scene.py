@@ -65,6 +65,15 @@ def scene_ids(root: str, split: str) -> List[int]:
     return sorted(int(n) for n in os.listdir(d) if n.isdigit() and os.path.isdir(os.path.join(d, n)))
 
 
+def _scene_dir(root: str, split: str, scene) -> str:
+    return os.path.join(root, split, f"{int(scene):06d}")
+
+
+def _key(it) -> Tuple[int, int, int]:
+    """The (scene, image, object) target of an item or instance."""
+    return int(it["scene"]), int(it["im"]), int(it["obj"])
+
+
 def _image_path(sdir: str, sub: str, im: int) -> str:
     for ext in (".png", ".jpg"):
         p = os.path.join(sdir, sub, f"{im:06d}{ext}")
@@ -151,7 +160,7 @@ class BopTree:
         self.items: List[Dict[str, object]] = []
         self.frame_hw: Optional[Tuple[int, int]] = None
         for sc in scene_ids(root, split):
-            sdir = os.path.join(root, split, f"{sc:06d}")
+            sdir = _scene_dir(root, split, sc)
             gt = _load_json(os.path.join(sdir, "scene_gt.json"))
             cam = _load_json(os.path.join(sdir, "scene_camera.json"))
             ipath = os.path.join(sdir, "scene_gt_info.json")
@@ -179,18 +188,15 @@ class BopTree:
         if self.items:
             it = self.items[0]
             from PIL import Image
-            with Image.open(os.path.join(root, split, f"{int(it['scene']):06d}", "depth", f"{int(it['im']):06d}.png")) as di:
+            with Image.open(os.path.join(self._sdir(it), "depth", f"{int(it['im']):06d}.png")) as di:
                 self.frame_hw = (di.size[1], di.size[0])
         self.instances: List[Dict[str, object]] = list(self.items)
         self.inst_count: Dict[Tuple[int, int, int], int] = {}
         for it in self.instances:
-            key = (int(it["scene"]), int(it["im"]), int(it["obj"]))
-            self.inst_count[key] = self.inst_count.get(key, 0) + 1
+            self.inst_count[_key(it)] = self.inst_count.get(_key(it), 0) + 1
         if want is not None:  # the targets file's own count, where it states one
             self.inst_count = {k: (want[k] if want[k] > 0 else n) for k, n in self.inst_count.items()}
-        if detections is not None and det_per_target == "inst_count":
-            self._pair_counted(detections, float(det_min_score))
-        elif detections is not None:
+        if detections is not None:
             self._pair(detections, float(det_min_score))
         self.info, mesh = load_models(root, self.objlist, faces=meshes)
         self.mesh: Dict[int, Tuple[np.ndarray, np.ndarray]] = mesh if meshes else {}
@@ -209,38 +215,30 @@ class BopTree:
             self.model_points[obj] = pts.astype(np.float32)
 
     def _pair(self, detections, min_score: float) -> None:
-        """Pair the kept GT instances with detection rows (class doc)."""
-        rows = read_detections(detections) if isinstance(detections, (str, os.PathLike)) else _check_rows(detections, "rows")
-        seen = set()
-        for it in self.items:
-            key = (int(it["scene"]), int(it["im"]), int(it["obj"]))
-            if key in seen:
+        """Pair the kept targets with detection rows (class doc): each target's best row, or with
+        det_per_target="inst_count" its inst_count best, one item each."""
+        counted = self.det_per_target == "inst_count"
+        rows, cand, dropped = _candidates(detections, [_key(it) for it in self.instances], min_score)
+        groups: Dict[Tuple[int, int, int], List[Dict[str, object]]] = {}
+        for it in self.instances:
+            key = _key(it)
+            if key in groups and not counted:
                 raise ValueError(f"target (scene {key[0]}, image {key[1]}, object {key[2]}) has more than one kept GT "
                                  "instance (inst_count > 1): matching several estimates to several instances is out of "
                                  "scope with detections")
-            seen.add(key)
-        best: Dict[Tuple[int, int, int], int] = {}
-        dropped = 0
-        for j, r in enumerate(rows):
-            seg = r.get("segmentation")
-            if r["bbox"][2] <= 0 or r["bbox"][3] <= 0 or (seg is not None and sum(seg["counts"][1::2]) <= 0):
-                dropped += 1
-                continue
-            key = (r["scene_id"], r["image_id"], r["category_id"])
-            if key not in seen or r["score"] < min_score:
-                continue
-            if key not in best or r["score"] > rows[best[key]]["score"]:     # a tie keeps the earlier row
-                best[key] = j
-        H, W = self.frame_hw if self.frame_hw else (0, 0)
+            groups.setdefault(key, []).append(it)
         items = []
-        for it in self.items:
-            key = (int(it["scene"]), int(it["im"]), int(it["obj"]))
-            if key not in best:
-                self.missed.append(key)
-                continue
-            items.append(self._det_item(it, rows, best[key]))
+        for key, inst in groups.items():
+            n = self.inst_count[key] if counted else 1
+            top = _by_score(rows, cand[key], nan_ok=not counted)[:n]
+            for j in top:
+                # the GT keys are lent by the kept instance whose bbox_visib overlaps the row's box most: "best" has
+                # one instance per target, argmax takes the lowest GT index on ties
+                ious = [_box_iou(it["bbox"], rows[j]["bbox"]) for it in inst]
+                items.append(self._det_item(inst[int(np.argmax(ious))], rows, j))
+            self.missed += [key] * (n - len(top))
         self.items = items
-        self.det_stats = {"rows": len(rows), "used": len(best), "unused": len(rows) - len(best) - dropped,
+        self.det_stats = {"rows": len(rows), "used": len(items), "unused": len(rows) - len(items) - dropped,
                           "dropped": dropped}
 
     def _det_item(self, it, rows, j: int) -> Dict[str, object]:
@@ -259,45 +257,17 @@ class BopTree:
                 raise ValueError(f"detection {j}: its runs do not fill the {H} x {W} frame")
         return dict(it, bbox=[float(v) for v in r["bbox"]], score=float(r["score"]), det=j, rle=runs)
 
-    def _pair_counted(self, detections, min_score: float) -> None:
-        """det_per_target="inst_count" (class doc): per kept target its inst_count best rows, one item each."""
-        rows = read_detections(detections) if isinstance(detections, (str, os.PathLike)) else _check_rows(detections, "rows")
-        groups: Dict[Tuple[int, int, int], List[Dict[str, object]]] = {}
-        for it in self.instances:
-            groups.setdefault((int(it["scene"]), int(it["im"]), int(it["obj"])), []).append(it)
-        cand: Dict[Tuple[int, int, int], List[int]] = {k: [] for k in groups}
-        dropped = 0
-        for j, r in enumerate(rows):
-            seg = r.get("segmentation")
-            if r["bbox"][2] <= 0 or r["bbox"][3] <= 0 or (seg is not None and sum(seg["counts"][1::2]) <= 0):
-                dropped += 1
-                continue
-            key = (r["scene_id"], r["image_id"], r["category_id"])
-            if key in cand and r["score"] >= min_score:
-                cand[key].append(j)
-        items, used = [], 0
-        for key, inst in groups.items():
-            n = self.inst_count[key]
-            top = sorted(cand[key], key=lambda j: -rows[j]["score"])[:n]     # stable: a tie keeps the earlier row
-            for j in top:
-                ious = [_box_iou(it["bbox"], rows[j]["bbox"]) for it in inst]
-                items.append(self._det_item(inst[int(np.argmax(ious))], rows, j))   # argmax: the lowest GT index on ties
-            used += len(top)
-            self.missed += [key] * (n - len(top))
-        self.items = items
-        self.det_stats = {"rows": len(rows), "used": used, "unused": len(rows) - used - dropped, "dropped": dropped}
-
     def has_symmetry(self, obj: int) -> bool:
         oi = self.info.get(obj, {})
         return bool(oi.get("symmetries_discrete")) or bool(oi.get("symmetries_continuous"))
 
     def _sdir(self, it) -> str:
-        return os.path.join(self.root, self.split, f"{int(it['scene']):06d}")
+        return _scene_dir(self.root, self.split, it["scene"])
 
     def read_image(self, scene: int, im: int, depth_scale: float):
         """(rgb u8 [H, W, 3], depth f32 [H, W] metres) of one image."""
         from PIL import Image
-        sdir = os.path.join(self.root, self.split, f"{scene:06d}")
+        sdir = _scene_dir(self.root, self.split, scene)
         with Image.open(_image_path(sdir, "rgb", im)) as ri:
             rgb = np.array(ri.convert("RGB"))
         return rgb, read_depth(sdir, im, depth_scale)
@@ -324,6 +294,36 @@ def _box_iou(a, b) -> float:
     inter = iw * ih
     union = max(aw, 0.0) * max(ah, 0.0) + max(bw, 0.0) * max(bh, 0.0) - inter
     return inter / union if union > 0.0 else 0.0
+
+
+def _candidates(detections, keys, min_score: float):
+    """Which detection rows qualify for which kept target (BopTree's class doc): (the rows, {key of `keys`: its
+    qualifying rows' indices in file order}, the rows dropped for a box with w <= 0 or h <= 0 or a mask without a set
+    pixel). A row qualifies unless its score is below min_score."""
+    rows = read_detections(detections) if isinstance(detections, (str, os.PathLike)) else _check_rows(detections, "rows")
+    cand: Dict[Tuple[int, int, int], List[int]] = {k: [] for k in keys}
+    dropped = 0
+    for j, r in enumerate(rows):
+        seg = r.get("segmentation")
+        if r["bbox"][2] <= 0 or r["bbox"][3] <= 0 or (seg is not None and sum(seg["counts"][1::2]) <= 0):
+            dropped += 1
+            continue
+        key = (r["scene_id"], r["image_id"], r["category_id"])
+        if key in cand and not r["score"] < min_score:
+            cand[key].append(j)
+    return rows, cand, dropped
+
+
+def _by_score(rows, js: List[int], nan_ok: bool) -> List[int]:
+    """The row indices `js` (in file order) by score descending, ties to the earlier row: "best" takes the first,
+    "inst_count" the first inst_count. A NaN score compares false with everything, and each mode keeps what that has
+    always meant for it. "inst_count" (nan_ok=False) asked for score >= det_min_score, so it never takes such a row.
+    "best" scanned the rows and replaced the one it held only for a strictly greater score: a NaN row that stands
+    first in file order is never displaced, any other is never picked."""
+    nan = lambda j: rows[j]["score"] != rows[j]["score"]  # noqa: E731
+    if nan_ok and js and nan(js[0]):
+        return js[:1]
+    return sorted((j for j in js if not nan(j)), key=lambda j: -rows[j]["score"])   # stable: file order on ties
 
 
 DET_KEYS = ("scene_id", "image_id", "category_id", "score", "bbox")
@@ -388,8 +388,8 @@ def gt_detections(tree: "BopTree") -> List[Dict[str, object]]:
     rows = []
     for i, it in enumerate(tree.items):
         m = tree.read_mask(i)
-        rows.append({"scene_id": int(it["scene"]), "image_id": int(it["im"]), "category_id": int(it["obj"]),
-                     "score": 1.0, "bbox": [float(v) for v in it["bbox"]],
+        sc, im, obj = _key(it)
+        rows.append({"scene_id": sc, "image_id": im, "category_id": obj, "score": 1.0, "bbox": [float(v) for v in it["bbox"]],
                      "segmentation": {"counts": rle.encode(m), "size": [int(m.shape[0]), int(m.shape[1])]}})
     return rows
 
@@ -399,17 +399,38 @@ def _save_json(path: str, content: Dict[int, object]) -> None:
         json.dump({str(k): v for k, v in sorted(content.items())}, f, indent=1)
 
 
-def _gt_scenes(root: str, split: str, device):
-    """What the ground-truth writers share: (scene ids, {scene: its scene_gt.json}, the objects they name, their
-    meshes concatenated on `device` as (verts, faces), {obj: (first face, faces)})."""
+def _require(dataset, message: str, layout: bool = False, meshes: bool = False) -> None:
+    """ValueError(message) unless `dataset` is a PoseDataset with layout="bop" (layout=True) and / or with
+    meshes=True (meshes=True)."""
+    if (layout and getattr(dataset, "layout", "linemod") != "bop") or (meshes and not getattr(dataset, "meshes", False)):
+        raise ValueError(message)
+
+
+def _refuse(path: str, overwrite: bool) -> None:
+    if os.path.exists(path) and not overwrite:
+        raise FileExistsError(f"{path} exists (overwrite=True replaces it)")
+
+
+def _visibility(verts, faces, ranges, R, t, K4, depth, frame, delta: float, masks: bool = True):
+    """bop.visibility of B poses whose operands are host lists: (first face, faces), R (9 or [3, 3] f64), t (f64
+    metres), (fx, fy, cx, cy) and the index into depth's frames, per pose; verts / faces / depth on the device."""
+    return bop.visibility(verts, faces, torch.tensor(ranges, dtype=torch.int32), torch.from_numpy(np.stack(R)),
+                          torch.from_numpy(np.stack(t)), torch.tensor(K4, dtype=torch.float32), depth,
+                          torch.tensor(frame, dtype=torch.int32), 1.0, delta, masks=masks)
+
+
+def _gt_batches(root: str, split: str, device, fname: str, overwrite: bool, batch: int, delta: float, masks: bool):
+    """What the ground-truth writers share. Reads every scene's scene_gt.json and puts the meshes of the objects they
+    name on `device`, concatenated. Then yields per scene (scene id, its directory, the path of its `fname`, its
+    scene_gt.json, its instances [(image, GT index, scene_gt entry)] in image and GT order, the split's objects,
+    batches); `batches` yields, per at most `batch` instances and only when asked, (that slice of the instances,
+    bop.visibility's result for it: the slice's distinct images' depth frames are read once). FileExistsError for an
+    existing `fname` unless overwrite, before anything is computed for that scene."""
     from .runtime import h2d
+    device = torch.device(device)
     scenes = scene_ids(root, split)
-    objs = set()
-    gts = {}
-    for sc in scenes:
-        gts[sc] = _load_json(os.path.join(root, split, f"{sc:06d}", "scene_gt.json"))
-        objs |= {int(e["obj_id"]) for v in gts[sc].values() for e in v}
-    objs = sorted(objs)
+    gts = {sc: _load_json(os.path.join(_scene_dir(root, split, sc), "scene_gt.json")) for sc in scenes}
+    objs = sorted({int(e["obj_id"]) for gt in gts.values() for v in gt.values() for e in v})
     _, mesh = load_models(root, objs)
     v0 = f0 = 0
     frange, vs, fs = {}, [], []
@@ -421,23 +442,25 @@ def _gt_scenes(root: str, split: str, device):
         v0, f0 = v0 + len(v), f0 + len(f)
     verts = h2d(torch.from_numpy(np.concatenate(vs)), device)
     faces = h2d(torch.from_numpy(np.concatenate(fs).astype(np.int32)), device)
-    return scenes, gts, objs, verts, faces, frange
 
+    def visibility(sdir, cam, part):
+        ims = list(dict.fromkeys(im for im, _, _ in part))
+        depth = np.stack([read_depth(sdir, im, float(cam[im].get("depth_scale", 1.0))) for im in ims])
+        K = [[float(k) for k in cam[im]["cam_K"]] for im, _, _ in part]
+        return _visibility(verts, faces, [frange[int(e["obj_id"])] for _, _, e in part],
+                           [np.array(e["cam_R_m2c"], np.float64) for _, _, e in part],
+                           [np.array(e["cam_t_m2c"], np.float64) / 1000.0 for _, _, e in part],
+                           [[k[0], k[4], k[2], k[5]] for k in K], h2d(torch.from_numpy(depth), device),
+                           [ims.index(im) for im, _, _ in part], delta, masks)
 
-def _gt_visibility(sdir: str, cam, part, verts, faces, frange, device, delta: float, masks: bool):
-    """bop.visibility of one batch `part` = [(image, GT index, scene_gt entry)] of a scene: its distinct images'
-    depth frames are read once."""
-    from .runtime import h2d
-    ims = list(dict.fromkeys(im for im, _, _ in part))
-    depth = np.stack([read_depth(sdir, im, float(cam[im].get("depth_scale", 1.0))) for im in ims])
-    K = [[float(k) for k in cam[im]["cam_K"]] for im, _, _ in part]
-    return bop.visibility(
-        verts, faces, torch.tensor([frange[int(e["obj_id"])] for _, _, e in part], dtype=torch.int32),
-        torch.tensor(np.stack([np.array(e["cam_R_m2c"], np.float64).reshape(3, 3) for _, _, e in part])),
-        torch.tensor(np.stack([np.array(e["cam_t_m2c"], np.float64) / 1000.0 for _, _, e in part])),
-        torch.tensor([[k[0], k[4], k[2], k[5]] for k in K], dtype=torch.float32),
-        h2d(torch.from_numpy(depth), device), torch.tensor([ims.index(im) for im, _, _ in part], dtype=torch.int32),
-        1.0, delta, masks=masks)
+    step = max(1, int(batch))
+    for sc in scenes:
+        sdir = _scene_dir(root, split, sc)
+        _refuse(os.path.join(sdir, fname), overwrite)
+        cam = _load_json(os.path.join(sdir, "scene_camera.json"))
+        inst = [(im, g, e) for im in sorted(gts[sc]) for g, e in enumerate(gts[sc][im])]
+        yield (sc, sdir, os.path.join(sdir, fname), gts[sc], inst, objs,
+               ((inst[lo:lo + step], visibility(sdir, cam, inst[lo:lo + step])) for lo in range(0, len(inst), step)))
 
 
 def _info_entry(q: Sequence[int], fract: float) -> Dict[str, object]:
@@ -456,27 +479,16 @@ def write_gt_info(root: str, split: str, device, masks: bool = False, delta: flo
     scene). Returns {scene: {image: [entry per instance]}}. The two departures from BOP's scripts that
     bop.visibility states apply: bbox_obj is clipped to the frame, and pixels are sampled at integer coordinates."""
     from PIL import Image
-    device = torch.device(device)
     out = {}
-    scenes, gts, _, verts, faces, frange = _gt_scenes(root, split, device)
-    for sc in scenes:
-        sdir = os.path.join(root, split, f"{sc:06d}")
-        ipath = os.path.join(sdir, "scene_gt_info.json")
-        if os.path.exists(ipath) and not overwrite:
-            raise FileExistsError(f"{ipath} exists (overwrite=True replaces it)")
-        cam = _load_json(os.path.join(sdir, "scene_camera.json"))
-        inst = [(im, g, e) for im in sorted(gts[sc]) for g, e in enumerate(gts[sc][im])]
+    for sc, sdir, ipath, gt, inst, _, batches in _gt_batches(root, split, device, "scene_gt_info.json", overwrite, batch,
+                                                           delta, masks):
         if masks:
             for sub in ("mask", "mask_visib"):
                 os.makedirs(os.path.join(sdir, sub), exist_ok=True)
                 for im, g, _ in inst:
-                    p = os.path.join(sdir, sub, f"{im:06d}_{g:06d}.png")
-                    if os.path.exists(p) and not overwrite:
-                        raise FileExistsError(f"{p} exists (overwrite=True replaces it)")
-        entries = {im: [None] * len(gts[sc][im]) for im in gts[sc]}
-        for lo in range(0, len(inst), max(1, int(batch))):
-            part = inst[lo:lo + max(1, int(batch))]
-            res = _gt_visibility(sdir, cam, part, verts, faces, frange, device, delta, masks)
+                    _refuse(os.path.join(sdir, sub, f"{im:06d}_{g:06d}.png"), overwrite)
+        entries = {im: [None] * len(gt[im]) for im in gt}
+        for part, res in batches:
             info, fract = res["info"].cpu().numpy(), res["visib_fract"].cpu().numpy()   # one read-back per batch
             planes = {k: res[k].cpu().numpy() for k in ("mask", "mask_visib")} if masks else {}
             for j, (im, g, _) in enumerate(part):
@@ -506,21 +518,12 @@ def write_gt_coco(root: str, split: str, device, visib: bool = True, min_visib: 
     formats and is not checked against the BOP toolkit's own output (the toolkit is not a dependency). The two
     departures from BOP's scripts that bop.visibility states apply: bbox_obj is clipped to the frame, and pixels are
     sampled at integer coordinates."""
-    device = torch.device(device)
     out = {}
-    scenes, gts, objs, verts, faces, frange = _gt_scenes(root, split, device)
     plane, px, box = ("mask_visib", 2, slice(7, 11)) if visib else ("mask", 0, slice(3, 7))
-    for sc in scenes:
-        sdir = os.path.join(root, split, f"{sc:06d}")
-        cpath = os.path.join(sdir, "scene_gt_coco.json")
-        if os.path.exists(cpath) and not overwrite:
-            raise FileExistsError(f"{cpath} exists (overwrite=True replaces it)")
-        cam = _load_json(os.path.join(sdir, "scene_camera.json"))
-        inst = [(im, g, e) for im in sorted(gts[sc]) for g, e in enumerate(gts[sc][im])]
+    for sc, sdir, cpath, _, _, objs, batches in _gt_batches(root, split, device, "scene_gt_coco.json", overwrite, batch,
+                                                          bop.DELTA, True):
         images, annotations = {}, []
-        for lo in range(0, len(inst), max(1, int(batch))):
-            part = inst[lo:lo + max(1, int(batch))]
-            res = _gt_visibility(sdir, cam, part, verts, faces, frange, device, bop.DELTA, True)
+        for part, res in batches:
             H, W = (int(v) for v in res[plane].shape[1:])
             runs = rle.encode_planes(res[plane])
             info, fract = res["info"].cpu().numpy(), res["visib_fract"].cpu().numpy()
@@ -542,6 +545,42 @@ def write_gt_coco(root: str, split: str, device, visib: bool = True, min_visib: 
     return out
 
 
+def _row_pose(row):
+    """A result row's pose in metres: (R f64 [9] row-major, t f64 [3])."""
+    return np.asarray(row["R"], np.float64).reshape(9), np.asarray(row["t"], np.float64).reshape(3) / 1000.0
+
+
+def _rows_by(rows, width: int, known):
+    """Result rows sorted into a tree's keys: ({the first `width` of (scene_id, im_id, obj_id): its rows' indices, in
+    order} over the rows whose triple `known` accepts, in order of first appearance; the number of rows it refuses)."""
+    by: Dict[tuple, List[int]] = {}
+    ignored = 0
+    for r, row in enumerate(rows):
+        key = (int(row["scene_id"]), int(row["im_id"]), int(row["obj_id"]))
+        if known(key):
+            by.setdefault(key[:width], []).append(r)
+        else:
+            ignored += 1
+    return by, ignored
+
+
+def _image_chunks(tree, images, chunk_images: int, device):
+    """`images` = [(scene, image)] in chunks of at most chunk_images: per chunk (its images, their depth frames f32
+    [n, H, W] on `device`), each frame read once and through read_depth alone (no RGB is decoded)."""
+    from .runtime import h2d
+    scale = {_key(it)[:2]: float(it["depth_scale"]) for it in tree.instances}
+    step = max(1, int(chunk_images))
+    for lo in range(0, len(images), step):
+        ims = images[lo:lo + step]
+        yield ims, h2d(torch.from_numpy(np.stack([
+            read_depth(_scene_dir(tree.root, tree.split, sc), im, scale[(sc, im)]) for sc, im in ims])), device)
+
+
+def _taking_part(n_top: int, n_est: int) -> int:
+    """How many of a target's n_est rows take part in the matching: its n_top best, all of them for n_top <= 0."""
+    return n_est if n_top <= 0 else min(n_top, n_est)
+
+
 def result_masks(dataset, rows, device, chunk_images: int = 32, delta: float = bop.DELTA):
     """The visible masks of estimated poses as detection rows: result rows as read_results returns them (t in
     millimetres) become rows in _check_rows' normal form, BOP's detection / segmentation result format, so a pose
@@ -555,40 +594,22 @@ def result_masks(dataset, rows, device, chunk_images: int = 32, delta: float = b
     the row's}, in the order of `rows`. Returns (rows, {"empty": the estimates without a visible pixel (behind the
     camera, outside the frame, hidden), which give no row, "ignored": the rows whose image or object the tree does
     not hold})."""
-    from .runtime import h2d
     device = torch.device(device)
     tree = dataset.tree
-    if getattr(dataset, "layout", "linemod") != "bop" or not getattr(dataset, "meshes", False):
-        raise ValueError("result_masks needs a PoseDataset with layout='bop' and meshes=True")
+    _require(dataset, "result_masks needs a PoseDataset with layout='bop' and meshes=True", layout=True, meshes=True)
     mesh = dataset._mesh_for(device)
-    cams = {(int(it["scene"]), int(it["im"])): (it["K4"], float(it["depth_scale"])) for it in tree.instances}
-    by_image: Dict[Tuple[int, int], List[int]] = {}
-    ignored = 0
-    for r, row in enumerate(rows):
-        key = (int(row["scene_id"]), int(row["im_id"]))
-        if key in cams and int(row["obj_id"]) in mesh["range"]:
-            by_image.setdefault(key, []).append(r)
-        else:
-            ignored += 1
+    K4 = {_key(it)[:2]: it["K4"] for it in tree.instances}
+    by_image, ignored = _rows_by(rows, 2, lambda k: k[:2] in K4 and k[2] in mesh["range"])
     out: List[Optional[Dict[str, object]]] = [None] * len(rows)
-    images = list(by_image)
     empty = 0
-    step = max(1, int(chunk_images))
-    for lo in range(0, len(images), step):
-        ims = images[lo:lo + step]
-        depth = h2d(torch.from_numpy(np.stack([
-            read_depth(os.path.join(tree.root, tree.split, f"{sc:06d}"), im, cams[(sc, im)][1]) for sc, im in ims])), device)
+    for ims, depth in _image_chunks(tree, list(by_image), chunk_images, device):
         H, W = int(depth.shape[1]), int(depth.shape[2])
         est = [(r, f) for f, key in enumerate(ims) for r in by_image[key]]
         for b0 in range(0, len(est), 64):                # write_gt_info's batch: 2 x 64 planes at a time
             part = est[b0:b0 + 64]
-            res = bop.visibility(
-                mesh["verts"], mesh["faces"],
-                torch.tensor([mesh["range"][int(rows[r]["obj_id"])] for r, _ in part], dtype=torch.int32),
-                torch.from_numpy(np.stack([np.asarray(rows[r]["R"], np.float64).reshape(3, 3) for r, _ in part])),
-                torch.from_numpy(np.stack([np.asarray(rows[r]["t"], np.float64).reshape(3) / 1000.0 for r, _ in part])),
-                torch.tensor([cams[ims[f]][0] for _, f in part], dtype=torch.float32), depth,
-                torch.tensor([f for _, f in part], dtype=torch.int32), 1.0, delta)
+            R, t = zip(*(_row_pose(rows[r]) for r, _ in part))
+            res = _visibility(mesh["verts"], mesh["faces"], [mesh["range"][int(rows[r]["obj_id"])] for r, _ in part], R, t,
+                              [K4[ims[f]] for _, f in part], depth, [f for _, f in part], delta)
             runs = rle.encode_planes(res["mask_visib"])
             info = res["info"].cpu().numpy()
             for j, (r, _) in enumerate(part):
@@ -675,43 +696,30 @@ def eval_results(dataset, rows, device, chunk_images: int = 32, delta: float = b
     from .runtime import h2d
     device = torch.device(device)
     tree = dataset.tree
-    if getattr(dataset, "layout", "linemod") != "bop" or not getattr(dataset, "meshes", False):
-        raise ValueError("eval_results needs a PoseDataset with layout='bop' and meshes=True")
+    _require(dataset, "eval_results needs a PoseDataset with layout='bop' and meshes=True", layout=True, meshes=True)
     mesh = dataset._mesh_for(device)
     T, NT, C = len(taus), len(bop.THETAS), len(taus) + 2
     width = float((tree.frame_hw or (0, bop.FRAME_W))[1])
     groups: Dict[Tuple[int, int, int], List[int]] = {}
     for i, it in enumerate(tree.instances):
-        groups.setdefault((int(it["scene"]), int(it["im"]), int(it["obj"])), []).append(i)
-    est: Dict[Tuple[int, int, int], List[int]] = {k: [] for k in groups}
-    ignored = 0
-    for r, row in enumerate(rows):
-        key = (int(row["scene_id"]), int(row["im_id"]), int(row["obj_id"]))
-        if key in est:
-            est[key].append(r)
-        else:
-            ignored += 1
-    count = 0
+        groups.setdefault(_key(it), []).append(i)
+    by, ignored = _rows_by(rows, 3, groups.__contains__)
+    est = {k: by.get(k, []) for k in groups}
     for key, inst in groups.items():
         if len(inst) > bop.MATCH_MAX:
             raise ValueError(f"target {key} has {len(inst)} kept instances > {bop.MATCH_MAX}")
         if len(est[key]) > bop.MATCH_MAX:
             order = _rank([float(rows[r]["score"]) for r in est[key]])[:bop.MATCH_MAX]
             est[key] = [est[key][a] for a in sorted(order)]
-        n_top = tree.inst_count[key]
-        count += len(est[key]) if n_top <= 0 else min(n_top, len(est[key]))
+    take = {k: _taking_part(tree.inst_count[k], len(est[k])) for k in groups}
     objs = list(dict.fromkeys(k[2] for k in groups))
     tp_obj = torch.zeros((max(1, len(objs)), C, NT), dtype=torch.int64, device=device)
     images = list(dict.fromkeys(k[:2] for k in groups))
-    scale = {(int(it["scene"]), int(it["im"])): float(it["depth_scale"]) for it in tree.instances}
     th, th_px = np.asarray(bop.THETAS), np.asarray(bop.THETAS_PX)
     pending = []                                             # per chunk: (instance indices, row indices, match column)
-    step = max(1, int(chunk_images))
-    for lo in range(0, len(images), step):
-        ims = images[lo:lo + step]
+    for ims, depth in _image_chunks(tree, images, chunk_images, device):
         frame = {im: f for f, im in enumerate(ims)}
         keys = [k for k in groups if k[:2] in frame]
-        depth = np.stack([tree.read_image(sc, im, scale[(sc, im)])[1] for sc, im in ims])
         slots, erows, er, gr, po, nt, thr, gobj = [], [], [], [], [], [], [], []
         Re, te, Rg, tg, K4, fi, fr, vr, sr, dia = [], [], [], [], [], [], [], [], [], []
         for key in keys:
@@ -724,8 +732,7 @@ def eval_results(dataset, rows, device, chunk_images: int = 32, delta: float = b
             gobj.append(objs.index(obj))
             thr.append(np.stack([th] * T + [np.array([t * d for t in th]), np.array([t * (width / 640.0) for t in th_px])]))
             for r in rws:
-                R = np.asarray(rows[r]["R"], np.float64).reshape(9)
-                t = np.asarray(rows[r]["t"], np.float64).reshape(3) / 1000.0
+                R, t = _row_pose(rows[r])
                 for i in inst:
                     it = tree.instances[i]
                     Re.append(R), te.append(t), Rg.append(it["R"].reshape(9)), tg.append(it["t"])
@@ -739,8 +746,7 @@ def eval_results(dataset, rows, device, chunk_images: int = 32, delta: float = b
             i32 = lambda a: torch.tensor(a, dtype=torch.int32)               # noqa: E731
             Kt = torch.tensor(K4, dtype=torch.float32)
             pose = (f64(Re), f64(te), f64(Rg), f64(tg))
-            v = bop.vsd(mesh["verts"], mesh["faces"], i32(fr), *pose, Kt, h2d(torch.from_numpy(depth), device), i32(fi),
-                        f64(dia), 1.0, delta, taus)
+            v = bop.vsd(mesh["verts"], mesh["faces"], i32(fr), *pose, Kt, depth, i32(fi), f64(dia), 1.0, delta, taus)
             m = bop.mssd_mspd(mesh["verts"], i32(vr), *pose, Kt, mesh["syms"], i32(sr))
             err = torch.cat([v["e_vsd"], m["mssd"][:, None], m["mspd"][:, None]], 1)
         else:
@@ -757,9 +763,8 @@ def eval_results(dataset, rows, device, chunk_images: int = 32, delta: float = b
         for i, x in zip(slots, col.cpu().tolist()):
             matches[i] = erows[x] if x >= 0 else -1
     n_obj = {o: sum(len(v) for k, v in groups.items() if k[2] == o) for o in objs}
-    c_obj = {o: sum(len(est[k]) if tree.inst_count[k] <= 0 else min(tree.inst_count[k], len(est[k]))
-                    for k in groups if k[2] == o) for o in objs}
-    out: Dict[str, object] = bop.recalls_from_tp(tp[:len(objs)].sum(0), len(tree.instances), count)
+    c_obj = {o: sum(take[k] for k in groups if k[2] == o) for o in objs}
+    out: Dict[str, object] = bop.recalls_from_tp(tp[:len(objs)].sum(0), len(tree.instances), sum(take.values()))
     out["per_obj"] = {o: bop.recalls_from_tp(tp[a], n_obj[o], c_obj[o]) for a, o in enumerate(objs)}
     out["ignored"], out["matches"] = ignored, matches
     return out

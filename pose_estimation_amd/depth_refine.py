@@ -25,6 +25,7 @@ from typing import Optional, Union
 import torch
 
 from . import _lib
+from .bop import per_crop, stage_scene
 from .icp import STATUS  # noqa: F401  (the same four codes, in the same order)
 from .runtime import h2d, ptr, stream_ptr
 
@@ -40,14 +41,6 @@ RADIUS_FRAC = 0.5    # rho = diameter / 2: a unit of the scaled rotation moves t
                      # translation, so one damping value serves both
 
 
-def _per_crop(x: Union[float, torch.Tensor], B: int, device, name: str) -> torch.Tensor:
-    if isinstance(x, torch.Tensor):
-        if x.numel() != B:
-            raise ValueError(f"{name} must be a float or a [B] tensor with B = {B}, got {tuple(x.shape)}")
-        return h2d(x.reshape(B), device, torch.float64)
-    return h2d(torch.full((B,), float(x), dtype=torch.float64), device)
-
-
 def refine(verts: torch.Tensor, faces: torch.Tensor, face_range: torch.Tensor, R: torch.Tensor, t: torch.Tensor,
            K4: torch.Tensor, depth: torch.Tensor, frame: torch.Tensor, max_dist: Union[float, torch.Tensor],
            radius: Union[float, torch.Tensor], mask: Optional[torch.Tensor] = None, depth_scale: float = 1.0,
@@ -59,32 +52,17 @@ def refine(verts: torch.Tensor, faces: torch.Tensor, face_range: torch.Tensor, R
     [B] and tensor max_dist / radius [B] may be host tensors (staged here). Nothing is read back and the host makes
     no decision between the launches: the start poses may come straight from a solver's launch. The inputs are not
     modified."""
-    if not (verts.is_cuda and faces.is_cuda and depth.is_cuda and (mask is None or mask.is_cuda)):
-        raise RuntimeError("depth_refine.refine runs on the HIP path only (verts / faces / depth / mask must be GPU "
-                           "tensors)")
-    dev = verts.device
-    B = int(face_range.reshape(-1, 2).shape[0])
-    if depth.dim() != 3:
-        raise ValueError(f"depth must be [F, H, W], got {tuple(depth.shape)}")
+    # every converted operand stays bound until the launches are enqueued (metric.add_metric's rule)
+    s = stage_scene("depth_refine.refine", verts, faces, face_range, K4, depth, frame, mask)
+    dev, B = verts.device, s.B
     if R.numel() != 9 * B or t.numel() != 3 * B:
         raise ValueError(f"R must be [B, 3, 3] and t [B, 3] with B = {B}, got {tuple(R.shape)}, {tuple(t.shape)}")
-    if mask is not None and (mask.dtype != torch.uint8 or tuple(mask.shape) != tuple(depth.shape)):
-        raise ValueError(f"mask must be uint8 {tuple(depth.shape)}, got {mask.dtype} {tuple(mask.shape)}")
-    # every converted operand stays bound until the launches are enqueued (metric.add_metric's rule)
-    v = verts.to(torch.float32).contiguous()
-    f = faces.to(torch.int32).contiguous()
-    d = depth.to(torch.float32).contiguous()
-    m = mask.contiguous() if mask is not None else None
-    fr = h2d(face_range.reshape(B, 2), dev, torch.int32)
     R0 = h2d(R.reshape(B, 9), dev, torch.float32)
     t0 = h2d(t.reshape(B, 3), dev, torch.float32)
-    K = h2d(K4.reshape(B, 4), dev, torch.float32)
-    fi = h2d(frame.reshape(B), dev, torch.int32)
-    md = _per_crop(max_dist, B, dev, "max_dist")
-    rho = _per_crop(radius, B, dev, "radius")
-    F, H, W = d.shape
+    md = per_crop(max_dist, B, dev, "max_dist")
+    rho = per_crop(radius, B, dev, "radius")
     n_bytes = ctypes.c_longlong(0)
-    _lib.call("krrn_pose_refine_depth_ws", B, H, W, ctypes.byref(n_bytes))
+    _lib.call("krrn_pose_refine_depth_ws", B, s.H, s.W, ctypes.byref(n_bytes))
     ws = torch.empty(((n_bytes.value + 7) // 8,), dtype=torch.float64, device=dev)
     Rn = torch.empty((B, 3, 3), dtype=torch.float32, device=dev)
     tn = torch.empty((B, 3), dtype=torch.float32, device=dev)
@@ -92,10 +70,10 @@ def refine(verts: torch.Tensor, faces: torch.Tensor, face_range: torch.Tensor, R
             "pairs": torch.empty((B,), dtype=torch.int32, device=dev),
             "rmse": torch.empty((B,), dtype=torch.float32, device=dev),
             "status": torch.empty((B,), dtype=torch.int32, device=dev)}
-    _lib.call("krrn_pose_refine_depth_f32", ptr(v), v.shape[0], ptr(f), f.shape[0], ptr(fr), ptr(R0), ptr(t0), ptr(K),
-              ptr(d), ptr(m), F, H, W, ptr(fi), float(depth_scale), ptr(md), ptr(rho), int(max_iter), float(tol),
-              int(min_pairs), float(damp), B, ptr(ws), ptr(Rn), ptr(tn), ptr(info["passes"]), ptr(info["pairs"]),
-              ptr(info["rmse"]), ptr(info["status"]), stream_ptr(dev))
+    _lib.call("krrn_pose_refine_depth_f32", ptr(s.v), s.v.shape[0], ptr(s.f), s.f.shape[0], ptr(s.fr), ptr(R0), ptr(t0),
+              ptr(s.K), ptr(s.d), ptr(s.m), s.F, s.H, s.W, ptr(s.fi), float(depth_scale), ptr(md), ptr(rho),
+              int(max_iter), float(tol), int(min_pairs), float(damp), B, ptr(ws), ptr(Rn), ptr(tn), ptr(info["passes"]),
+              ptr(info["pairs"]), ptr(info["rmse"]), ptr(info["status"]), stream_ptr(dev))
     if return_info:
         return Rn, tn, info
     return Rn, tn

@@ -25,15 +25,15 @@ from __future__ import annotations
 
 import copy
 from collections import namedtuple
-from typing import Dict, List, Optional, Sequence
+from typing import Dict, List, NamedTuple, Optional, Sequence
 
 import numpy as np
 import torch
 import torch.distributed as dist
 
 from . import distributed as kd
-from .bop import BOP_REC, FRAME_W, TAUS, bop_errors, fold_bop
-from .bop_scene import eval_results, write_result_masks, write_results
+from .bop import BOP_REC, FRAME_W, TAUS, bop_errors, fold_bop, valid_by_crop
+from .bop_scene import _require, eval_results, write_result_masks, write_results
 from .dataset import PoseDataset
 from .krrn import KRRN
 from .loss import map_losses
@@ -55,8 +55,30 @@ POSE_REC = ("crop",) + tuple(f"r{k}" for k in range(9)) + ("tx", "ty", "tz")
 # two counts the score is made of
 SEL_REC = ("crop", "cand", "score", "inter", "union", "valid")
 # what one evaluated batch leaves on the device until the epoch's single read-back (idx: its crop indices, on
-# the host; pred_t / add_f are None without opt_pose, lc without GT maps)
-_Batch = namedtuple("_Batch", "idx cls_id target_r target_t base_r base_t pred_t fin_r add_b add_f lc")
+# the host; score_r / score_t: the pose test_dis scores, i.e. the final pose (fin_r, pred_t) with opt_pose and the base
+# pose without; add_f is None without opt_pose, lc without GT maps)
+_Batch = namedtuple("_Batch", "idx cls_id target_r target_t base_r base_t score_r score_t add_b add_f lc")
+
+
+class EpochTables(NamedTuple):
+    """The per-crop tables of one eval epoch, f64 with one row per crop in the order evaluated, or None for a table
+    that was not asked for: rec [n, len(REC)], bop [n, len(BOP_REC)], poses [n, len(POSE_REC)], sel [n, len(SEL_REC)]."""
+    rec: Optional[torch.Tensor] = None
+    bop: Optional[torch.Tensor] = None
+    poses: Optional[torch.Tensor] = None
+    sel: Optional[torch.Tensor] = None
+
+    def legacy(self):
+        """eval_records' documented return: the tables that are set, in the order rec, bop, poses, sel, as a tuple;
+        rec alone as the lone tensor."""
+        tabs = tuple(t for t in self if t is not None)
+        return tabs if len(tabs) > 1 else tabs[0]
+
+    @classmethod
+    def of(cls, ret, bop: bool, poses: bool, select: bool) -> "EpochTables":
+        """The bundle back from legacy()'s value, given which tables were asked for."""
+        tabs = iter(ret if isinstance(ret, tuple) else (ret,))
+        return cls(*(next(tabs) if on else None for on in (True, bop, poses, select)))
 
 
 def _batches(buckets: Dict[int, List[int]], bs: int):
@@ -121,10 +143,10 @@ def eval_records(model: KRRN, dataset: PoseDataset, indices: Dict[int, List[int]
         raise ValueError(f"select must be None or 'depth', got {select!r}")
     if select and not opt_pose:
         raise ValueError("select='depth' chooses the final pose: it needs opt_pose=True")
-    if select and not getattr(dataset, "meshes", False):
-        raise ValueError("select='depth' renders the objects' meshes: it needs a dataset with meshes=True")
-    if refine == "depth" and not getattr(dataset, "meshes", False):
-        raise ValueError("refine='depth' renders the objects' meshes: it needs a dataset with meshes=True")
+    if select:
+        _require(dataset, "select='depth' renders the objects' meshes: it needs a dataset with meshes=True", meshes=True)
+    if refine == "depth":
+        _require(dataset, "refine='depth' renders the objects' meshes: it needs a dataset with meshes=True", meshes=True)
     solve_pose = get_pose if pose_solver == "pnp" else get_pose_umeyama
     metric = Metric(dataset.sym_obj)
     pending = []
@@ -194,91 +216,72 @@ def eval_records(model: KRRN, dataset: PoseDataset, indices: Dict[int, List[int]
                     sel = select_pose(cands, data, dataset)
                     fin_r, pred_t = sel["R"], sel["t"]
                     sel_pending.append(sel)
+                # the pose test_dis scores, chosen here once: the final pose, or the base pose without opt_pose
+                score_r, score_t = (fin_r, pred_t) if opt_pose else (base_r, base_t.reshape(B, 3))
                 add_f = None
                 if opt_pose:
                     # reg = final = (PnP R, TBase t) (trainer.py:198-201)
                     add_f = add_metric(fin_r, pred_t, data["model_points"], data["target"], data["cls_id"],
                                        metric.sys)
                 if bop:
-                    bop_pending.append(bop_errors(fin_r, pred_t, data, dataset) if opt_pose else
-                                       bop_errors(base_r, base_t.reshape(B, 3), data, dataset))
-            pending.append(_Batch(idx, data["cls_id"], data["target_r"], data["target_t"], base_r, base_t, pred_t,
-                                  fin_r, add_b, add_f, lc))
+                    bop_pending.append(bop_errors(score_r, score_t, data, dataset))
+            pending.append(_Batch(idx, data["cls_id"], data["target_r"], data["target_t"], base_r, base_t, score_r,
+                                  score_t, add_b, add_f, lc))
     finally:
         model.return_views = views
     main.wait_stream(pstr)
     for p in pending:  # made on the pose stream, read back on the caller's
-        for t in (p.base_r, p.base_t, p.add_b, p.add_f) + ((p.pred_t, p.fin_r) if refine or select else ()):
+        for t in (p.base_r, p.base_t, p.add_b, p.add_f) + ((p.score_t, p.score_r) if refine or select else ()):
             if t is not None:
                 t.record_stream(main)
     for e in bop_pending + sel_pending:
         for t in e.values():
             t.record_stream(main)
-    if not pending:
-        empty = (torch.zeros((0, len(REC)), dtype=torch.float64),)
-        empty += (torch.zeros((0, len(BOP_REC)), dtype=torch.float64),) if bop else ()
-        empty += (torch.zeros((0, len(POSE_REC)), dtype=torch.float64),) if poses else ()
-        empty += (torch.zeros((0, len(SEL_REC)), dtype=torch.float64),) if select else ()
-        return empty if len(empty) > 1 else empty[0]
     # one read-back and one vectorised host pass for the whole epoch: per batch, the rotation /
     # translation errors' six small copies and ~60 CPU ops ran after the GPU had drained (a serial
     # host tail of ~1 ms per batch); every quantity is per crop, so the values are the same
-    cat = lambda k, w: torch.cat([getattr(p, k).reshape(len(p.idx), w) for p in pending])  # noqa: E731
     n = sum(len(p.idx) for p in pending)
-    rec = np.zeros((n, len(REC)), dtype=np.float64)
-    rec[:, _R["crop"]] = np.concatenate([np.asarray(p.idx, dtype=np.float64) for p in pending])
-    rec[:, _R["cls"]] = cat("cls_id", 1).reshape(n).cpu().numpy()
-    rec[:, _R["valid"]] = 1.0
-    o = 0
-    for p in pending:
-        if p.lc is not None:
-            rec[o:o + len(p.idx), [_R["l_xyz"], _R["l_normal"], _R["l_mask"]]] = p.lc.cpu().numpy()[:, [0, 1, 3]]
-        o += len(p.idx)
-    base_r, tr, tt = cat("base_r", 9), cat("target_r", 9), cat("target_t", 3)
-    rec[:, _R["add_b"]] = cat("add_b", 1).reshape(n).cpu().numpy()
-    rec[:, _R["r_b"]], rec[:, _R["t_b"]] = rt_errors(base_r, cat("base_t", 3), tr, tt)
-    if opt_pose:
-        rec[:, _R["add_f"]] = cat("add_f", 1).reshape(n).cpu().numpy()
-        fin_r = cat("fin_r", 9) if refine or select else base_r
-        rec[:, _R["r_f"]], rec[:, _R["t_f"]] = rt_errors(fin_r, cat("pred_t", 3), tr, tt)
-    prec = None
-    if poses:
-        prec = np.zeros((n, len(POSE_REC)), dtype=np.float64)
-        prec[:, 0] = rec[:, _R["crop"]]
+    rec, brec, prec, srec = (np.zeros((n, len(cols)), dtype=np.float64) if on else None for on, cols in
+                             ((True, REC), (bop, BOP_REC), (poses, POSE_REC), (select, SEL_REC)))
+    if pending:
+        cat = lambda k, w: torch.cat([getattr(p, k).reshape(len(p.idx), w) for p in pending])  # noqa: E731
+        crop = rec[:, _R["crop"]] = np.concatenate([np.asarray(p.idx, dtype=np.float64) for p in pending])
+        rec[:, _R["cls"]] = cat("cls_id", 1).reshape(n).cpu().numpy()
+        rec[:, _R["valid"]] = 1.0
+        o = 0
+        for p in pending:
+            if p.lc is not None:
+                rec[o:o + len(p.idx), [_R["l_xyz"], _R["l_normal"], _R["l_mask"]]] = p.lc.cpu().numpy()[:, [0, 1, 3]]
+            o += len(p.idx)
+        tr, tt, score_r, score_t = cat("target_r", 9), cat("target_t", 3), cat("score_r", 9), cat("score_t", 3)
+        rec[:, _R["add_b"]] = cat("add_b", 1).reshape(n).cpu().numpy()
+        rec[:, _R["r_b"]], rec[:, _R["t_b"]] = rt_errors(cat("base_r", 9), cat("base_t", 3), tr, tt)
         if opt_pose:
-            prec[:, 1:10] = (cat("fin_r", 9) if refine or select else base_r).double().cpu().numpy()
-            prec[:, 10:13] = cat("pred_t", 3).double().cpu().numpy()
-        else:
-            prec[:, 1:10] = base_r.double().cpu().numpy()
-            prec[:, 10:13] = cat("base_t", 3).double().cpu().numpy()
-    tail = (torch.from_numpy(prec),) if poses else ()
-    if select:
-        srec = np.zeros((n, len(SEL_REC)), dtype=np.float64)
-        best = torch.cat([e["best"] for e in sel_pending]).cpu().numpy().astype(np.int64)
-        score = np.concatenate([e["score"].cpu().numpy() for e in sel_pending])      # [n, C]: one C per epoch
-        counts = np.concatenate([e["counts"].cpu().numpy() for e in sel_pending])    # [n, C, 6]
-        rows = np.arange(n)
-        srec[:, 0], srec[:, 1], srec[:, 2], srec[:, -1] = rec[:, _R["crop"]], best, score[rows, best], 1.0
-        srec[:, 3], srec[:, 4] = counts[rows, best, 4], counts[rows, best, 5]
-        tail += (torch.from_numpy(srec),)
-    if not bop:
-        return (torch.from_numpy(rec),) + tail if tail else torch.from_numpy(rec)
-    T = len(TAUS)
-    brec = np.zeros((n, len(BOP_REC)), dtype=np.float64)
-    brec[:, 0], brec[:, 1], brec[:, -1] = rec[:, _R["crop"]], rec[:, _R["cls"]], 1.0
-    brec[:, 2:2 + T] = torch.cat([e["vsd"] for e in bop_pending]).cpu().numpy()
-    brec[:, 2 + T] = torch.cat([e["mssd"] for e in bop_pending]).cpu().numpy()
-    brec[:, 3 + T] = torch.cat([e["mspd"] for e in bop_pending]).cpu().numpy()
-    return (torch.from_numpy(rec), torch.from_numpy(brec)) + tail
+            rec[:, _R["add_f"]] = cat("add_f", 1).reshape(n).cpu().numpy()
+            rec[:, _R["r_f"]], rec[:, _R["t_f"]] = rt_errors(score_r, score_t, tr, tt)
+        if poses:
+            prec[:, 0], prec[:, 1:10], prec[:, 10:13] = crop, score_r.double().cpu().numpy(), score_t.double().cpu().numpy()
+        if select:
+            best = torch.cat([e["best"] for e in sel_pending]).cpu().numpy().astype(np.int64)
+            score = np.concatenate([e["score"].cpu().numpy() for e in sel_pending])      # [n, C]: one C per epoch
+            counts = np.concatenate([e["counts"].cpu().numpy() for e in sel_pending])    # [n, C, 6]
+            rows = np.arange(n)
+            srec[:, 0], srec[:, 1], srec[:, 2], srec[:, -1] = crop, best, score[rows, best], 1.0
+            srec[:, 3], srec[:, 4] = counts[rows, best, 4], counts[rows, best, 5]
+        if bop:
+            T = len(TAUS)
+            brec[:, 0], brec[:, 1], brec[:, -1] = crop, rec[:, _R["cls"]], 1.0
+            brec[:, 2:2 + T] = torch.cat([e["vsd"] for e in bop_pending]).cpu().numpy()
+            brec[:, 2 + T] = torch.cat([e["mssd"] for e in bop_pending]).cpu().numpy()
+            brec[:, 3 + T] = torch.cat([e["mspd"] for e in bop_pending]).cpu().numpy()
+    return EpochTables(*(None if t is None else torch.from_numpy(t) for t in (rec, brec, prec, srec))).legacy()
 
 
 def fold_records(records: torch.Tensor, objlist: Sequence[int], diameter: Sequence[float], opt_pose: bool,
                  metric: Metric) -> Dict[str, object]:
     """The reference's per-object bookkeeping (trainer.py:165-250) over per-crop records, in global
     crop order (independent of how crops were batched or sharded)."""
-    rec = records.numpy() if isinstance(records, torch.Tensor) else np.asarray(records)
-    rec = rec[rec[:, _R["valid"]] > 0]
-    rec = rec[np.argsort(rec[:, _R["crop"]], kind="stable")]
+    rec = valid_by_crop(records)
     result = {k: {o: 0.0 for o in objlist} for k in _KEYS}
     cls = rec[:, _R["cls"]].astype(np.int64)
     col = lambda k: rec[:, _R[k]]  # noqa: E731
@@ -322,6 +325,19 @@ def fold_records(records: torch.Tensor, objlist: Sequence[int], diameter: Sequen
     out["auc"] = {o: metric.cal_auc(v) for o, v in adds.items()}
     out["auc_all"] = metric.cal_auc([a for v in adds.values() for a in v]) if adds else 0.0
     return out
+
+
+def result_rows(pose_table, items, conf: Dict[int, float]) -> List[Dict[str, object]]:
+    """The epoch's scored poses as BOP result rows (bop_scene.write_results' dicts, t in millimetres) in crop order:
+    pose_table = the gathered POSE_REC rows plus a `valid` column, items = the BOP tree's (their scene, image and object
+    ids), conf = {crop: score}; a crop without one scores 1.0, and time is -1 (not measured per image). What the result
+    CSV, the matched recalls and the segmentation result file are all made from."""
+    rows = []
+    for row in valid_by_crop(pose_table):
+        it = items[int(row[0])]
+        rows.append({"scene_id": it["scene"], "im_id": it["im"], "obj_id": it["obj"], "score": conf.get(int(row[0]), 1.0),
+                     "R": row[1:10], "t": row[10:13] * 1000.0, "time": -1.0})
+    return rows
 
 
 def gather_epoch_records(local: torch.Tensor, shard_sizes: Sequence[int], device, group=None) -> torch.Tensor:
@@ -381,15 +397,19 @@ def test_epoch(model: KRRN, dataset: PoseDataset, bs: int = 64, device=None, opt
     PoseDataset(layout="bop", detections=seg_json) crops and masks a second pass from this pass's poses. One key is
     added, "seg": {"rows": the rows written, "empty": the estimates without a visible pixel}; no other key changes."""
     device = torch.device(device) if device is not None else next(model.parameters()).device
-    if seg_json and not (getattr(dataset, "layout", "linemod") == "bop" and getattr(dataset, "meshes", False)):
-        raise ValueError("seg_json renders the estimates' masks on a BOP tree: it needs a PoseDataset with layout='bop' "
-                         "and meshes=True")
-    if match and not (bop and getattr(dataset, "layout", "linemod") == "bop"):
-        raise ValueError("match=True scores result rows against a BOP tree: it needs bop=True and a PoseDataset with "
-                         "layout='bop'")
+    if seg_json:
+        _require(dataset, "seg_json renders the estimates' masks on a BOP tree: it needs a PoseDataset with layout='bop' "
+                 "and meshes=True", layout=True, meshes=True)
+    if match:
+        msg = "match=True scores result rows against a BOP tree: it needs bop=True and a PoseDataset with layout='bop'"
+        if not bop:
+            raise ValueError(msg)
+        _require(dataset, msg, layout=True)
     if bop and not match and getattr(getattr(dataset, "tree", None), "det_per_target", "best") == "inst_count":
         raise ValueError("a dataset built with det_per_target='inst_count' pairs crops with GT instances only "
                          "provisionally: bop=True needs match=True on it")
+    if bop_csv:
+        _require(dataset, "bop_csv writes BOP's scene / image ids: it needs a PoseDataset with layout='bop'", layout=True)
     if world is None:
         world = dist.get_world_size(group) if dist.is_initialized() else 1
     if rank is None:
@@ -398,32 +418,21 @@ def test_epoch(model: KRRN, dataset: PoseDataset, bs: int = 64, device=None, opt
         raise ValueError(f"rank {rank} outside world {world}")
     sizes = [dataset.crop_size(i) for i in range(len(dataset))]
     mine = kd.bucket_shard(sizes, world, rank)
-    if bop_csv and getattr(dataset, "layout", "linemod") != "bop":
-        raise ValueError("bop_csv writes BOP's scene / image ids: it needs a PoseDataset with layout='bop'")
-    local = eval_records(model, dataset, mine, bs, device, opt_pose=opt_pose, with_loss=criterion is not None,
-                         pose_solver=pose_solver, refine=refine, **({"bop": True} if bop else {}),
-                         **({"poses": True} if bop_csv or match or seg_json else {}), **({"select": select} if select else {}))
-    local_bop = local_pose = local_sel = None
-    if select:
-        local, local_sel = (local[:-1] if len(local) > 2 else local[0]), local[-1]
-    if bop_csv or match or seg_json:
-        local, local_pose = local[:-1] if bop else local[0], local[-1]
-        # gather_epoch_records marks pad rows by a last column `valid` = 0
-        local_pose = torch.cat([local_pose, torch.ones((local_pose.shape[0], 1), dtype=torch.float64)], 1)
-    if bop:
-        local, local_bop = local
+    want_poses = bool(bop_csv or match or seg_json)
+    local = EpochTables.of(eval_records(model, dataset, mine, bs, device, opt_pose=opt_pose, with_loss=criterion is not None,
+                                        pose_solver=pose_solver, refine=refine, bop=bool(bop), poses=want_poses,
+                                        select=select), bop, want_poses, select)
     shard_sizes = [sum(len(v) for v in kd.bucket_shard(sizes, world, r).values()) for r in range(world)]
-    allrec = gather_epoch_records(local, shard_sizes, device, group) if world > 1 else local
+    gather = lambda t: gather_epoch_records(t, shard_sizes, device, group) if world > 1 else t  # noqa: E731
     metric = Metric(dataset.sym_obj)
-    out = fold_records(allrec, dataset.objlist, dataset.diameter, opt_pose, metric)
+    out = fold_records(gather(local.rec), dataset.objlist, dataset.diameter, opt_pose, metric)
     det = bool(getattr(dataset, "detections", False))  # a detection-mode dataset: targets without an estimate count
     missed: Dict[int, int] = {}
     for _, _, obj in (dataset.tree.missed if det else ()):
         missed[obj] = missed.get(obj, 0) + 1
     if bop:  # a record table of its own, gathered by the same mechanism
-        allbop = gather_epoch_records(local_bop, shard_sizes, device, group) if world > 1 else local_bop
-        out["bop"] = fold_bop(allbop, dataset.objlist, dataset.diameter, getattr(dataset, "frame_hw", (0, FRAME_W))[1],
-                              **({"missed": missed} if det else {}))
+        out["bop"] = fold_bop(gather(local.bop), dataset.objlist, dataset.diameter,
+                              getattr(dataset, "frame_hw", (0, FRAME_W))[1], missed if det else None)
     conf = {}
     if det:
         st = dataset.tree.det_stats
@@ -432,26 +441,16 @@ def test_epoch(model: KRRN, dataset: PoseDataset, bs: int = 64, device=None, opt
                              "dropped": st["dropped"]}
         conf = {i: float(it["score"]) for i, it in enumerate(dataset.tree.items)}
     if select:
-        allsel = gather_epoch_records(local_sel, shard_sizes, device, group) if world > 1 else local_sel
-        tab = allsel.numpy()
-        tab = tab[tab[:, -1] > 0]
-        tab = tab[np.argsort(tab[:, 0], kind="stable")]
+        tab = valid_by_crop(gather(local.sel))
         picked = {int(c): int((tab[:, 1] == c).sum()) for c in sorted(set(tab[:, 1].tolist()))}
         out["select"] = {"picked": picked, "mean_score": float(np.cumsum(tab[:, 2])[-1]) / len(tab) if len(tab) else 0.0}
         conf = {int(r[0]): float(r[2]) for r in tab}
-    if bop_csv or match or seg_json:
-        allpose = gather_epoch_records(local_pose, shard_sizes, device, group) if world > 1 else local_pose
-        if rank == 0:
-            tab = allpose.numpy()
-            tab = tab[tab[:, -1] > 0]
-            tab = tab[np.argsort(tab[:, 0], kind="stable")]
-            rows = []
-            for row in tab:
-                it = dataset.tree.items[int(row[0])]
-                rows.append({"scene_id": it["scene"], "im_id": it["im"], "obj_id": it["obj"], "score": conf.get(int(row[0]), 1.0),
-                             "R": row[1:10], "t": row[10:13] * 1000.0, "time": -1.0})
-            if bop_csv:
-                write_results(bop_csv, rows)
+    if want_poses:
+        # gather_epoch_records marks pad rows by a last column `valid` = 0
+        allpose = gather(torch.cat([local.poses, torch.ones((local.poses.shape[0], 1), dtype=torch.float64)], 1))
+        rows = result_rows(allpose, dataset.tree.items, conf) if rank == 0 else None
+        if bop_csv and rank == 0:
+            write_results(bop_csv, rows)
         if seg_json:
             res = [None]
             if rank == 0:
@@ -468,8 +467,8 @@ def test_epoch(model: KRRN, dataset: PoseDataset, bs: int = 64, device=None, opt
     if world > 1:
         # the ranks' own crop / success tallies, summed, must equal the gathered table's
         key = "add_f" if opt_pose else "add_b"
-        dia = torch.tensor([dataset.diameter[int(c)] for c in local[:, _R["cls"]]], dtype=torch.float64)
-        mine_t = torch.tensor([float(local.shape[0]), float((local[:, _R[key]] < 0.1 * dia).sum())],
+        dia = torch.tensor([dataset.diameter[int(c)] for c in local.rec[:, _R["cls"]]], dtype=torch.float64)
+        mine_t = torch.tensor([float(local.rec.shape[0]), float((local.rec[:, _R[key]] < 0.1 * dia).sum())],
                               dtype=torch.float64)
         t = mine_t.to(device) if dist.get_backend(group) == "nccl" else mine_t
         dist.all_reduce(t, group=group)

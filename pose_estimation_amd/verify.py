@@ -17,7 +17,7 @@ from typing import Dict, Optional, Union
 import torch
 
 from . import _lib
-from .bop import DELTA
+from .bop import DELTA, per_crop, stage_scene
 from .runtime import h2d, ptr, stream_ptr
 
 TAU = DELTA                                             # metres: the tolerance BOP uses for the same question
@@ -33,42 +33,25 @@ def score_poses(verts: torch.Tensor, faces: torch.Tensor, face_range: torch.Tens
     depth [F, H, W] / mask u8 [F, H, W] are GPU tensors; face_range [B, 2], R [B, C, 3, 3], t [B, C, 3], K4 [B, 4],
     frame [B], box [B, 4] = (rmin, rmax, cmin, cmax) and tau (a float or [B], metres) may be host tensors (staged
     here). Nothing is read back: the candidates may come straight from a solver's launch."""
-    if not (verts.is_cuda and faces.is_cuda and depth.is_cuda and (mask is None or mask.is_cuda)):
-        raise RuntimeError("score_poses runs on the HIP path only (verts / faces / depth / mask must be GPU tensors)")
-    dev = verts.device
-    B = int(face_range.reshape(-1, 2).shape[0])
-    if depth.dim() != 3:
-        raise ValueError(f"depth must be [F, H, W], got {tuple(depth.shape)}")
+    # every converted operand stays bound until the launch is enqueued (metric.add_metric's rule)
+    s = stage_scene("score_poses", verts, faces, face_range, K4, depth, frame, mask)
+    dev, B = verts.device, s.B
     if t.dim() != 3 or t.shape[0] != B or t.shape[2] != 3:
         raise ValueError(f"t must be [B, C, 3] with B = {B}, got {tuple(t.shape)}")
     C = int(t.shape[1])
     if not 1 <= C <= MAX_C:
         raise ValueError(f"1 .. {MAX_C} candidates, got {C}")
-    if mask is not None and (mask.dtype != torch.uint8 or tuple(mask.shape) != tuple(depth.shape)):
-        raise ValueError(f"mask must be uint8 {tuple(depth.shape)}, got {mask.dtype} {tuple(mask.shape)}")
-    # every converted operand stays bound until the launch is enqueued (metric.add_metric's rule)
-    v = verts.to(torch.float32).contiguous()
-    f = faces.to(torch.int32).contiguous()
-    d = depth.to(torch.float32).contiguous()
-    m = mask.contiguous() if mask is not None else None
-    fr = h2d(face_range.reshape(B, 2), dev, torch.int32)
     Rd = h2d(R, dev, torch.float64).reshape(B, C, 9).contiguous()
     td = h2d(t, dev, torch.float64).reshape(B, C, 3).contiguous()
-    K = h2d(K4.reshape(B, 4), dev, torch.float32)
-    fi = h2d(frame.reshape(B), dev, torch.int32)
     bx = h2d(box.reshape(B, 4), dev, torch.int32) if box is not None else None
-    if isinstance(tau, torch.Tensor):
-        ta = h2d(tau.reshape(B), dev, torch.float64)
-    else:
-        ta = h2d(torch.full((B,), float(tau), dtype=torch.float64), dev)
-    F, H, W = d.shape
+    ta = per_crop(tau, B, dev, "tau")
     ws = torch.empty((B, C, 4), dtype=torch.int32, device=dev)        # krrn_pose_score_ws(B, C)
     out = {"counts": torch.empty((B, C, len(COUNTS)), dtype=torch.int32, device=dev),
            "score": torch.empty((B, C), dtype=torch.float64, device=dev),
            "best": torch.empty((B,), dtype=torch.int32, device=dev),
            "R": torch.empty((B, 3, 3), dtype=torch.float32, device=dev),
            "t": torch.empty((B, 3), dtype=torch.float32, device=dev)}
-    _lib.call("krrn_pose_score_f32", ptr(v), v.shape[0], ptr(f), f.shape[0], ptr(fr), ptr(Rd), ptr(td), C, ptr(K),
-              ptr(d), ptr(m), F, H, W, ptr(fi), ptr(bx), float(depth_scale), ptr(ta), B, ptr(ws), ptr(out["counts"]),
-              ptr(out["score"]), ptr(out["best"]), ptr(out["R"]), ptr(out["t"]), stream_ptr(dev))
+    _lib.call("krrn_pose_score_f32", ptr(s.v), s.v.shape[0], ptr(s.f), s.f.shape[0], ptr(s.fr), ptr(Rd), ptr(td), C,
+              ptr(s.K), ptr(s.d), ptr(s.m), s.F, s.H, s.W, ptr(s.fi), ptr(bx), float(depth_scale), ptr(ta), B, ptr(ws),
+              ptr(out["counts"]), ptr(out["score"]), ptr(out["best"]), ptr(out["R"]), ptr(out["t"]), stream_ptr(dev))
     return out
