@@ -646,6 +646,30 @@ int krrn_rle_encode_ws(int n, int W, long long* n_ints);
 int krrn_rle_encode_u8(const unsigned char* mask, int n, int H, int W, int max_runs, int* ws, int* counts,
                        int* n_runs, int* info, void* stream);
 
+/* Paste the mask head's logits into full-frame planes: B crops, each the S x S window of its H x W frame whose top
+ * left pixel is (rmin, cmin), to u8 masks that krrn_rle_encode_u8 takes. logits f32: crop b, channel c, pixel (i, j)
+ * at logits[b ld_b + (c S + i) S + j], ld_b >= C1 S S (a channel slice of a wider tensor is passed as it lies);
+ * chan int32 [B], rc int32 [B][2] = (rmin, cmin), device memory. The label convention is multi_cls_mask = mask (cls +
+ * 1): channel 0 is background and channel cls + 1 the object. Per crop pixel, with ordinary IEEE comparisons,
+ *   best = 0; for c = 1 .. C1 - 1: if (l[c] > l[best]) best = c
+ * so ties go to the lowest channel, -0.0 ties with +0.0, a NaN logit never wins and a NaN in channel 0 leaves best =
+ * 0. The pixel is set iff (1 <= chan[b] < C1 and best == chan[b]) or (chan[b] == 0 and best != 0: any foreground);
+ * any other chan[b] sets nothing. Crop pixel (i, j) is frame pixel (rmin + i, cmin + j); pixels outside [0, H) x
+ * [0, W) are dropped. The differences are taken in 64-bit: any rc, INT32_MIN / INT32_MAX included, reads and writes
+ * nothing out of bounds. Outputs: mask u8 [B][H][W] row-major at any byte address, every byte written by the call, 1
+ * where set and 0 elsewhere (no memset by the caller or the entry point); info int32 [B][5] = (pixel count, x, y, w,
+ * h) exactly as krrn_rle_decode_u8 defines it (w = x_max - x_min, h = y_max - y_min; five zeros for an empty mask),
+ * every row written by the entry point. Two launches: 16 x 16 frame tiles, a block per span of 8 side by side and
+ * crop (a tile the window cannot touch stores zeros without reading a logit), then for info one block per crop that
+ * reduces the plane's bytes inside the clipped window in a fixed order: no atomics. Comparisons and integer work
+ * only: the result is deterministic and a crop's does not depend on the rest of the batch, bit for bit. Nothing is
+ * read back (the call can be captured in a graph). Host checks, before any HIP call: null logits / chan / rc /
+ * mask / info or overlapping buffers KRRN_EARG; B < 0, C1 < 1, S < 1, H <= 0, W <= 0, H W > INT32_MAX, C1 S S >
+ * INT32_MAX or ld_b < C1 S S KRRN_ESHAPE (shapes are tested before overlap, whose extents they give); B == 0
+ * returns 0 and launches nothing. */
+int krrn_mask_paste_f32(const float* logits, long long ld_b, int C1, int S, const int* chan, const int* rc, int B,
+                        int H, int W, unsigned char* mask, int* info, void* stream);
+
 /* MSSD / MSPD, the maximum symmetry-aware surface / projection distance. verts f32 [Vtot][3] (all mesh
  * vertices), vert_range int32 [B][2] = first vertex, count of crop b; syms f64 [NStot][12] = row-major R
  * then t (metres, model frame), sym_range int32 [B][2] (each object's set begins with the identity). Per

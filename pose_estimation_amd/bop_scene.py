@@ -39,6 +39,8 @@ hold several rows per target. BopTree(..., det_per_target="inst_count") makes on
 Masks of a result file. write_result_masks(path, dataset, rows, device) renders every estimate's visible mask against
 the observed depth (bop.visibility under the estimated pose), encodes it on the GPU (rle.encode_planes) and writes
 the rows in the detection format above: a segmentation result file, which BopTree(..., detections=path) reads back.
+net_mask_rows(rows, runs, info, H, W) makes the same rows from masks that are already run lists: the network's own
+segmentation, which evaluate.test_epoch(seg_json=..., seg_source="net") pastes and encodes per batch.
 
 Out of scope: binary PLY."""
 from __future__ import annotations
@@ -630,6 +632,27 @@ def write_result_masks(path, dataset, rows, device, chunk_images: int = 32, delt
     det, stats = result_masks(dataset, rows, device, chunk_images, delta)
     write_detections(path, det)
     return det, stats
+
+
+def net_mask_rows(rows, runs, info, H: int, W: int):
+    """The network's own masks as detection rows (host only): `rows` = result rows as evaluate.result_rows /
+    read_results give them, runs[k] = the run list of row k's full-frame H x W mask and info[k] its five ints (pixel
+    count, x, y, w, h), as rle.paste_masks and rle.encode_planes return them. Row k gives {scene_id, image_id,
+    category_id, score = the row's, bbox = [x, y, w, h] of info as floats, segmentation = {"counts": run list, "size":
+    [H, W]}, time = the row's}: _check_rows' normal form, the dict result_masks builds, in the order of `rows`. A row
+    whose pixel count is 0 gives no row. Returns (rows, {"empty": the number of those})."""
+    if not len(rows) == len(runs) == len(info):
+        raise ValueError(f"{len(rows)} rows, {len(runs)} run lists and {len(info)} info rows: one of each per row")
+    out, empty = [], 0
+    for row, r, q in zip(rows, runs, info):
+        q = [int(v) for v in q]
+        if q[0] == 0:
+            empty += 1
+            continue
+        out.append({"scene_id": int(row["scene_id"]), "image_id": int(row["im_id"]), "category_id": int(row["obj_id"]),
+                    "score": float(row["score"]), "bbox": [float(v) for v in q[1:5]],
+                    "segmentation": {"counts": [int(v) for v in r], "size": [int(H), int(W)]}, "time": float(row["time"])})
+    return out, {"empty": empty}
 
 
 RESULT_HEADER = "scene_id,im_id,obj_id,score,R,t,time"

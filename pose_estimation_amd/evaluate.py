@@ -33,7 +33,8 @@ import torch.distributed as dist
 
 from . import distributed as kd
 from .bop import BOP_REC, FRAME_W, TAUS, bop_errors, fold_bop, valid_by_crop
-from .bop_scene import _require, eval_results, write_result_masks, write_results
+from . import rle
+from .bop_scene import _require, eval_results, net_mask_rows, write_detections, write_result_masks, write_results
 from .dataset import PoseDataset
 from .krrn import KRRN
 from .loss import map_losses
@@ -92,7 +93,7 @@ def _batches(buckets: Dict[int, List[int]], bs: int):
 def eval_records(model: KRRN, dataset: PoseDataset, indices: Dict[int, List[int]], bs: int, device,
                  opt_pose: bool = True, with_loss: bool = True, pose_solver: str = "pnp",
                  refine: Optional[str] = None, bop: bool = False, poses: bool = False,
-                 select: Optional[str] = None):
+                 select: Optional[str] = None, net_masks: bool = False):
     """Run the eval path over {S: [crop indices]} in batches of <= bs; returns f64 [n, len(REC)]
     (rows in the order evaluated). Every batch's inputs, forward, pose and ADD(-S) are queued on
     the device without a host round trip; the per-crop records are read back once at the end (the
@@ -134,7 +135,16 @@ def eval_records(model: KRRN, dataset: PoseDataset, indices: Dict[int, List[int]
     (PnP R, raw pred_t) and 3 the unrefined base pose. The winner replaces the final pose for add_f, r_f / t_f,
     the BOP errors and the pose table; the base columns are untouched. One more launch per batch on the pose
     stream, no host round trip. The return value then ends with an f64 [n, len(SEL_REC)] table in the same row
-    order, read back in the epoch's single read-back. With select=None nothing changes."""
+    order, read back in the epoch's single read-back. With select=None nothing changes.
+
+    net_masks (off by default: nothing changes; needs a dataset with layout="bop", whose frames share one size): also
+    the network's own segmentation of every crop as a full-frame mask. Right after each forward, on its stream and
+    so before the next forward rewrites the plan's buffer, rle.paste_masks decides every pixel of the view
+    pred["mask"] for channel cls_id + 1 and places the crop's window (dataset.boxes: rows rmin .., columns cmin ..)
+    into a plane of dataset.frame_hw, and rle.encode_gpu encodes the planes; chan and rc are built on the host. The
+    runs are read back once the batch's pose step is queued (one read-back per batch, and one more encode for a
+    batch in which a mask outgrows the encoder's default slot), so the planes live for one batch only. The return
+    value then ends with a list [(crop, run list, info = the mask's five ints)] in the same row order."""
     if pose_solver not in ("pnp", "umeyama"):
         raise ValueError(f"pose_solver must be 'pnp' or 'umeyama', got {pose_solver!r}")
     if refine not in (None, "icp", "depth"):
@@ -147,11 +157,14 @@ def eval_records(model: KRRN, dataset: PoseDataset, indices: Dict[int, List[int]
         _require(dataset, "select='depth' renders the objects' meshes: it needs a dataset with meshes=True", meshes=True)
     if refine == "depth":
         _require(dataset, "refine='depth' renders the objects' meshes: it needs a dataset with meshes=True", meshes=True)
+    if net_masks:
+        _require(dataset, "net_masks pastes into a BOP tree's frames: it needs a PoseDataset with layout='bop'", layout=True)
     solve_pose = get_pose if pose_solver == "pnp" else get_pose_umeyama
     metric = Metric(dataset.sym_obj)
     pending = []
     bop_pending = []   # per batch, with bop: bop_errors' dict of device tensors
     sel_pending = []   # per batch, with select: select_pose's dict of device tensors
+    net = []           # with net_masks: (crop, run list, info) per crop
     batches = list(_batches(indices, bs))
     device = torch.device(device)
     dia = torch.tensor(dataset.diameter, dtype=torch.float32).to(device) if refine else None  # [classes], metres
@@ -184,6 +197,11 @@ def eval_records(model: KRRN, dataset: PoseDataset, indices: Dict[int, List[int]
                 nxt = build(j + 1)
             pred = model(data["img_croped"], data["cloud"], data["choose"], data["cls_id"], opt_pose=opt_pose)
             B = len(idx)
+            pasted = enc = None
+            if net_masks:  # pred["mask"] is a view of the plan's buffer: read here, on the forward's stream
+                pasted = rle.paste_masks(pred["mask"], [dataset.objlist.index(dataset._meta(i)[0]) + 1 for i in idx],
+                                         [[dataset.boxes[i][0], dataset.boxes[i][2]] for i in idx], *dataset.frame_hw)
+                enc = rle.encode_gpu(pasted["mask"])
             lc = None
             if with_loss and "xyz" in data and "multi_cls_mask" in data:
                 lc = map_losses(pred, data, per_crop=True)  # [B, 8]: xyz, normal, region, mask, counts
@@ -227,6 +245,9 @@ def eval_records(model: KRRN, dataset: PoseDataset, indices: Dict[int, List[int]
                     bop_pending.append(bop_errors(score_r, score_t, data, dataset))
             pending.append(_Batch(idx, data["cls_id"], data["target_r"], data["target_t"], base_r, base_t, score_r,
                                   score_t, add_b, add_f, lc))
+            if net_masks:  # the host waits for this forward only now, with the pose step and the next inputs queued
+                runs, info = rle.runs_of(pasted["mask"], enc), pasted["info"].cpu().numpy()
+                net += [(int(i), runs[k], [int(v) for v in info[k]]) for k, i in enumerate(idx)]
     finally:
         model.return_views = views
     main.wait_stream(pstr)
@@ -274,7 +295,10 @@ def eval_records(model: KRRN, dataset: PoseDataset, indices: Dict[int, List[int]
             brec[:, 2:2 + T] = torch.cat([e["vsd"] for e in bop_pending]).cpu().numpy()
             brec[:, 2 + T] = torch.cat([e["mssd"] for e in bop_pending]).cpu().numpy()
             brec[:, 3 + T] = torch.cat([e["mspd"] for e in bop_pending]).cpu().numpy()
-    return EpochTables(*(None if t is None else torch.from_numpy(t) for t in (rec, brec, prec, srec))).legacy()
+    tabs = EpochTables(*(None if t is None else torch.from_numpy(t) for t in (rec, brec, prec, srec))).legacy()
+    if net_masks:
+        return (tabs if isinstance(tabs, tuple) else (tabs,)) + (net,)
+    return tabs
 
 
 def fold_records(records: torch.Tensor, objlist: Sequence[int], diameter: Sequence[float], opt_pose: bool,
@@ -361,7 +385,7 @@ def test_epoch(model: KRRN, dataset: PoseDataset, bs: int = 64, device=None, opt
                criterion=None, world: Optional[int] = None, rank: Optional[int] = None,
                group=None, pose_solver: str = "pnp", refine: Optional[str] = None,
                bop: bool = False, bop_csv: Optional[str] = None, select: Optional[str] = None,
-               match: bool = False, seg_json: Optional[str] = None) -> Dict[str, object]:
+               match: bool = False, seg_json: Optional[str] = None, seg_source: str = "render") -> Dict[str, object]:
     """Trainer.test_epoch over `dataset`. world/rank default to the initialised process group
     (1/0 without one). `criterion` enables the per-crop map-loss terms (dis_xyz / dis_mask /
     dis_normal) when the batches carry GT maps, i.e. for a PoseDataset built with gt_maps=True (a
@@ -395,9 +419,25 @@ def test_epoch(model: KRRN, dataset: PoseDataset, bs: int = 64, device=None, opt
     writes them and calls bop_scene.write_result_masks(seg_json, dataset, rows, device), which renders each pose's
     visible mask against the observed depth and encodes it on the GPU. The file is in the detection format, so
     PoseDataset(layout="bop", detections=seg_json) crops and masks a second pass from this pass's poses. One key is
-    added, "seg": {"rows": the rows written, "empty": the estimates without a visible pixel}; no other key changes."""
+    added, "seg": {"rows": the rows written, "empty": the estimates without a visible pixel}; no other key changes.
+    `seg_source` says whose masks `seg_json` holds: "render" (the default) the rendered ones above; "net" the network's
+    own segmentation, the mask head's logits that otherwise only the eval-time cross-entropy reads. It needs seg_json
+    and a dataset with layout="bop" but no meshes, and world == 1 (gathering the ranks' ragged run lists is not built);
+    ValueError otherwise, before any batch is built. Per batch eval_records(net_masks=True) pastes each crop's decided
+    pixels (channel cls_id + 1 wins) into a full-frame plane and encodes it on the GPU; rank 0 builds the result rows
+    exactly as `bop_csv` writes them, pairs them with the runs by crop and writes write_detections(seg_json,
+    bop_scene.net_mask_rows(...)): a row's bbox is its mask's tight box, a crop without a set pixel gives no row and
+    counts as "empty". "seg" is added as above; no other key changes."""
     device = torch.device(device) if device is not None else next(model.parameters()).device
-    if seg_json:
+    if seg_source not in ("render", "net"):
+        raise ValueError(f"seg_source must be 'render' or 'net', got {seg_source!r}")
+    net = seg_source == "net"
+    if net:
+        if not seg_json:
+            raise ValueError("seg_source='net' writes the network's masks to a file: it needs seg_json")
+        _require(dataset, "seg_source='net' writes BOP's scene / image ids: it needs a PoseDataset with layout='bop'",
+                 layout=True)
+    elif seg_json:
         _require(dataset, "seg_json renders the estimates' masks on a BOP tree: it needs a PoseDataset with layout='bop' "
                  "and meshes=True", layout=True, meshes=True)
     if match:
@@ -416,12 +456,19 @@ def test_epoch(model: KRRN, dataset: PoseDataset, bs: int = 64, device=None, opt
         rank = dist.get_rank(group) if dist.is_initialized() else 0
     if not 0 <= rank < world:
         raise ValueError(f"rank {rank} outside world {world}")
+    if net and world > 1:
+        raise ValueError("seg_source='net' runs on one rank: gathering the ranks' run lists is not built")
     sizes = [dataset.crop_size(i) for i in range(len(dataset))]
     mine = kd.bucket_shard(sizes, world, rank)
     want_poses = bool(bop_csv or match or seg_json)
-    local = EpochTables.of(eval_records(model, dataset, mine, bs, device, opt_pose=opt_pose, with_loss=criterion is not None,
-                                        pose_solver=pose_solver, refine=refine, bop=bool(bop), poses=want_poses,
-                                        select=select), bop, want_poses, select)
+    ret = eval_records(model, dataset, mine, bs, device, opt_pose=opt_pose, with_loss=criterion is not None,
+                       pose_solver=pose_solver, refine=refine, bop=bool(bop), poses=want_poses, select=select,
+                       net_masks=net)
+    net_runs = {}
+    if net:
+        net_runs = {crop: (runs, info) for crop, runs, info in ret[-1]}
+        ret = ret[:-1]
+    local = EpochTables.of(ret, bop, want_poses, select)
     shard_sizes = [sum(len(v) for v in kd.bucket_shard(sizes, world, r).values()) for r in range(world)]
     gather = lambda t: gather_epoch_records(t, shard_sizes, device, group) if world > 1 else t  # noqa: E731
     metric = Metric(dataset.sym_obj)
@@ -451,7 +498,13 @@ def test_epoch(model: KRRN, dataset: PoseDataset, bs: int = 64, device=None, opt
         rows = result_rows(allpose, dataset.tree.items, conf) if rank == 0 else None
         if bop_csv and rank == 0:
             write_results(bop_csv, rows)
-        if seg_json:
+        if net:
+            crops = [int(r[0]) for r in valid_by_crop(allpose)]  # result_rows' order
+            det, st = net_mask_rows(rows, [net_runs[c][0] for c in crops], [net_runs[c][1] for c in crops],
+                                    *dataset.frame_hw)
+            write_detections(seg_json, det)
+            out["seg"] = {"rows": len(det), "empty": st["empty"]}
+        elif seg_json:
             res = [None]
             if rank == 0:
                 det, st = write_result_masks(seg_json, dataset, rows, device)

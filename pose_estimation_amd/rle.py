@@ -1,6 +1,7 @@
 """COCO run-length encoded masks, the `segmentation` of BOP's detection files: the string codec, an encoder and a
-box's runs on the host, and the decoder and the encoder on the GPU (krrn_rle_decode_u8 / krrn_rle_encode_u8;
-include/krrn_hip.h states the definitions).
+box's runs on the host, and the decoder, the encoder and the paste of the mask head's crop windows into full-frame
+planes on the GPU (krrn_rle_decode_u8 / krrn_rle_encode_u8 / krrn_mask_paste_f32; include/krrn_hip.h states the
+definitions).
 
     runs = counts_from_string("61X13mN000`0")           # [6, 1, 40, 4, 5, 4, 5, 4, 21]; counts_to_string inverts it
     runs = encode(mask)                                 # host u8 / bool [H, W] -> run list
@@ -8,6 +9,7 @@ include/krrn_hip.h states the definitions).
     out = decode(counts, offs, H, W, device)            # {"mask": u8 [n, H, W] of 0 / 1, "info": int32 [n, 5]}
     enc = encode_gpu(planes)                            # GPU u8 / bool [n, H, W] -> {"counts", "n_runs", "info"}
     runs = encode_planes(planes)                        # the same as n run lists: [encode(m) for m in planes.cpu()]
+    res = paste_masks(pred["mask"], chan, rc, H, W)     # crop-window logits -> {"mask": u8 [B, H, W], "info"}
 
 Run semantics are COCO's: pixels are numbered column-major (p = x * H + y), the first run is zeros, the runs
 alternate, and a run may have length 0 (the first one when pixel (0, 0) is set). `info` = (pixel count, x, y, w, h):
@@ -180,7 +182,12 @@ def encode_planes(mask: torch.Tensor, max_runs: Optional[int] = None) -> List[Li
     """The run lists of the n planes of a GPU mask (as encode_gpu takes it), python ints: equal to [encode(m) for m
     in mask.cpu()], but only the runs cross the bus. One read-back of n_runs and counts; if a mask has more than
     max_runs runs, one more call with max_runs = n_runs.max()."""
-    res = encode_gpu(mask, max_runs)
+    return runs_of(mask, encode_gpu(mask, max_runs))
+
+
+def runs_of(mask: torch.Tensor, res: Dict[str, torch.Tensor]) -> List[List[int]]:
+    """encode_planes' read-back for a `res` = encode_gpu(mask, ...) queued earlier: the planes' run lists, with one more
+    encode_gpu call if a mask has more runs than res's slot holds (so `mask` must still hold the planes)."""
     nr = res["n_runs"].cpu().numpy()
     cap = int(res["counts"].shape[1])
     if len(nr) and int(nr.max()) > cap:
@@ -188,3 +195,62 @@ def encode_planes(mask: torch.Tensor, max_runs: Optional[int] = None) -> List[Li
     top = int(nr.max()) if len(nr) else 0
     counts = res["counts"][:, :top].cpu().numpy()        # the slots' zero tails past the longest list stay behind
     return [counts[i, :int(k)].tolist() for i, k in enumerate(nr)]
+
+
+def _int32_operand(v, shape, name: str, device) -> torch.Tensor:
+    """`v` as an int32 device tensor of `shape`: a host integer sequence is staged with h2d, a tensor must already
+    be int32, contiguous and on `device`."""
+    if isinstance(v, torch.Tensor):
+        if v.dtype != torch.int32 or tuple(v.shape) != shape or v.device != device or not v.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous int32 {list(shape)} tensor on {device} (or a host sequence)")
+        return v
+    a = np.asarray(v, dtype=np.int64).reshape(shape)     # raises ValueError for another size
+    if a.size and (a.min() < -0x80000000 or a.max() > 0x7fffffff):
+        raise ValueError(f"{name} must fit an int32")
+    if a.size == 0:
+        return torch.empty(shape, dtype=torch.int32, device=device)
+    return h2d(torch.from_numpy(a.astype(np.int32)), device)
+
+
+def paste_masks(logits: torch.Tensor, chan, rc, H: int, W: int, out: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+    """krrn_mask_paste_f32: the mask head's logits of B crops, a GPU f32 [B, C1, S, S] tensor, to full-frame planes
+    that encode_gpu takes. Crop b is the S x S window of its H x W frame with top left pixel rc[b] = (rmin, cmin);
+    chan[b] is the channel that sets a pixel where it wins the walk `best = 0; for c: if l[c] > l[best]: best = c`
+    (cls_id + 1 under the label convention multi_cls_mask = mask (cls + 1); 0 = any foreground channel; any other
+    value sets nothing). `logits` may be a view such as pred["mask"], a channel slice of a wider tensor: strides (>=
+    C1 S S, S S, S, 1) are passed through, no copy is made (the view is read when the call runs on the stream:
+    enqueue it before the next forward rewrites the plan's buffer). Another stride pattern, dtype or rank raises
+    ValueError, a CPU tensor RuntimeError, before anything is launched. chan [B] and rc [B, 2]: host integer sequences
+    (staged with h2d) or int32 device tensors. `out`: an optional contiguous u8 [B, H, W] GPU tensor at any byte
+    address (another dtype, shape or layout raises ValueError). Returns {"mask": u8 [B, H, W] of 0 / 1, "info": int32
+    [B, 5]} (info as decode's). Queued on the current stream; nothing is read back."""
+    if not isinstance(logits, torch.Tensor) or logits.dtype != torch.float32 or logits.dim() != 4 or \
+            logits.shape[2] != logits.shape[3]:
+        what = f"{logits.dtype} {tuple(logits.shape)}" if isinstance(logits, torch.Tensor) else type(logits).__name__
+        raise ValueError(f"logits must be an f32 [B, C1, S, S] tensor, got {what}")
+    B, C1, S = (int(v) for v in logits.shape[:3])
+    H, W = int(H), int(W)
+    if C1 < 1 or S < 1 or C1 * S * S > 0x7fffffff:
+        raise ValueError(f"logits [B, {C1}, {S}, {S}]: C1 and S must be positive and C1 * S * S fit an int32")
+    if H <= 0 or W <= 0 or H * W > 0x7fffffff:
+        raise ValueError(f"frame {H} x {W}: H and W must be positive and H * W fit an int32")
+    sb, sc, si, sj = (int(v) for v in logits.stride())   # the stride of an axis of one element is never used
+    if not ((S == 1 or (si, sj) == (S, 1)) and (C1 == 1 or sc == S * S) and (B <= 1 or sb >= C1 * S * S)):
+        raise ValueError(f"logits must have strides (>= C1 S S, S S, S, 1), got {tuple(logits.stride())}")
+    if out is not None and (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8
+                            or tuple(out.shape) != (B, H, W) or not out.is_contiguous()):
+        raise ValueError(f"out must be a contiguous u8 [{B}, {H}, {W}] tensor")
+    if not logits.is_cuda:
+        raise RuntimeError("rle.paste_masks runs on the HIP path only (a GPU tensor)")
+    dev = logits.device
+    if out is None:
+        out = torch.empty((B, H, W), dtype=torch.uint8, device=dev)
+    elif out.device != dev:
+        raise ValueError(f"out must be on the logits' device {dev}, got {out.device}")
+    cd, rd = _int32_operand(chan, (B,), "chan", dev), _int32_operand(rc, (B, 2), "rc", dev)
+    info = torch.empty((B, 5), dtype=torch.int32, device=dev)
+    if B == 0:
+        return {"mask": out, "info": info}
+    _lib.call("krrn_mask_paste_f32", ptr(logits), sb if B > 1 else C1 * S * S, C1, S, ptr(cd), ptr(rd), B, H, W,
+              ptr(out), ptr(info), stream_ptr(dev))
+    return {"mask": out, "info": info}
