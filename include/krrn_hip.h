@@ -720,6 +720,82 @@ int krrn_bop_match_f64(const double* score, int Etot, const double* err, long lo
                        const int* n_top, int G, int GTtot, int max_est, int max_gt, int* match, int* tp,
                        void* stream);
 
+/* IoU of P pairs of run-length encoded masks, from the run lists alone: no plane is decoded and no H or W is
+ * needed (a mask is its runs). counts int32 [n_counts]: the run lengths of the n masks, concatenated; offs int32
+ * [n + 1] (device memory): mask i owns counts[offs[i] .. offs[i + 1]), as krrn_rle_decode_u8 takes them; pair int32
+ * [P][2] = (detection mask, ground-truth mask); crowd u8 [P] (optional, NULL = no crowd). For mask m with runs c_0 ..
+ * c_{n-1} (a negative count counts as 0):
+ *   e_k   = the inclusive prefix sum of the runs, saturated at INT32_MAX (as the decoder saturates at H W); e_{-1} = 0
+ *   the set runs are the odd k, covering the pixels [e_{k-1}, e_k); area(m) = the sum of the odd runs' e_k - e_{k-1}
+ *   s_k   = the sum of the odd runs with index <= k, s_{-1} = 0
+ *   F_m(p) = the number of set pixels of m with index < p: with j = #{k : e_k <= p}, F_m(p) = s_{n-1} for j >= n,
+ *            else s_{j-1} + (j odd ? p - e_{j-1} : 0)
+ *   inter(a, b) = sum over a's odd k of F_b(e^a_k) - F_b(e^a_{k-1});   union = area(a) + area(b) - inter
+ *   iou = inter / union in f64: one correctly rounded division of two integers; where crowd[p] is set, iou = inter /
+ *   area(a) (a = the detection); iou = 0.0 where the denominator is 0.
+ * Unlike the decoder, a pixel at or past the runs' total is never set. Outputs, every element written by the call:
+ * inter int32 [P], iou f64 [P], area int32 [n]. ws: int32 workspace of krrn_rle_iou_ws(n_counts) elements (e, then
+ * s). A pair naming a mask outside [0, n) gives inter = 0, iou = 0.0; a range that is negative, reversed or past
+ * min(offs[n], n_counts) is an empty mask (area 0, so inter = 0 and iou = 0.0). Nothing outside the buffers is read
+ * or written. Two launches: one block per mask scans its runs into ws; then one wave per pair, whose lanes stride
+ * over the set runs of the list with fewer runs and search the other list's e twice each (intersection is symmetric,
+ * so the choice changes only the work), with a wave-wide integer add; a pair whose set spans [e_0, last odd end) do
+ * not overlap stores 0 without a search. Integers only, no atomics, no read-back (the call can be captured in a
+ * graph): a pair's result does not depend on the batch, bit for bit. Host checks, before any HIP call: null counts /
+ * offs / pair / ws / inter / iou / area (n_ints for _ws) KRRN_EARG; n < 0, P < 0 or n_counts < 0 KRRN_ESHAPE; P == 0
+ * and n == 0 returns 0 and launches nothing. */
+int krrn_rle_iou_ws(int n_counts, long long* n_ints);
+int krrn_rle_iou_f64(const int* counts, int n_counts, const int* offs, int n, const int* pair,
+                     const unsigned char* crowd, int P, int* ws, int* inter, double* iou, int* area, void* stream);
+
+/* IoU of P pairs of [x, y, w, h] boxes as plain rectangles. box f64 [n][4]; pair int32 [P][2] = (detection,
+ * ground truth) and crowd u8 [P] (optional) as above. In f64 with every operation rounded on its own (no FMA
+ * contraction), where max(u, v) = (v > u ? v : u) and min(u, v) = (v < u ? v : u):
+ *   iw = max(0, min(ax + aw, bx + bw) - max(ax, bx));  ih likewise in y;  inter = iw ih
+ *   area(m) = max(w, 0) max(h, 0);  den = area(a) + area(b) - inter, or area(a) where crowd[p] is set
+ *   iou = den > 0 ? inter / den : 0.0
+ * Outputs, every element written by the call: iou f64 [P], area f64 [n]. A pair naming a box outside [0, n) gives
+ * 0.0. One thread per pair; no atomics, no read-back. Host checks, before any HIP call: null box / pair / iou / area
+ * KRRN_EARG; n < 0 or P < 0 KRRN_ESHAPE; P == 0 and n == 0 returns 0 and launches nothing. */
+int krrn_box_iou_f64(const double* box, int n, const int* pair, const unsigned char* crowd, int P, double* iou,
+                     double* area, void* stream);
+
+/* COCO's per-image matching (pycocotools' published COCOeval.evaluateImg) for G groups at once; a group is one
+ * (scene, image, category). score f64 [Dtot] the detections' scores; det_range int32 [G][2] = (first detection,
+ * n_det) into score / det_area; gt_range int32 [G][2] = (first ground truth, n_gt) into gt_area / gt_flags; pair_off
+ * int32 [G] = the group's first element in iou f64 [Ptot]: a group owns n_det n_gt elements, detection-major, iou(d,
+ * j) = iou[pair_off + d n_gt + j]. det_area f64 [Dtot], gt_area f64 [GTtot]; gt_flags int32 [GTtot]: bit 0 =
+ * iscrowd, bit 1 = ignore; area_rng f64 [A][2] = (lo, hi), 1 <= A <= 8; iou_thr f64 [T], 1 <= T <= 16; max_det <=
+ * 128 = COCO's maxDets. Each cell (g, a, t) is matched on its own:
+ *   ig[j] = (gt_flags[j] != 0) or gt_area[j] < lo_a or gt_area[j] > hi_a (the bounds are inclusive)
+ *   the ground truths are walked in the order: the j with ig[j] == 0 in index order, then the others in index order
+ *   the detections are ordered by score descending, ties to the lower index, a NaN score as -inf; only the first
+ *   max_det take part. For each detection d in that order: best = min(iou_thr[t], 1 - 1e-10), m = -1; for each j in
+ *   the walk: skip j if it is already matched and not crowd; stop if m >= 0, ig[m] == 0 and ig[j] == 1; skip j if
+ *   iou(d, j) < best or iou(d, j) is NaN; otherwise best = iou(d, j), m = j (an equal IoU moves to the later ground
+ *   truth). If m >= 0: dt_match = m, dt_ig = ig[m], and m is marked matched. An unmatched detection has dt_ig =
+ *   (det_area[d] < lo_a or det_area[d] > hi_a).
+ * Outputs, every element of an owned detection or ground truth written by the call: dt_match int32 [Dtot][A][T] =
+ * the global ground-truth index (into gt_area), or -1; dt_ig u8 [Dtot][A][T]; gt_ig u8 [GTtot][A] = ig; rank int32
+ * [Dtot] = the detection's position in its group's order, or -1 at or past max_det (such a detection has dt_match =
+ * -1, dt_ig = 1 in every cell). The groups' ranges must not overlap; an element that no group owns keeps what the
+ * buffer held. Limits: n_det <= lim_det <= 128 and n_gt <= lim_gt <= 128, which the caller states because the ranges
+ * are device memory. The kernel honours them: a group with n_det > lim_det, n_gt > lim_gt, a negative range, a range
+ * past Dtot / GTtot or pair elements past Ptot is matched as an empty group: the detections its range owns inside
+ * [0, Dtot) get rank -1, dt_match -1 and dt_ig 1, the ground truths it owns inside [0, GTtot) their gt_ig; nothing
+ * outside the buffers is read or written. Comparisons only, no atomics, one block per group: the result is
+ * bit-reproducible and a group's outputs do not depend on the rest of the batch. Written from the published
+ * definition; not checked against pycocotools' own output. Host checks, before any HIP call: null det_range /
+ * gt_range / pair_off / area_rng / iou_thr, null score / det_area / dt_match / dt_ig / rank with Dtot > 0, iou with
+ * Ptot > 0, gt_area / gt_flags / gt_ig with GTtot > 0 KRRN_EARG; G, Dtot, GTtot or Ptot < 0, Ptot > INT32_MAX, A
+ * outside 1..8, T outside 1..16, max_det, lim_det or lim_gt outside 0..128 KRRN_ESHAPE; G == 0 returns 0 and launches
+ * nothing. */
+int krrn_coco_match_f64(const double* score, int Dtot, const int* det_range, const int* gt_range, const int* pair_off,
+                        const double* iou, long long Ptot, const double* det_area, const double* gt_area,
+                        const int* gt_flags, int GTtot, const double* area_rng, int A, const double* iou_thr, int T,
+                        int max_det, int lim_det, int lim_gt, int G, int* dt_match, unsigned char* dt_ig,
+                        unsigned char* gt_ig, int* rank, void* stream);
+
 /* Pose verification by render-and-compare: C candidate poses per crop scored against the observed depth frame
  * and the detector's mask, without a ground-truth pose, and the best one selected. verts / faces / face_range /
  * K4 / depth / frame / depth_scale as krrn_bop_vsd_f32; R f64 [B][C][9], t f64 [B][C][3], 1 <= C <= 8; mask u8

@@ -42,7 +42,14 @@ the rows in the detection format above: a segmentation result file, which BopTre
 net_mask_rows(rows, runs, info, H, W) makes the same rows from masks that are already run lists: the network's own
 segmentation, which evaluate.test_epoch(seg_json=..., seg_source="net") pastes and encodes per batch.
 
-Out of scope: binary PLY."""
+Scoring a detection or segmentation result file. eval_coco(gt, rows, device, iou_type="segm" | "bbox") is the
+counterpart of the toolkit's eval_bop22_coco: COCO's average precision of the rows against scene_gt_coco.json, with the
+mask IoUs taken from the run lists on the GPU (rle.iou) and the per-image matching there too (coco.match).
+
+    write_gt_coco("/data/mine", "test", device)
+    res = eval_coco(("/data/mine", "test"), read_detections("krrn_mine-test_seg.json"), "cuda:0")   # AP, AP50, AR100, ...
+
+Out of scope: binary PLY, polygon segmentations, keypoints."""
 from __future__ import annotations
 
 import json
@@ -790,4 +797,141 @@ def eval_results(dataset, rows, device, chunk_images: int = 32, delta: float = b
     out: Dict[str, object] = bop.recalls_from_tp(tp[:len(objs)].sum(0), len(tree.instances), sum(take.values()))
     out["per_obj"] = {o: bop.recalls_from_tp(tp[a], n_obj[o], c_obj[o]) for a, o in enumerate(objs)}
     out["ignored"], out["matches"] = ignored, matches
+    return out
+
+
+def _coco_gt(gt) -> Dict[int, Dict[str, object]]:
+    """eval_coco's ground truth as {scene: coco dict}: read from the scenes' scene_gt_coco.json for a (root, split)
+    pair, passed through for the dict write_gt_coco returns."""
+    if isinstance(gt, dict):
+        return {int(sc): c for sc, c in gt.items()}
+    if not (isinstance(gt, (tuple, list)) and len(gt) == 2):
+        raise ValueError("gt must be a (root, split) pair or the {scene: coco dict} that write_gt_coco returns")
+    root, split = str(gt[0]), str(gt[1])
+    out = {}
+    for sc in scene_ids(root, split):
+        path = os.path.join(_scene_dir(root, split, sc), "scene_gt_coco.json")
+        if not os.path.exists(path):
+            raise FileNotFoundError(f"{path} is missing: write_gt_coco(root, split, device) writes it")
+        with open(path) as f:
+            out[sc] = json.load(f)
+    return out
+
+
+def eval_coco(gt, rows, device, iou_type: str = "segm", use_ignore: bool = True, chunk_images: int = 32
+              ) -> Dict[str, object]:
+    """Score a detection or segmentation result file with COCO's average precision, the metric of BOP's 2D
+    detection and 2D segmentation tasks (the toolkit's eval_bop22_coco, which takes it from pycocotools). `gt`: a
+    (root, split) pair whose scenes' scene_gt_coco.json are read (FileNotFoundError names write_gt_coco when one is
+    missing), or the {scene: coco dict} that write_gt_coco returns. `rows`: detection rows in _check_rows' normal form
+    (read_detections gives them). iou_type "segm" compares masks (every row must carry a `segmentation` whose `size`
+    equals its image's [height, width]: otherwise ValueError with the row's index), "bbox" compares `bbox`.
+
+    A group is one (scene_id, image_id, category_id), so image ids may repeat across scenes; the groups are the
+    triples that hold a ground truth or a row, in sorted order. A row whose scene, image or category `gt` does not
+    hold is counted in "ignored". A ground truth is ignored where it is a crowd, where its `ignore` is set
+    (use_ignore=False drops this clause, which is stock pycocotools; write_gt_coco sets it for visib_fract <
+    min_visib), or where its `area` lies outside the area range. A group with more than coco.MATCH_MAX detections
+    keeps its MATCH_MAX best-scored ones (the kernel's order), as eval_results does; one with more ground truths than
+    that raises ValueError. Per chunk of at most `chunk_images` images: one rle.iou (or rle.box_iou) call over every
+    group's n_det x n_gt pairs, whose run lists never become planes, and one coco.match call at coco.IOU_THRS x
+    coco.AREA_RNG with maxDet 100. A detection's area is its mask's pixel count (its box's w h for "bbox"), a ground
+    truth's its annotation's `area`. Everything is read back once, at the end, and coco.accumulate / coco.summarize
+    fold it on the host.
+
+    Returns AP, AP50, AP75, AP_small, AP_medium, AP_large, AR1, AR10, AR100 (-1 where nothing defines one), "per_obj":
+    {category: {"AP", "AR100"}}, "count" = the rows that took part, "targets" = the ground-truth annotations,
+    "ignored". Written from the published definitions; not checked against pycocotools' own output, which is not a
+    dependency."""
+    from . import coco as kc
+    if iou_type not in ("segm", "bbox"):
+        raise ValueError(f"iou_type must be 'segm' or 'bbox', got {iou_type!r}")
+    device = torch.device(device)
+    segm = iou_type == "segm"
+    gts = _coco_gt(gt)
+    size: Dict[Tuple[int, int], List[int]] = {}
+    cats = sorted({int(c["id"]) for coco in gts.values() for c in coco["categories"]})
+    gt_by: Dict[Tuple[int, int, int], List[Dict[str, object]]] = {}
+    for sc in sorted(gts):
+        for im in gts[sc]["images"]:
+            size[(sc, int(im["id"]))] = [int(im["height"]), int(im["width"])]
+        for a in gts[sc]["annotations"]:
+            gt_by.setdefault((sc, int(a["image_id"]), int(a["category_id"])), []).append(a)
+    for key, anns in gt_by.items():
+        if len(anns) > kc.MATCH_MAX:
+            raise ValueError(f"group {key} has {len(anns)} ground truths > {kc.MATCH_MAX}")
+    det_by: Dict[Tuple[int, int, int], List[int]] = {}
+    ignored = 0
+    for r, row in enumerate(rows):
+        key = (int(row["scene_id"]), int(row["image_id"]), int(row["category_id"]))
+        seg = row.get("segmentation")
+        if segm and seg is None:
+            raise ValueError(f"row {r} has no segmentation: iou_type='segm' compares masks")
+        if key[:2] not in size or key[2] not in cats:
+            ignored += 1
+            continue
+        if segm and [int(v) for v in seg["size"]] != size[key[:2]]:
+            raise ValueError(f"row {r}: segmentation.size {seg['size']} is not its image's {size[key[:2]]}")
+        det_by.setdefault(key, []).append(r)
+    for key, rs in det_by.items():
+        if len(rs) > kc.MATCH_MAX:
+            order = _rank([float(rows[r]["score"]) for r in rs])[:kc.MATCH_MAX]
+            det_by[key] = [rs[a] for a in sorted(order)]
+    keys = sorted(set(gt_by) | set(det_by))
+    images = sorted({k[:2] for k in keys})
+    step = max(1, int(chunk_images))
+    runs_of = lambda seg: rle.counts_from_string(seg["counts"]) if isinstance(seg["counts"], str) else seg["counts"]  # noqa: E731
+    cat_of, d_rng, g_rng, scores, pending = [], [], [], [], []
+    n_det = n_gt = 0
+    for lo in range(0, len(images), step):
+        part = set(images[lo:lo + step])
+        ck = [k for k in keys if k[:2] in part]
+        d_items = [r for k in ck for r in det_by.get(k, [])]
+        g_items = [a for k in ck for a in gt_by.get(k, [])]
+        D = len(d_items)
+        pair, crowd, dr, gr, po = [], [], [], [], []
+        d0 = g0 = 0
+        for k in ck:
+            nd, ng = len(det_by.get(k, [])), len(gt_by.get(k, []))
+            dr.append((d0, nd)), gr.append((g0, ng)), po.append(len(pair))
+            for d in range(d0, d0 + nd):
+                for j in range(g0, g0 + ng):
+                    pair.append((d, D + j))
+                    crowd.append(int(g_items[j].get("iscrowd", 0)) != 0)
+            d0, g0 = d0 + nd, g0 + ng
+            cat_of.append(cats.index(k[2]))
+            d_rng.append((n_det + dr[-1][0], nd)), g_rng.append((n_gt + gr[-1][0], ng))
+        if segm:
+            lists = [rows[r]["segmentation"]["counts"] for r in d_items] + [runs_of(a["segmentation"]) for a in g_items]
+            offs = np.concatenate([[0], np.cumsum([len(c) for c in lists])]).astype(np.int64)
+            res = rle.iou(np.concatenate([np.asarray(c, np.int64) for c in lists]) if lists else np.zeros(0, np.int64),
+                          offs, pair, crowd, device)
+            det_area = res["area"][:D].to(torch.float64)
+        else:
+            boxes = [rows[r]["bbox"] for r in d_items] + [a["bbox"] for a in g_items]
+            res = rle.box_iou(np.asarray(boxes, np.float64).reshape(-1, 4), pair, crowd, device)
+            det_area = res["area"][:D]
+        flags = [(1 if int(a.get("iscrowd", 0)) else 0) | (2 if use_ignore and a.get("ignore", False) else 0)
+                 for a in g_items]
+        sc = np.array([float(rows[r]["score"]) for r in d_items], np.float64)
+        m = kc.match(sc, np.array(dr, np.int32).reshape(-1, 2), np.array(gr, np.int32).reshape(-1, 2),
+                     np.array(po, np.int32), res["iou"], det_area, np.array([float(a["area"]) for a in g_items], np.float64),
+                     np.array(flags, np.int32), device=device)
+        scores.append(sc)
+        pending.append(m)
+        n_det, n_gt = n_det + len(d_items), n_gt + len(g_items)
+    A, T = len(kc.AREA_RNG), len(kc.IOU_THRS)
+    if pending:                                          # the one read-back: every chunk's outputs as one int32 tensor
+        flat = torch.cat([t.reshape(-1).to(torch.int32) for k in ("rank", "dt_match", "dt_ig", "gt_ig") for t in
+                          (m[k] for m in pending)]).cpu().numpy()
+    else:
+        flat = np.zeros(0, np.int32)
+    cut = np.cumsum([0, n_det, n_det * A * T, n_det * A * T, n_gt * A])
+    rank, dt_match = flat[cut[0]:cut[1]], flat[cut[1]:cut[2]].reshape(n_det, A, T).copy()
+    dt_ig, gt_ig = flat[cut[2]:cut[3]].reshape(n_det, A, T), flat[cut[3]:cut[4]].reshape(n_gt, A)
+    # dt_match indexes the chunk's ground truths: nothing below needs more than matched or not
+    acc = kc.accumulate(cat_of, np.array(d_rng, np.int64).reshape(-1, 2), np.array(g_rng, np.int64).reshape(-1, 2),
+                        np.concatenate(scores) if scores else np.zeros(0), rank, dt_match, dt_ig, gt_ig, len(cats))
+    out = kc.summarize(acc, cats=cats)
+    out["count"], out["targets"], out["ignored"] = n_det, n_gt, ignored
     return out

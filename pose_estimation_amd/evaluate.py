@@ -34,7 +34,8 @@ import torch.distributed as dist
 from . import distributed as kd
 from .bop import BOP_REC, FRAME_W, TAUS, bop_errors, fold_bop, valid_by_crop
 from . import rle
-from .bop_scene import _require, eval_results, net_mask_rows, write_detections, write_result_masks, write_results
+from .bop_scene import (_require, eval_coco, eval_results, net_mask_rows, write_detections, write_result_masks,
+                        write_results)
 from .dataset import PoseDataset
 from .krrn import KRRN
 from .loss import map_losses
@@ -385,7 +386,8 @@ def test_epoch(model: KRRN, dataset: PoseDataset, bs: int = 64, device=None, opt
                criterion=None, world: Optional[int] = None, rank: Optional[int] = None,
                group=None, pose_solver: str = "pnp", refine: Optional[str] = None,
                bop: bool = False, bop_csv: Optional[str] = None, select: Optional[str] = None,
-               match: bool = False, seg_json: Optional[str] = None, seg_source: str = "render") -> Dict[str, object]:
+               match: bool = False, seg_json: Optional[str] = None, seg_source: str = "render",
+               coco: bool = False) -> Dict[str, object]:
     """Trainer.test_epoch over `dataset`. world/rank default to the initialised process group
     (1/0 without one). `criterion` enables the per-crop map-loss terms (dis_xyz / dis_mask /
     dis_normal) when the batches carry GT maps, i.e. for a PoseDataset built with gt_maps=True (a
@@ -427,11 +429,17 @@ def test_epoch(model: KRRN, dataset: PoseDataset, bs: int = 64, device=None, opt
     pixels (channel cls_id + 1 wins) into a full-frame plane and encodes it on the GPU; rank 0 builds the result rows
     exactly as `bop_csv` writes them, pairs them with the runs by crop and writes write_detections(seg_json,
     bop_scene.net_mask_rows(...)): a row's bbox is its mask's tight box, a crop without a set pixel gives no row and
-    counts as "empty". "seg" is added as above; no other key changes."""
+    counts as "empty". "seg" is added as above; no other key changes.
+    `coco` (off by default: nothing changes; needs seg_json, else ValueError, and the tree's scene_gt_coco.json, which
+    bop_scene.write_gt_coco writes) scores the file just written with COCO's average precision: rank 0 adds one key,
+    "coco" = bop_scene.eval_coco((root, split), the rows written, device, "segm"); no other key changes. It runs where
+    seg_json runs: the ranks' run lists are not gathered."""
     device = torch.device(device) if device is not None else next(model.parameters()).device
     if seg_source not in ("render", "net"):
         raise ValueError(f"seg_source must be 'render' or 'net', got {seg_source!r}")
     net = seg_source == "net"
+    if coco and not seg_json:
+        raise ValueError("coco=True scores the segmentation file this epoch writes: it needs seg_json")
     if net:
         if not seg_json:
             raise ValueError("seg_source='net' writes the network's masks to a file: it needs seg_json")
@@ -504,14 +512,19 @@ def test_epoch(model: KRRN, dataset: PoseDataset, bs: int = 64, device=None, opt
                                     *dataset.frame_hw)
             write_detections(seg_json, det)
             out["seg"] = {"rows": len(det), "empty": st["empty"]}
+            if coco:
+                out["coco"] = eval_coco((dataset.tree.root, dataset.tree.split), det, device, "segm")
         elif seg_json:
-            res = [None]
+            res = [None, None]
             if rank == 0:
                 det, st = write_result_masks(seg_json, dataset, rows, device)
-                res = [{"rows": len(det), "empty": st["empty"]}]
+                res = [{"rows": len(det), "empty": st["empty"]},
+                       eval_coco((dataset.tree.root, dataset.tree.split), det, device, "segm") if coco else None]
             if world > 1:
                 dist.broadcast_object_list(res, src=0, group=group)
             out["seg"] = res[0]
+            if coco:
+                out["coco"] = res[1]
         if match:  # the protocol's recalls over the rows, in place of the 1 : 1 fold above
             res = [eval_results(dataset, rows, device)] if rank == 0 else [None]
             if world > 1:

@@ -1,7 +1,7 @@
 """COCO run-length encoded masks, the `segmentation` of BOP's detection files: the string codec, an encoder and a
 box's runs on the host, and the decoder, the encoder and the paste of the mask head's crop windows into full-frame
 planes on the GPU (krrn_rle_decode_u8 / krrn_rle_encode_u8 / krrn_mask_paste_f32; include/krrn_hip.h states the
-definitions).
+definitions), and the IoU of pairs of run lists or boxes on the GPU (krrn_rle_iou_f64 / krrn_box_iou_f64).
 
     runs = counts_from_string("61X13mN000`0")           # [6, 1, 40, 4, 5, 4, 5, 4, 21]; counts_to_string inverts it
     runs = encode(mask)                                 # host u8 / bool [H, W] -> run list
@@ -10,6 +10,8 @@ definitions).
     enc = encode_gpu(planes)                            # GPU u8 / bool [n, H, W] -> {"counts", "n_runs", "info"}
     runs = encode_planes(planes)                        # the same as n run lists: [encode(m) for m in planes.cpu()]
     res = paste_masks(pred["mask"], chan, rc, H, W)     # crop-window logits -> {"mask": u8 [B, H, W], "info"}
+    res = iou(counts, offs, pair, crowd, device)        # run-list pairs -> {"inter", "iou" f64 [P], "area" [n]}
+    res = box_iou(box, pair, crowd, device)             # [x, y, w, h] pairs -> {"iou" f64 [P], "area" f64 [n]}
 
 Run semantics are COCO's: pixels are numbered column-major (p = x * H + y), the first run is zeros, the runs
 alternate, and a run may have length 0 (the first one when pixel (0, 0) is set). `info` = (pixel count, x, y, w, h):
@@ -139,6 +141,107 @@ def decode(counts, offs, H: int, W: int, device, out: Optional[torch.Tensor] = N
     ends = torch.empty((len(c64),), dtype=torch.int32, device=device)
     _lib.call("krrn_rle_decode_u8", ptr(cd), ptr(od), n, H, W, ptr(ends), ptr(out), ptr(info), stream_ptr(device))
     return {"mask": out, "info": info}
+
+
+def _pairs(pair, crowd):
+    """pair as int64 [P, 2] and crowd as u8 [P] or None (host arrays); ValueError for another shape."""
+    pr = np.asarray(pair, dtype=np.int64).reshape(-1, 2)
+    if pr.size and (pr.min() < -0x80000000 or pr.max() > 0x7fffffff):
+        raise ValueError("pair must fit an int32")
+    cr = None
+    if crowd is not None:
+        cr = (np.asarray(crowd).reshape(-1) != 0).astype(np.uint8)
+        if len(cr) != len(pr):
+            raise ValueError(f"crowd must hold one flag per pair: {len(cr)} flags for {len(pr)} pairs")
+    return pr, cr
+
+
+def iou(counts, offs, pair, crowd=None, device=None) -> Dict[str, torch.Tensor]:
+    """krrn_rle_iou_f64 for P pairs of n masks: the intersection, the areas and the IoU from the run lists alone (no
+    plane is decoded, and no H or W is needed). `counts` / `offs` as decode takes them, `pair` [P, 2] = (detection
+    mask, ground-truth mask), `crowd` [P] (optional): where set, the pair's IoU is inter / area(detection), COCO's
+    crowd form. Host integer arrays. Refused before anything is launched, with a ValueError naming the mask or the
+    pair: a mask with no run, a negative count, runs whose sum does not fit an int32, non-increasing offs, and a
+    pair whose two masks do not have the same total (masks of different frames). A pair that names a mask outside
+    [0, n) is passed on and gives 0, as the header states. Returns {"inter": int32 [P], "iou": f64 [P], "area": int32
+    [n]} on the device. Queued on the current stream; nothing is read back. The definition is written from COCO's
+    published one and not checked against pycocotools' own output (it is not a dependency)."""
+    c64 = np.asarray(counts, dtype=np.int64).reshape(-1)
+    o64 = np.asarray(offs, dtype=np.int64).reshape(-1)
+    if len(o64) < 1:
+        raise ValueError("offs must be [n + 1]")
+    n = len(o64) - 1
+    total = np.zeros(n, np.int64)
+    for i in range(n):
+        a, b = int(o64[i]), int(o64[i + 1])
+        if a < 0 or b > len(c64):
+            raise ValueError(f"mask {i}: its runs {a} .. {b} lie outside the {len(c64)} counts")
+        if b < a:
+            raise ValueError(f"mask {i}: offs is not increasing ({a} then {b})")
+        if b == a:
+            raise ValueError(f"mask {i} has no run")
+        c = c64[a:b]
+        if (c < 0).any():
+            raise ValueError(f"mask {i} has a negative count")
+        total[i] = int(c.sum())
+        if total[i] > 0x7fffffff:
+            raise ValueError(f"mask {i}: its runs sum to {int(total[i])}, which does not fit an int32")
+    pr, cr = _pairs(pair, crowd)
+    inside = ((pr >= 0) & (pr < n)).all(1)
+    odd = np.flatnonzero(inside & (total[np.where(inside, pr[:, 0], 0)] != total[np.where(inside, pr[:, 1], 0)])) if n else []
+    if len(odd):
+        p, (a, b) = int(odd[0]), pr[odd[0]].tolist()
+        raise ValueError(f"pair {p}: mask {a} has {int(total[a])} pixels and mask {b} {int(total[b])}")
+    if device is None or torch.device(device).type != "cuda":
+        raise RuntimeError("rle.iou runs on the HIP path only (a GPU device)")
+    device = torch.device(device)
+    P = len(pr)
+    out = {"inter": torch.empty((P,), dtype=torch.int32, device=device),
+           "iou": torch.empty((P,), dtype=torch.float64, device=device),
+           "area": torch.empty((n,), dtype=torch.int32, device=device)}
+    if P == 0 and n == 0:
+        return out
+    dummy = torch.empty((1,), dtype=torch.float64, device=device)  # a non-null address for an empty operand
+    at = lambda t: ptr(t) if t.numel() else ptr(dummy)  # noqa: E731
+    cd = h2d(torch.from_numpy(c64.astype(np.int32)), device) if len(c64) else dummy
+    od = h2d(torch.from_numpy(o64.astype(np.int32)), device)
+    pd = h2d(torch.from_numpy(pr.astype(np.int32)), device) if P else dummy
+    kd = h2d(torch.from_numpy(cr), device) if cr is not None and P else None
+    n_ints = ctypes.c_longlong(0)
+    _lib.call("krrn_rle_iou_ws", len(c64), ctypes.byref(n_ints))
+    ws = torch.empty((max(1, n_ints.value),), dtype=torch.int32, device=device)
+    _lib.call("krrn_rle_iou_f64", ptr(cd), len(c64), ptr(od), n, ptr(pd), ptr(kd), P, ptr(ws), at(out["inter"]),
+              at(out["iou"]), at(out["area"]), stream_ptr(device))
+    return out
+
+
+def box_iou(box, pair, crowd=None, device=None) -> Dict[str, torch.Tensor]:
+    """krrn_box_iou_f64 for P pairs of n boxes: `box` [n, 4] = [x, y, w, h] (host numbers), `pair` / `crowd` as iou
+    takes them. bop_scene._box_iou's arithmetic in f64, bit for bit; the crowd form divides by the detection's area.
+    Returns {"iou": f64 [P], "area": f64 [n] = max(w, 0) max(h, 0)} on the device. Queued on the current stream;
+    nothing is read back. ValueError for a box array that is not [n, 4]."""
+    b64 = np.asarray(box, dtype=np.float64)
+    if b64.size == 0:
+        b64 = b64.reshape(0, 4)
+    if b64.ndim != 2 or b64.shape[1] != 4:
+        raise ValueError(f"box must be [n, 4] = [x, y, w, h], got {b64.shape}")
+    n = len(b64)
+    pr, cr = _pairs(pair, crowd)
+    if device is None or torch.device(device).type != "cuda":
+        raise RuntimeError("rle.box_iou runs on the HIP path only (a GPU device)")
+    device = torch.device(device)
+    P = len(pr)
+    out = {"iou": torch.empty((P,), dtype=torch.float64, device=device),
+           "area": torch.empty((n,), dtype=torch.float64, device=device)}
+    if P == 0 and n == 0:
+        return out
+    dummy = torch.empty((1,), dtype=torch.float64, device=device)  # a non-null address for an empty operand
+    at = lambda t: ptr(t) if t.numel() else ptr(dummy)  # noqa: E731
+    bd = h2d(torch.from_numpy(np.ascontiguousarray(b64)), device) if n else dummy
+    pd = h2d(torch.from_numpy(pr.astype(np.int32)), device) if P else dummy
+    kd = h2d(torch.from_numpy(cr), device) if cr is not None and P else None
+    _lib.call("krrn_box_iou_f64", ptr(bd), n, ptr(pd), ptr(kd), P, at(out["iou"]), at(out["area"]), stream_ptr(device))
+    return out
 
 
 def encode_gpu(mask: torch.Tensor, max_runs: Optional[int] = None) -> Dict[str, torch.Tensor]:
