@@ -181,7 +181,7 @@ def mssd_mspd(verts: torch.Tensor, vert_range: torch.Tensor, R_est: torch.Tensor
     return out
 
 
-MATCH_MAX = 128                                         # kMatchMax of csrc/bop_match.hip: estimates / instances per group
+MATCH_MAX = 128                                         # kMatchMax of csrc/krrn_match.h: rows per side of a group (coco's too)
 MAX_NT = 16                                             # kMatchMaxNT: thresholds of correctness per error function
 
 

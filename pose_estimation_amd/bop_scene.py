@@ -54,6 +54,7 @@ from __future__ import annotations
 
 import json
 import os
+from itertools import accumulate
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -389,6 +390,13 @@ def write_detections(path, rows) -> None:
         json.dump(_check_rows(rows, "rows"), f)
 
 
+def _mask_row(sc, im, obj, score, bbox, counts, size, time=None) -> Dict[str, object]:
+    """One detection row with a mask in _check_rows' normal form; without `time` the key is left out."""
+    return {"scene_id": int(sc), "image_id": int(im), "category_id": int(obj), "score": float(score),
+            "bbox": [float(v) for v in bbox], "segmentation": {"counts": counts, "size": [int(size[0]), int(size[1])]},
+            **({} if time is None else {"time": float(time)})}
+
+
 def gt_detections(tree: "BopTree") -> List[Dict[str, object]]:
     """Oracle detections of a tree built without detections: one row per item, from its bbox_visib and its
     mask_visib PNG, with score 1.0. A dataset built on them equals the tree's own PNG mode (an upper-bound run)."""
@@ -397,9 +405,7 @@ def gt_detections(tree: "BopTree") -> List[Dict[str, object]]:
     rows = []
     for i, it in enumerate(tree.items):
         m = tree.read_mask(i)
-        sc, im, obj = _key(it)
-        rows.append({"scene_id": sc, "image_id": im, "category_id": obj, "score": 1.0, "bbox": [float(v) for v in it["bbox"]],
-                     "segmentation": {"counts": rle.encode(m), "size": [int(m.shape[0]), int(m.shape[1])]}})
+        rows.append(_mask_row(*_key(it), 1.0, it["bbox"], rle.encode(m), m.shape))
     return rows
 
 
@@ -598,11 +604,10 @@ def result_masks(dataset, rows, device, chunk_images: int = 32, delta: float = b
 
     Per chunk of at most `chunk_images` distinct images, as in eval_results, the depth frames are read once; the
     chunk's estimates go through bop.visibility under their own poses, 64 at a time, and rle.encode_planes of
-    mask_visib brings back the runs alone. Each estimate with a visible pixel gives {scene_id, image_id, category_id,
-    score = the row's, bbox = the estimate's bbox_visib, segmentation = {"counts": run list, "size": [H, W]}, time =
-    the row's}, in the order of `rows`. Returns (rows, {"empty": the estimates without a visible pixel (behind the
-    camera, outside the frame, hidden), which give no row, "ignored": the rows whose image or object the tree does
-    not hold})."""
+    mask_visib brings back the runs alone. Each estimate with a visible pixel gives one _mask_row (the row's ids, score
+    and time, bbox = the estimate's bbox_visib, the run list), in the order of `rows`. Returns (rows, {"empty": the
+    estimates without a visible pixel (behind the camera, outside the frame, hidden), which give no row, "ignored":
+    the rows whose image or object the tree does not hold})."""
     device = torch.device(device)
     tree = dataset.tree
     _require(dataset, "result_masks needs a PoseDataset with layout='bop' and meshes=True", layout=True, meshes=True)
@@ -627,9 +632,8 @@ def result_masks(dataset, rows, device, chunk_images: int = 32, delta: float = b
                     empty += 1
                     continue
                 row = rows[r]
-                out[r] = {"scene_id": int(row["scene_id"]), "image_id": int(row["im_id"]), "category_id": int(row["obj_id"]),
-                          "score": float(row["score"]), "bbox": [float(v) for v in q[7:11]],
-                          "segmentation": {"counts": runs[j], "size": [H, W]}, "time": float(row["time"])}
+                out[r] = _mask_row(row["scene_id"], row["im_id"], row["obj_id"], row["score"], q[7:11], runs[j], (H, W),
+                                   row["time"])
     return [e for e in out if e is not None], {"empty": empty, "ignored": ignored}
 
 
@@ -644,10 +648,9 @@ def write_result_masks(path, dataset, rows, device, chunk_images: int = 32, delt
 def net_mask_rows(rows, runs, info, H: int, W: int):
     """The network's own masks as detection rows (host only): `rows` = result rows as evaluate.result_rows /
     read_results give them, runs[k] = the run list of row k's full-frame H x W mask and info[k] its five ints (pixel
-    count, x, y, w, h), as rle.paste_masks and rle.encode_planes return them. Row k gives {scene_id, image_id,
-    category_id, score = the row's, bbox = [x, y, w, h] of info as floats, segmentation = {"counts": run list, "size":
-    [H, W]}, time = the row's}: _check_rows' normal form, the dict result_masks builds, in the order of `rows`. A row
-    whose pixel count is 0 gives no row. Returns (rows, {"empty": the number of those})."""
+    count, x, y, w, h), as rle.paste_masks and rle.encode_planes return them. Row k gives one _mask_row (the
+    row's ids, score and time, bbox = [x, y, w, h] of info, the run list), as result_masks does, in the order of `rows`.
+    A row whose pixel count is 0 gives no row. Returns (rows, {"empty": the number of those})."""
     if not len(rows) == len(runs) == len(info):
         raise ValueError(f"{len(rows)} rows, {len(runs)} run lists and {len(info)} info rows: one of each per row")
     out, empty = [], 0
@@ -656,9 +659,8 @@ def net_mask_rows(rows, runs, info, H: int, W: int):
         if q[0] == 0:
             empty += 1
             continue
-        out.append({"scene_id": int(row["scene_id"]), "image_id": int(row["im_id"]), "category_id": int(row["obj_id"]),
-                    "score": float(row["score"]), "bbox": [float(v) for v in q[1:5]],
-                    "segmentation": {"counts": [int(v) for v in r], "size": [int(H), int(W)]}, "time": float(row["time"])})
+        out.append(_mask_row(row["scene_id"], row["im_id"], row["obj_id"], row["score"], q[1:5], [int(v) for v in r],
+                             (H, W), row["time"]))
     return out, {"empty": empty}
 
 
@@ -702,6 +704,17 @@ def _rank(scores: Sequence[float]) -> List[int]:
     return sorted(range(len(key)), key=lambda i: (-key[i], i))
 
 
+def _keep_best(rows, idx: List[int], limit: int) -> List[int]:
+    """`idx`, indices into `rows`, cut to its `limit` best-scored rows (_rank's order), kept in the order of `idx`."""
+    return [idx[a] for a in sorted(_rank([float(rows[r]["score"]) for r in idx])[:limit])]
+
+
+def _pair_layout(n_a: Sequence[int], n_b: Sequence[int]):
+    """The kernels' group layout: (side a's (first, count) ranges, side b's, each n_a x n_b block's offset, pairs)."""
+    a0, b0, p0 = (list(accumulate(n, initial=0)) for n in (n_a, n_b, [a * b for a, b in zip(n_a, n_b)]))
+    return list(zip(a0, n_a)), list(zip(b0, n_b)), p0[:-1], p0[-1]
+
+
 def eval_results(dataset, rows, device, chunk_images: int = 32, delta: float = bop.DELTA,
                  taus: Sequence[float] = bop.TAUS) -> Dict[str, object]:
     """Score result rows against a tree the way the BOP-19 protocol does (the toolkit's eval_bop19_pose): per
@@ -734,13 +747,10 @@ def eval_results(dataset, rows, device, chunk_images: int = 32, delta: float = b
     for i, it in enumerate(tree.instances):
         groups.setdefault(_key(it), []).append(i)
     by, ignored = _rows_by(rows, 3, groups.__contains__)
-    est = {k: by.get(k, []) for k in groups}
     for key, inst in groups.items():
         if len(inst) > bop.MATCH_MAX:
             raise ValueError(f"target {key} has {len(inst)} kept instances > {bop.MATCH_MAX}")
-        if len(est[key]) > bop.MATCH_MAX:
-            order = _rank([float(rows[r]["score"]) for r in est[key]])[:bop.MATCH_MAX]
-            est[key] = [est[key][a] for a in sorted(order)]
+    est = {k: _keep_best(rows, by.get(k, []), bop.MATCH_MAX) for k in groups}
     take = {k: _taking_part(tree.inst_count[k], len(est[k])) for k in groups}
     objs = list(dict.fromkeys(k[2] for k in groups))
     tp_obj = torch.zeros((max(1, len(objs)), C, NT), dtype=torch.int64, device=device)
@@ -750,14 +760,13 @@ def eval_results(dataset, rows, device, chunk_images: int = 32, delta: float = b
     for ims, depth in _image_chunks(tree, images, chunk_images, device):
         frame = {im: f for f, im in enumerate(ims)}
         keys = [k for k in groups if k[:2] in frame]
-        slots, erows, er, gr, po, nt, thr, gobj = [], [], [], [], [], [], [], []
+        er, gr, po, P = _pair_layout([len(est[k]) for k in keys], [len(groups[k]) for k in keys])
+        erows, slots = [r for k in keys for r in est[k]], [i for k in keys for i in groups[k]]   # the ranges' rows
+        nt, thr, gobj = [], [], []
         Re, te, Rg, tg, K4, fi, fr, vr, sr, dia = [], [], [], [], [], [], [], [], [], []
         for key in keys:
             inst, rws, obj = groups[key], est[key], key[2]
             d = float(tree.info[obj]["diameter"]) / 1000.0
-            er.append((len(erows), len(rws)))
-            gr.append((len(slots), len(inst)))
-            po.append(len(fi))
             nt.append(tree.inst_count[key])
             gobj.append(objs.index(obj))
             thr.append(np.stack([th] * T + [np.array([t * d for t in th]), np.array([t * (width / 640.0) for t in th_px])]))
@@ -768,9 +777,6 @@ def eval_results(dataset, rows, device, chunk_images: int = 32, delta: float = b
                     Re.append(R), te.append(t), Rg.append(it["R"].reshape(9)), tg.append(it["t"])
                     K4.append(it["K4"]), fi.append(frame[key[:2]]), dia.append(d)
                     fr.append(mesh["range"][obj]), vr.append(mesh["vrange"][obj]), sr.append(mesh["srange"][obj])
-            erows += rws
-            slots += inst
-        P = len(fi)
         if P:
             f64 = lambda a: torch.from_numpy(np.asarray(a, np.float64))      # noqa: E731
             i32 = lambda a: torch.tensor(a, dtype=torch.int32)               # noqa: E731
@@ -873,10 +879,7 @@ def eval_coco(gt, rows, device, iou_type: str = "segm", use_ignore: bool = True,
         if segm and [int(v) for v in seg["size"]] != size[key[:2]]:
             raise ValueError(f"row {r}: segmentation.size {seg['size']} is not its image's {size[key[:2]]}")
         det_by.setdefault(key, []).append(r)
-    for key, rs in det_by.items():
-        if len(rs) > kc.MATCH_MAX:
-            order = _rank([float(rows[r]["score"]) for r in rs])[:kc.MATCH_MAX]
-            det_by[key] = [rs[a] for a in sorted(order)]
+    det_by = {key: _keep_best(rows, rs, kc.MATCH_MAX) for key, rs in det_by.items()}
     keys = sorted(set(gt_by) | set(det_by))
     images = sorted({k[:2] for k in keys})
     step = max(1, int(chunk_images))
@@ -889,18 +892,12 @@ def eval_coco(gt, rows, device, iou_type: str = "segm", use_ignore: bool = True,
         d_items = [r for k in ck for r in det_by.get(k, [])]
         g_items = [a for k in ck for a in gt_by.get(k, [])]
         D = len(d_items)
-        pair, crowd, dr, gr, po = [], [], [], [], []
-        d0 = g0 = 0
-        for k in ck:
-            nd, ng = len(det_by.get(k, [])), len(gt_by.get(k, []))
-            dr.append((d0, nd)), gr.append((g0, ng)), po.append(len(pair))
-            for d in range(d0, d0 + nd):
-                for j in range(g0, g0 + ng):
-                    pair.append((d, D + j))
-                    crowd.append(int(g_items[j].get("iscrowd", 0)) != 0)
-            d0, g0 = d0 + nd, g0 + ng
+        dr, gr, po, _ = _pair_layout([len(det_by.get(k, [])) for k in ck], [len(gt_by.get(k, [])) for k in ck])
+        pair = [(d, D + j) for (d0, nd), (g0, ng) in zip(dr, gr) for d in range(d0, d0 + nd) for j in range(g0, g0 + ng)]
+        crowd = [int(g_items[j - D].get("iscrowd", 0)) != 0 for _, j in pair]
+        for k, (d0, nd), (g0, ng) in zip(ck, dr, gr):
             cat_of.append(cats.index(k[2]))
-            d_rng.append((n_det + dr[-1][0], nd)), g_rng.append((n_gt + gr[-1][0], ng))
+            d_rng.append((n_det + d0, nd)), g_rng.append((n_gt + g0, ng))
         if segm:
             lists = [rows[r]["segmentation"]["counts"] for r in d_items] + [runs_of(a["segmentation"]) for a in g_items]
             offs = np.concatenate([[0], np.cumsum([len(c) for c in lists])]).astype(np.int64)

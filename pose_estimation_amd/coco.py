@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .bop import MATCH_MAX                               # kMatchMax of csrc/krrn_match.h: rows per side of a group
 from .runtime import h2d, ptr, stream_ptr
 
 IOU_THRS = np.linspace(0.5, 0.95, 10)
@@ -26,7 +27,6 @@ REC_THRS = np.linspace(0.0, 1.0, 101)
 AREA_RNG = np.array([[0.0, 1e10], [0.0, 32.0 ** 2], [32.0 ** 2, 96.0 ** 2], [96.0 ** 2, 1e10]])   # all, small, medium, large
 AREA_NAMES = ("all", "small", "medium", "large")
 MAX_DETS = (1, 10, 100)
-MATCH_MAX = 128                                          # detections and ground truths per group (the kernel's LDS)
 
 
 def match(score, det_range, gt_range, pair_off, iou, det_area, gt_area, gt_flags, area_rng=AREA_RNG, iou_thr=IOU_THRS,

@@ -140,9 +140,8 @@ __global__ void bop_vsd_finish_kernel(const int* __restrict__ counts, int B, int
 //      of its counters and box bounds.
 //   2. bop_visib_kernel, one block per 16 x 16 tile and instance: a tile outside the box returns after reading
 //      4 ints; otherwise one depth walk, the observed depth, the two flags per pixel. A wave holds 4 rows of 16
-//      pixels, so its 64-bit ballot of a flag is 4 rows of 16 bits: the lane at the head of each row expands its
-//      16 bits to 16 bytes and stores the row with one 16-byte store (a row cut by the frame's right border, or
-//      a plane whose rows are not 16-byte aligned, takes per-pixel byte stores instead). The same ballots give
+//      pixels (krrn_mask.h's tile layout), so its 64-bit ballot of a flag is 4 rows of 16 bits, which
+//      mask_store_row writes to the plane. The same ballots give
 //      the counts (popcount) and the wave's box bounds (first / last set column and row), which go through LDS
 //      and then one integer atomicAdd / atomicMin / atomicMax per block and quantity: all order-independent.
 //   3. bop_visib_finish_kernel: (lo, hi) bounds to (x, y, w, h), and visib_fract.
@@ -166,17 +165,10 @@ __global__ __launch_bounds__(kRastThreads) void bop_visib_box_kernel(
 }
 
 // one plane's stores and one box's bounds for one wave: bal = the wave's ballot of the pixel flag
-__device__ __forceinline__ void bop_visib_emit(unsigned long long bal, bool flag, bool inside, bool row_fast,
+__device__ __forceinline__ void bop_visib_emit(unsigned long long bal, bool inside, bool row_fast,
                                                unsigned char* __restrict__ plane, size_t pix, int lane, int lx,
                                                int wy, int* s_bounds) {
-  if (plane) {
-    if (row_fast) {
-      if ((lane & 15) == 0 && inside)
-        *reinterpret_cast<uint4*>(plane + pix) = krrn_row_bytes((unsigned)(bal >> lane) & 0xffffu);
-    } else if (inside) {
-      plane[pix] = flag ? 1 : 0;
-    }
-  }
+  if (plane) mask_store_row(bal, lane, inside, row_fast, plane, pix);
   if (lane == 0 && bal) {
     const unsigned cols = (unsigned)((bal | (bal >> 16) | (bal >> 32) | (bal >> 48)) & 0xffffull);
     int r0 = 0, r1 = 3;
@@ -231,15 +223,13 @@ __global__ __launch_bounds__(kRastThreads) void bop_visib_kernel(
     in_visib = bop_visible(obs, dist, delta);
   }
   const size_t pix = ((size_t)b * H + y) * W + x;  // used only where `inside`
-  // a whole 16-pixel row of the tile lies in the frame and starts on a 16-byte boundary (uniform over the row)
-  const bool full = lx + kRastTile <= W;
-  const size_t row0 = ((size_t)b * H + y) * W + lx;
-  const bool fast_m = full && mask && ((reinterpret_cast<uintptr_t>(mask) + row0) & 15) == 0;
-  const bool fast_v = full && mask_visib && ((reinterpret_cast<uintptr_t>(mask_visib) + row0) & 15) == 0;
+  const size_t row0 = pix - (x - lx);
+  const bool fast_m = mask && mask_row_fast(mask + row0, W - lx);
+  const bool fast_v = mask_visib && mask_row_fast(mask_visib + row0, W - lx);
   const unsigned long long bal_m = __ballot(in_mask), bal_val = __ballot(in_valid), bal_v = __ballot(in_visib);
-  const int wy = ly + 4 * wave;
-  bop_visib_emit(bal_m, in_mask, inside, fast_m, mask, pix, lane, lx, wy, s_out + 3);
-  bop_visib_emit(bal_v, in_visib, inside, fast_v, mask_visib, pix, lane, lx, wy, s_out + 7);
+  const int wy = ly + kMaskWaveRows * wave;
+  bop_visib_emit(bal_m, inside, fast_m, mask, pix, lane, lx, wy, s_out + 3);
+  bop_visib_emit(bal_v, inside, fast_v, mask_visib, pix, lane, lx, wy, s_out + 7);
   if (lane == 0) {
     if (bal_m) atomicAdd(&s_out[0], __popcll(bal_m));
     if (bal_val) atomicAdd(&s_out[1], __popcll(bal_val));

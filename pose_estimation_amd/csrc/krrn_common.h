@@ -26,13 +26,6 @@ static inline bool krrn_aligned16(const void* p) { return (((uintptr_t)p) & 15u)
 
 __host__ __device__ static inline int krrn_cdiv(int a, int b) { return (a + b - 1) / b; }
 
-// 16 flag bits -> 16 bytes of 0 / 1 (bit i to byte i): one row of a 16 x 16 tile's u8 plane as a 16-byte store
-// (bop.hip's visibility planes, rle.hip's decoded masks)
-__device__ __forceinline__ uint4 krrn_row_bytes(unsigned bits) {
-  auto four = [](unsigned n) { return ((n & 0xfu) * 0x00204081u) & 0x01010101u; };  // the shifted copies do not overlap
-  return make_uint4(four(bits), four(bits >> 4), four(bits >> 8), four(bits >> 12));
-}
-
 // Bijective XCD-aware block remap (cdna_hip_programming.md §5 "XCD swizzle must be
 // bijective"): consecutive logical tiles land on the same XCD so that tiles that share
 // an operand panel hit the same L2.

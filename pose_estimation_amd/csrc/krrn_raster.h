@@ -5,13 +5,13 @@
 #pragma once
 #include <math.h>
 
-#include "krrn_common.h"
+#include "krrn_mask.h"  // the 16 x 16 tile layout (integer code only)
 
 namespace {
 
-constexpr int kRastTile = 16;
-constexpr int kRastThreads = kRastTile * kRastTile;  // one thread per pixel of the tile; also the face chunk
-constexpr int kRastWaves = kRastThreads / 64;
+constexpr int kRastTile = kMaskTile;
+constexpr int kRastThreads = kMaskThreads;  // one thread per pixel of the tile; also the face chunk
+constexpr int kRastWaves = kMaskWaves;
 constexpr int kRastSetup = 14;                       // doubles per compacted face
 constexpr double kRastNear = 1e-3;
 

@@ -2,33 +2,29 @@
 // full-frame planes of 0 / 1 with each plane's pixel count and tight box (include/krrn_hip.h states the definition;
 // tests/paste_ref.py restates it in numpy). Comparisons and integer work only: no arithmetic on a logit, no atomics,
 // nothing that depends on an order. Two launches:
-//   1. mask_paste_tile_kernel, 16 x 16 tiles of the frame laid out like rle_tile_kernel and bop_visib_kernel: 256
-//      threads, a wave is 4 rows of 16 pixels. A block takes kPasteSpan tiles side by side of one crop, one after the
-//      other (a block per tile spent more time starting blocks than storing: DESIGN.md section 3). A tile that the
+//   1. mask_paste_tile_kernel, 16 x 16 tiles of the frame in krrn_mask.h's tile layout. A block takes kPasteSpan
+//      tiles side by side of one crop, one after the other (a block per tile spent more time starting blocks than
+//      storing: DESIGN.md section 3). A tile that the
 //      crop's window cannot touch (or a crop whose chan selects nothing) stores zeros without reading a logit:
 //      block-uniform, and most tiles of a frame; a whole span of them, when it is full width and its rows start on
 //      16-byte boundaries, is zeroed by one 16-byte store per thread of two waves, 128 consecutive bytes a row. In a
 //      touched tile each lane inside the window walks its pixel's C1 logits, channel stride S S: the 16 lanes of a
-//      row read 64 consecutive bytes per channel. Stores as rle_tile_kernel: the wave's 64-bit ballot is four 16-bit
-//      rows, the lane at the head of a row expands its 16 bits to one 16-byte store; a row cut by the right border,
-//      or one that does not start on a 16-byte boundary, takes per-pixel byte stores. Every tile stores all its
-//      pixels: no memset.
+//      row read 64 consecutive bytes per channel. The wave's ballot is stored by mask_store_row. Every tile stores
+//      all its pixels: no memset.
 //   2. mask_paste_info_kernel, one block per crop: the set bytes of the plane inside the clipped window (no pixel
-//      outside it can be set) reduced to count / min / max in a fixed order (lanes by shuffles, the waves through
-//      LDS, as rle_scan_kernel), and thread 0 writes the row. Wave w takes the window's rows w, w + 4, ..; a lane
-//      its columns lane, lane + 64, ..
+//      outside it can be set) reduced to count / min / max and written by mask_info_row. Wave w takes the window's
+//      rows w, w + 4, ..; a lane its columns lane, lane + 64, ..
 // The window's position is taken in 64-bit, so any rc reads and writes nothing out of bounds. Both kernels read only
 // crop b's logits, chan and rc and write only its plane and info row.
-#include "krrn_raster.h"  // Span / rast_overlap: the entry points' overlap check
+#include "krrn_raster.h"  // Span / rast_overlap: the entry points' overlap check; brings krrn_mask.h
 
 namespace {
 
-constexpr int kPasteThreads = 256;
-constexpr int kPasteWaves = kPasteThreads / 64;
-constexpr int kPasteTile = 16;
+constexpr int kPasteThreads = kMaskThreads;
+constexpr int kPasteWaves = kMaskWaves;
+constexpr int kPasteTile = kMaskTile;
 constexpr int kPasteSpan = 8;      // tiles side by side per block: 128 columns, 8 stores of 16 bytes to a row
 static_assert(kPasteSpan * kPasteTile == 8 * 16 && kPasteThreads >= 8 * kPasteTile, "the span's zero stores");
-constexpr int kPasteMaxY = 65535;  // grid.y's limit: more crops than that share blocks
 
 __global__ __launch_bounds__(kPasteThreads) void mask_paste_tile_kernel(const float* __restrict__ logits,
                                                                         long long ld_b, int C1, int S,
@@ -59,7 +55,6 @@ __global__ __launch_bounds__(kPasteThreads) void mask_paste_tile_kernel(const fl
       if (lx64 >= W) break;
       const int lx = (int)lx64, x = lx + (tid & (kPasteTile - 1));
       const bool inside = x < W && y < H;
-      const bool full = W - lx >= kPasteTile;
       // uniform: the tile's rows / columns against the window's rmin .. rmin + S - 1 / cmin .. cmin + S - 1
       const bool touched = rows_hit && (long long)lx + kPasteTile > cmin && lx < cmin + S;
       bool flag = false;
@@ -78,13 +73,7 @@ __global__ __launch_bounds__(kPasteThreads) void mask_paste_tile_kernel(const fl
       }
       const unsigned long long bal = __ballot(flag);
       const size_t pix = ((size_t)b * H + y) * W + x;  // used only where `inside`
-      const size_t row0 = ((size_t)b * H + y) * W + lx;
-      if (full && ((reinterpret_cast<uintptr_t>(mask) + row0) & 15) == 0) {  // uniform over the row's 16 lanes
-        if ((lane & 15) == 0 && inside)
-          *reinterpret_cast<uint4*>(mask + pix) = krrn_row_bytes((unsigned)(bal >> lane) & 0xffffu);
-      } else if (inside) {
-        mask[pix] = flag ? 1 : 0;
-      }
+      mask_store_row(bal, lane, inside, mask_row_fast(mask + (pix - (x - lx)), W - lx), mask, pix);
     }
   }
 }
@@ -115,23 +104,7 @@ __global__ __launch_bounds__(kPasteThreads) void mask_paste_info_kernel(const un
         if (n) cnt += n, xlo = min(xlo, xx), xhi = max(xhi, xx), ylo = min(ylo, (int)r0 + lo), yhi = max(yhi, (int)r0 + hi);
       }
     }
-    for (int d = 32; d > 0; d >>= 1) {
-      cnt += __shfl_xor(cnt, d);
-      xlo = min(xlo, __shfl_xor(xlo, d)), xhi = max(xhi, __shfl_xor(xhi, d));
-      ylo = min(ylo, __shfl_xor(ylo, d)), yhi = max(yhi, __shfl_xor(yhi, d));
-    }
-    if (lane == 0) s_red[wave][0] = cnt, s_red[wave][1] = xlo, s_red[wave][2] = xhi, s_red[wave][3] = ylo, s_red[wave][4] = yhi;
-    __syncthreads();
-    if (tid == 0) {
-      for (int w = 1; w < kPasteWaves; ++w) {
-        cnt += s_red[w][0];
-        xlo = min(xlo, s_red[w][1]), xhi = max(xhi, s_red[w][2]);
-        ylo = min(ylo, s_red[w][3]), yhi = max(yhi, s_red[w][4]);
-      }
-      int* q = info + (size_t)b * 5;
-      const bool any = cnt > 0;
-      q[0] = cnt, q[1] = any ? xlo : 0, q[2] = any ? ylo : 0, q[3] = any ? xhi - xlo : 0, q[4] = any ? yhi - ylo : 0;
-    }
+    mask_info_row(cnt, xlo, xhi, ylo, yhi, s_red, info + (size_t)b * 5);
     __syncthreads();  // the next crop rewrites s_red
   }
 }
@@ -160,7 +133,7 @@ KRRN_API int krrn_mask_paste_f32(const float* logits, long long ld_b, int C1, in
   hipStream_t st = (hipStream_t)stream;
   const int tiles_y = (H - 1) / kPasteTile + 1;
   const int spans_x = (W - 1) / (kPasteTile * kPasteSpan) + 1;  // spans_x * tiles_y <= H * W
-  hipLaunchKernelGGL(mask_paste_tile_kernel, dim3(spans_x * tiles_y, B < kPasteMaxY ? B : kPasteMaxY),
+  hipLaunchKernelGGL(mask_paste_tile_kernel, dim3(spans_x * tiles_y, B < kMaskMaxY ? B : kMaskMaxY),
                      dim3(kPasteThreads), 0, st, logits, ld_b, C1, S, chan, rc, B, H, W, spans_x, mask);
   hipLaunchKernelGGL(mask_paste_info_kernel, dim3(B), dim3(kPasteThreads), 0, st, mask, S, rc, B, H, W, info);
   return krrn_launch_status();

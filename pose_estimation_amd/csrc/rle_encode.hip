@@ -4,30 +4,30 @@
 // launches over a per-column workspace ws [n][kEncFields][W]:
 //   1. rle_count_kernel, one wave per strip of 16 columns and mask (4 strips per block). Runs follow the pixels
 //      column-major, so a wave walks its strip downwards, 64 rows per step: lane r loads the 16 bytes of row y0 + r
-//      (one 16-byte load when the strip is full width and the address is 16-byte aligned, byte loads otherwise: the
-//      rule of the decoder's stores), and 16 ballots ("byte c of my row is set") turn the 64 x 16 bytes into one
-//      64-bit word of rows per column. Lane c < 16 keeps column x0 + c: its transitions are w ^ ((w << 1) | carry),
-//      carry = the pixel above the step's first row, which at y = 0 is pixel (x - 1, H - 1) (0 for x = 0): a run
-//      that ends a column and begins the next is one run. Rows past H are masked out. Per column: the number of
-//      transitions, the number of set pixels, the lowest and highest set row, the position of the last transition.
+//      (one 16-byte load or byte loads: mask_row_fast of krrn_mask.h, the rule of the plane stores), and 16 ballots
+//      ("byte c of my row is set") turn the 64 x 16 bytes into one 64-bit word of rows per column. Lane c < 16
+//      keeps column x0 + c: its transitions are w ^ ((w << 1) | carry), carry = the pixel above the step's first
+//      row, which at y = 0 is pixel (x - 1, H - 1) (0 for x = 0): a run that ends a column and begins the next is
+//      one run. Rows past H are masked out. Per column: the number of transitions, the number of set pixels, the
+//      lowest and highest set row, the position of the last transition.
 //   2. rle_offsets_kernel, one block per mask: the exclusive prefix sum of the columns' transition counts (the index
-//      of each column's first run; the shuffle scan of rle_scan_kernel) and the running "last transition before
-//      column x", in chunks of 256 columns with a carry; the reduction of count / box for `info`; then n_runs = T +
-//      1, the final run H W - t_{T-1}, and zeros from n_runs to the end of the slot.
+//      of each column's first run) and the running "last transition before column x", the steps of krrn_mask.h's
+//      mask_block_scan for the (sum, max) pair at once, in chunks of 256 columns with a carry (the helper scans one
+//      value: two calls would take four barriers a chunk); mask_info_row for count / box; then
+//      n_runs = T + 1, the final run H W - t_{T-1}, and zeros from n_runs to the end of the slot.
 //   3. rle_emit_kernel, the walk of 1 again: lane c visits the set bits of its column's transition word in
 //      increasing order and stores counts[j] = t_j - t_{j-1} at j = first[x] + rank while j < max_runs; the
 //      predecessor is the bit before, else the column's last transition of an earlier step, else the scan's last
 //      transition before the column (0 for j = 0).
 // Every kernel reads and writes only mask i's plane, workspace rows and output slots, so a mask's outputs do not
 // depend on the rest of the batch.
-#include "krrn_common.h"
+#include "krrn_mask.h"
 
 namespace {
 
-constexpr int kEncThreads = 256;
-constexpr int kEncWaves = kEncThreads / 64;  // strips per block in count / emit
-constexpr int kEncCols = 16;                 // columns per strip: the bytes of one 16-byte load
-constexpr int kEncMaxY = 65535;              // grid.y's limit: more masks than that share blocks
+constexpr int kEncThreads = kMaskThreads;
+constexpr int kEncWaves = kMaskWaves;  // strips per block in count / emit
+constexpr int kEncCols = kMaskTile;    // columns per strip: the bytes of one 16-byte load
 // ws fields, each [W] per mask
 enum { kEncTrans = 0, kEncCount, kEncYlo, kEncYhi, kEncLast, kEncFirst, kEncPrev, kEncFields };
 constexpr int kEncNone = 0x7fffffff;
@@ -43,7 +43,7 @@ __device__ __forceinline__ unsigned long long enc_words(const unsigned char* __r
   uint4 q = make_uint4(0u, 0u, 0u, 0u);
   if (y < H) {
     const unsigned char* row = plane + (size_t)y * W + x0;
-    if (W - x0 >= kEncCols && (reinterpret_cast<uintptr_t>(row) & 15) == 0) {
+    if (mask_row_fast(row, W - x0)) {
       q = *reinterpret_cast<const uint4*>(row);
     } else {
       unsigned v[4] = {0u, 0u, 0u, 0u};
@@ -119,6 +119,7 @@ __global__ __launch_bounds__(kEncThreads) void rle_offsets_kernel(int n, int H, 
       const bool in = base + tid < W;
       const int x = in ? (int)(base + tid) : 0;
       const int nt = in ? c_trans[x] : 0, lt = in ? c_last[x] : -1;
+      // mask_block_scan's steps for the (sum, max) pair at once, so that a chunk takes two barriers, not four
       int v = nt, m = lt;  // inclusive sum / max over the wave
       for (int d = 1; d < 64; d <<= 1) {
         const int uv = __shfl_up(v, d), um = __shfl_up(m, d);
@@ -141,22 +142,8 @@ __global__ __launch_bounds__(kEncThreads) void rle_offsets_kernel(int n, int H, 
       total += all, tlast = max(tlast, mall);
       __syncthreads();  // the next chunk rewrites s_sum / s_max
     }
-    for (int d = 32; d > 0; d >>= 1) {
-      cnt += __shfl_xor(cnt, d);
-      xlo = min(xlo, __shfl_xor(xlo, d)), xhi = max(xhi, __shfl_xor(xhi, d));
-      ylo = min(ylo, __shfl_xor(ylo, d)), yhi = max(yhi, __shfl_xor(yhi, d));
-    }
-    if (lane == 0) s_red[wave][0] = cnt, s_red[wave][1] = xlo, s_red[wave][2] = xhi, s_red[wave][3] = ylo, s_red[wave][4] = yhi;
-    __syncthreads();
+    mask_info_row(cnt, xlo, xhi, ylo, yhi, s_red, info + (size_t)i * 5);
     if (tid == 0) {
-      for (int w = 1; w < kEncWaves; ++w) {
-        cnt += s_red[w][0];
-        xlo = min(xlo, s_red[w][1]), xhi = max(xhi, s_red[w][2]);
-        ylo = min(ylo, s_red[w][3]), yhi = max(yhi, s_red[w][4]);
-      }
-      int* q = info + (size_t)i * 5;
-      const bool any = cnt > 0;
-      q[0] = cnt, q[1] = any ? xlo : 0, q[2] = any ? ylo : 0, q[3] = any ? xhi - xlo : 0, q[4] = any ? yhi - ylo : 0;
       n_runs[i] = total < 0x7fffffff ? total + 1 : 0x7fffffff;
       if (total < max_runs) counts[(size_t)i * max_runs + total] = HW - max(tlast, 0);
     }
@@ -210,7 +197,7 @@ KRRN_API int krrn_rle_encode_u8(const unsigned char* mask, int n, int H, int W, 
   if (n == 0) return KRRN_OK;
   hipStream_t st = (hipStream_t)stream;
   const int strips = (W - 1) / kEncCols + 1;
-  const dim3 walk(krrn_cdiv(strips, kEncWaves), n < kEncMaxY ? n : kEncMaxY);
+  const dim3 walk(krrn_cdiv(strips, kEncWaves), n < kMaskMaxY ? n : kMaskMaxY);
   hipLaunchKernelGGL(rle_count_kernel, walk, dim3(kEncThreads), 0, st, mask, n, H, W, strips, ws);
   hipLaunchKernelGGL(rle_offsets_kernel, dim3(n), dim3(kEncThreads), 0, st, n, H, W, H * W, max_runs, ws, counts, n_runs,
                      info);

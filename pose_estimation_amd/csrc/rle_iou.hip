@@ -2,12 +2,11 @@
 // masks, taken from the run lists themselves: no plane is decoded (include/krrn_hip.h states the definition;
 // tests/coco_ref.py restates it through decoded planes). Integer work plus one f64 division per pair: no atomics,
 // nothing that depends on an order between threads, so a pair's result does not depend on the batch. Two launches:
-//   1. rle_iou_scan_kernel, one block per mask, rle.hip's saturating scan: the inclusive prefix sums of the mask's
-//      runs into `ends` (saturated at INT32_MAX, so they are non-decreasing and never wrap) and, from the clipped
-//      lengths of the odd runs, a second scan into `s`: s[k] = the set pixels in runs 0 .. k. Thread 0 writes the
-//      mask's area, the last s.
+//   1. rle_iou_scan_kernel, one block per mask: the inclusive prefix sums of the mask's runs into `ends` by
+//      mask_scan_runs (krrn_mask.h; saturated at INT32_MAX) and, from the clipped lengths of the odd runs, a second
+//      mask_block_scan into `s`: s[k] = the set pixels in runs 0 .. k. Thread 0 writes the mask's area, the last s.
 //   2. rle_iou_pair_kernel, one wave per pair. The set pixels below p of a mask are F(p) = s[j - 1] + (j odd ? p -
-//      ends[j - 1] : 0) with j = #{k : ends[k] <= p}, one upper-bound binary search. The lanes stride over the set
+//      ends[j - 1] : 0) with j = #{k : ends[k] <= p}, one mask_upper_bound. The lanes stride over the set
 //      runs [lo, hi) of the list with fewer runs and add F_other(hi) - F_other(lo); a wave-wide integer add finishes
 //      the pair. Intersection is symmetric, so which list is walked changes nothing but the work. A wave whose two
 //      masks' set spans [ends[0], last odd end) do not overlap stores 0 without a search.
@@ -16,20 +15,13 @@
 //
 // krrn_box_iou_f64: the same for [x, y, w, h] boxes, one thread per pair, bop_scene._box_iou's arithmetic in f64
 // with every operation rounded on its own (this file is built without FMA contraction).
-#include "krrn_common.h"
+#include "krrn_mask.h"
 
 namespace {
 
-constexpr int kIouThreads = 256;
-constexpr int kIouWaves = kIouThreads / 64;
+constexpr int kIouThreads = kMaskThreads;
+constexpr int kIouWaves = kMaskWaves;
 constexpr long long kIouCap = 0x7fffffffll;
-
-// the runs of mask i: counts / ends / s [r0, r0 + nr); a bad range is empty
-__device__ __forceinline__ void iou_range(const int* __restrict__ offs, int n, int n_counts, int i, int& r0, int& nr) {
-  const int a = offs[i], b = offs[i + 1], total = min(offs[n], n_counts);
-  r0 = a, nr = b - a;
-  if (a < 0 || b < a || b > total) r0 = 0, nr = 0;
-}
 
 __global__ __launch_bounds__(kIouThreads) void rle_iou_scan_kernel(const int* __restrict__ counts,
                                                                    const int* __restrict__ offs, int n, int n_counts,
@@ -37,58 +29,26 @@ __global__ __launch_bounds__(kIouThreads) void rle_iou_scan_kernel(const int* __
                                                                    int* __restrict__ area) {
   __shared__ long long s_tot[kIouWaves];
   __shared__ int s_odd[kIouWaves];
-  const int i = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int i = blockIdx.x;
   int r0, nr;
-  iou_range(offs, n, n_counts, i, r0, nr);
-  long long carry = 0;  // uniform: the saturated sum of the chunks before this one
-  int carry_s = 0;      // uniform: the set pixels of the chunks before this one (<= carry)
-  for (int base = 0; base < nr; base += kIouThreads) {  // uniform over the block
-    const int k = base + tid;
-    const int c = k < nr ? max(counts[r0 + k], 0) : 0;
-    long long v = c;
-    for (int d = 1; d < 64; d <<= 1) {
-      const long long up = __shfl_up(v, d);
-      if (lane >= d) v += up;
-    }
-    if (lane == 63) s_tot[wave] = v;
-    __syncthreads();
-    long long before = carry, all = 0;
-    for (int w = 0; w < kIouWaves; ++w) {
-      if (w < wave) before += s_tot[w];
-      all += s_tot[w];
-    }
-    const long long e = min(before + v, kIouCap), e_prev = min(before + v - c, kIouCap);
+  mask_runs_range(offs, n, n_counts, i, r0, nr);
+  int carry_s = 0;  // uniform: the set pixels of the steps before this one
+  mask_scan_runs(counts + r0, nr, kIouCap, s_tot, [&](int k, long long e_prev, long long e) {
     // the clipped length of an odd run; the odd runs are disjoint in [0, INT32_MAX], so their sum fits an int
-    int o = (k < nr && (k & 1)) ? (int)(e - e_prev) : 0;
-    for (int d = 1; d < 64; d <<= 1) {
-      const int up = __shfl_up(o, d);
-      if (lane >= d) o += up;
-    }
-    if (lane == 63) s_odd[wave] = o;
-    __syncthreads();
-    int before_s = carry_s, all_s = 0;
-    for (int w = 0; w < kIouWaves; ++w) {
-      if (w < wave) before_s += s_odd[w];
-      all_s += s_odd[w];
-    }
+    int o = (k < nr && (k & 1)) ? (int)(e - e_prev) : 0, before_s, all_s;
+    mask_block_scan(o, 0, [](int a, int b) { return a + b; }, s_odd, before_s, all_s);
     if (k < nr) {
       ends[r0 + k] = (int)e;
-      s[r0 + k] = before_s + o;
+      s[r0 + k] = carry_s + before_s + o;
     }
-    carry = min(carry + all, kIouCap);
-    carry_s += all_s;
-    __syncthreads();  // the next chunk rewrites s_tot / s_odd
-  }
-  if (tid == 0) area[i] = carry_s;
+    carry_s += all_s;  // s_odd is rewritten after the next step's first barrier
+  });
+  if (threadIdx.x == 0) area[i] = carry_s;
 }
 
 // F(p): the set pixels with index < p of the mask whose scans are e / s [0, nr)
 __device__ __forceinline__ int iou_below(const int* __restrict__ e, const int* __restrict__ s, int nr, int p) {
-  int lo = 0, hi = nr;
-  while (lo < hi) {  // the number of e[k] <= p
-    const int mid = (lo + hi) >> 1;
-    if (e[mid] <= p) lo = mid + 1; else hi = mid;
-  }
+  const int lo = mask_upper_bound(e, nr, p);  // the number of e[k] <= p
   if (lo >= nr) return nr > 0 ? s[nr - 1] : 0;
   if (lo == 0) return 0;
   return s[lo - 1] + ((lo & 1) ? p - e[lo - 1] : 0);
@@ -114,8 +74,8 @@ __global__ __launch_bounds__(kIouThreads) void rle_iou_pair_kernel(const int* __
   long long area_a = 0, area_b = 0;
   if (a >= 0 && a < n && b >= 0 && b < n) {
     int ra, na, rb, nb;
-    iou_range(offs, n, n_counts, a, ra, na);
-    iou_range(offs, n, n_counts, b, rb, nb);
+    mask_runs_range(offs, n, n_counts, a, ra, na);
+    mask_runs_range(offs, n, n_counts, b, rb, nb);
     area_a = area[a], area_b = area[b];
     if (na >= 2 && nb >= 2) {  // fewer runs than two: no set run
       // walk w's set runs, search in o

@@ -1,8 +1,8 @@
 """Per-kernel register / scratch / LDS / occupancy table of libkrrn_hip.so's sources, from hipcc's
-`-Rpass-analysis=kernel-resource-usage` remarks with the Makefile's flags (per-file FLAGS_* included).
-CPU only (hipcc cross-compiles for gfx950):
+`-Rpass-analysis=kernel-resource-usage` remarks with the Makefile's flags (its per-file FLAGS_<stem> lines are read,
+not restated). CPU only (hipcc cross-compiles for gfx950):
 
-    python3 profiles/resource_usage.py [--out profiles/r4_resource_usage.txt]
+    python3 profiles/resource_usage.py [--out profiles/r4_resource_usage.txt] [--csrc other/checkout/csrc]
 
 Every kernel with ScratchSize > 0 is flagged: a spill in a hot loop costs HBM traffic per launch
 (VERDICT r3 weak #6 / #7)."""
@@ -16,7 +16,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "pose_estimation_amd", "csrc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=fast-honor-pragmas",
          "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]  # as pose_estimation_amd/csrc/Makefile
-EXTRA = {"pnp": ["-ffp-contract=off"], "winograd": ["-fno-slp-vectorize"]}
 FIELDS = ("VGPRs", "AGPRs", "ScratchSize [bytes/lane]", "Occupancy [waves/SIMD]", "LDS Size [bytes/block]", "TotalSGPRs",
           "VGPRs Spill")
 
@@ -30,10 +29,16 @@ def demangle(names):
         return names
 
 
-def kernels(src):
+def extra_flags(csrc):
+    """The per-file `FLAGS_<stem> := ...` lines of the Makefile: {stem: [flag, ...]}."""
+    with open(os.path.join(csrc, "Makefile")) as f:
+        return {m.group(1): m.group(2).split() for m in re.finditer(r"^FLAGS_(\w+)\s*:=\s*(.*)$", f.read(), re.M)}
+
+
+def kernels(src, extra):
     stem = os.path.splitext(os.path.basename(src))[0]
     with tempfile.TemporaryDirectory() as td:
-        r = subprocess.run(["/opt/rocm/bin/hipcc", *FLAGS, *EXTRA.get(stem, []), "-c", src, "-o",
+        r = subprocess.run(["/opt/rocm/bin/hipcc", *FLAGS, *extra.get(stem, []), "-c", src, "-o",
                             os.path.join(td, "k.o"), "-Rpass-analysis=kernel-resource-usage"],
                            capture_output=True, text=True)
     rows, cur = [], None
@@ -55,11 +60,12 @@ def kernels(src):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default="")
+    ap.add_argument("--csrc", default=CSRC, help="another checkout's csrc/ (to compare two commits)")
     args = ap.parse_args()
-    rows = []
-    for f in sorted(os.listdir(CSRC)):
+    rows, extra = [], extra_flags(args.csrc)
+    for f in sorted(os.listdir(args.csrc)):
         if f.endswith(".hip"):
-            rows += kernels(os.path.join(CSRC, f))
+            rows += kernels(os.path.join(args.csrc, f), extra)
     hdr = f"{'file':14s} {'VGPR':>4s} {'AGPR':>4s} {'SGPR':>4s} {'scratch':>7s} {'spill':>5s} {'occ':>3s} {'LDS':>6s}  kernel"
     lines = [hdr]
     for r in rows:

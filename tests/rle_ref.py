@@ -4,7 +4,7 @@ an encoder, the compressed string codec written independently of pose_estimation
 tests run on."""
 import numpy as np
 
-CHUNK = 256                                              # kRleChunk of csrc/rle.hip: runs per scan step
+CHUNK = 256                                              # kMaskThreads of csrc/krrn_mask.h: runs per step of mask_scan_runs
 SIZES = ((5, 3), (16, 16), (21, 37), (41, 50), (48, 64), (480, 640))   # H x W
 # two literal vectors of the string form (made by a restatement of the published algorithm; not cross-checked with
 # pycocotools, which is not a dependency)
