@@ -490,6 +490,40 @@ int krrn_choose_points(const unsigned char* mask, int B, int S, int N, const flo
                        int stream_id, long long* choose, float* cloud, float* xmap, float* ymap, int* count,
                        void* stream);
 
+/* The same two steps for crops resampled to one network size T: the reference's Data.RESIZE path
+ * (_load_resize_data, dataset/linemod/batchdataset.py:339-601) by this project's own definition.
+ * Crop b is the S_b x S_b window of frame[b] at rows rc[2b] .., cols rc[2b+1] .., S_b = side[b] (int32 [B], read
+ * on the device: one launch mixes sides). All index arithmetic is integer. Output pixel j of T sits at window
+ * coordinate ((2j+1) S_b - T) / (2T) (cv2.resize's half-pixel centres; rows alike): nx = (2j+1) S_b - T, D = 2T,
+ * x0 = floor(nx / D), wx = (double)(nx - x0 D) / (double)D, taps xa = clamp(x0, 0, S_b - 1), xb = clamp(x0 + 1, 0,
+ * S_b - 1): the border is the window's own edge (the reference resizes the cut window).
+ * krrn_crop_inputs_resize_u8: img f32 [B][3][T][T]: per channel on the raw u8 values, in f64 with every product and
+ * sum rounded on its own, top = (1 - wx) a[ya][xa] + wx a[ya][xb], bot likewise on row yb, p = (1 - wy) top + wy bot;
+ * then (float(p / 255.) - mean) / std as krrn_crop_inputs_u8. Plain bilinear also when S_b > T (INTER_LINEAR; no area
+ * averaging). mask u8 [B][T*T] = krrn_crop_inputs_u8's predicate at the nearest source pixel of the centre,
+ * (r0 + ((2i+1) S_b) / D, c0 + ((2j+1) S_b) / D) by integer division, always inside the window. The reference's
+ * 'resize' branch resizes the whole frame, not the window, for mask, coordinate and region: not copied.
+ * With S_b == T both outputs equal krrn_crop_inputs_u8's bit for bit. 1 <= T <= 4096, 1 <= B <= 65535 (KRRN_ESHAPE
+ * otherwise, before any launch). The host cannot see side[b] or rc: the caller keeps every window inside the
+ * frame (dataset.build_inputs checks its boxes); a window that is not gives a crop of zeros with an empty mask. */
+int krrn_crop_inputs_resize_u8(const unsigned char* rgb, const float* depth, const unsigned char* mask_label,
+                               const unsigned char* obj_mask, int F, int H, int W, const int* frame, const int* rc,
+                               const int* side, int B, int T, float* img, unsigned char* mask, void* stream);
+
+/* choose over the T*T mask exactly as krrn_choose_points (the same keys of (seed, stream_id, crop, rank), order,
+ * wrap padding, zeros and count 0 for an empty mask; choose int64 [B][N] = i*T + j). For a chosen pixel (i, j):
+ * x_map = (float)((double)c0 + (double)nx / (double)D), y_map likewise: the resized pixel's centre in full-frame
+ * coordinates, generally fractional, which is what krrn_pnp_ransac_f32 reads; cloud = the back-projection of the
+ * nearest source pixel (sr, sc) above with the frame's own K4 in krrn_choose_points' f32 order (z = depth[sr][sc] /
+ * depth_scale, ((float)sc - cx) z / fx, ((float)sr - cy) z / fy). The reference (:551-553) truncates bilinear x / y
+ * maps to int16 to index the depth and (:526) moves the principal point to OUT_SIZE / 2: not copied. With
+ * S_b == T every output equals krrn_choose_points' bit for bit. Limits as above, N >= 1, depth_scale != 0,
+ * 0 <= stream_id <= 65534; a window outside the frame gives count 0 and zeros. */
+int krrn_choose_points_resize(const unsigned char* mask, int B, int T, int N, const float* depth, int H, int W,
+                              const int* frame, const int* rc, const int* side, const float* K4, float depth_scale,
+                              const long long* seed, int stream_id, long long* choose, float* cloud, float* xmap,
+                              float* ymap, int* count, void* stream);
+
 /* Farthest point sampling (tools/script/sample_model.py:35-48): per set b of
  * pts [B][n][3], out_idx int32 [B][n_samples] = start at 0, then repeatedly the argmax (lowest
  * index on ties) of the running min distance to the selected set; distances as numpy computes

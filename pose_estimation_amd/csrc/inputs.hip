@@ -10,27 +10,13 @@
 //                         to N when fewer (:675-679); then x/y_map_choosed (full-frame column / row,
 //                         :712-715) and the back-projected cloud (:714-721)
 //
-// One workgroup per crop for choose: block-wide ballot scans keep the row-major order, and the
-// random subset is the N smallest of per-rank 32-bit hash keys found by a 4-pass radix select
-// (ties broken by rank), so no sort and no workspace. The reference draws the subset with
+// One workgroup per crop for choose; the selection itself (krrn_choose.h, shared with inputs_resize.hip)
+// is the N smallest of per-rank 32-bit hash keys. The reference draws the subset with
 // numpy's global RNG (np.random.shuffle); this one is a counter hash of (seed, crop, rank):
 // the same distribution, not the same draw.
-#include "krrn_common.h"
+#include "krrn_choose.h"
 
 namespace {
-
-constexpr int kChooseThreads = 1024;
-constexpr int kChooseWaves = kChooseThreads / 64;
-constexpr int kChooseStreamMax = 65534;
-
-__device__ __forceinline__ unsigned mix32(unsigned long long x) {
-  // splitmix64 finaliser, high half
-  x += 0x9E3779B97F4A7C15ull;
-  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-  x ^= x >> 31;
-  return (unsigned)(x >> 32);
-}
 
 __global__ __launch_bounds__(256) void crop_inputs_kernel(const unsigned char* __restrict__ rgb,
                                                           const float* __restrict__ depth,
@@ -58,122 +44,20 @@ __global__ __launch_bounds__(256) void crop_inputs_kernel(const unsigned char* _
   mask[(size_t)b * S * S + p] = m ? 1 : 0;
 }
 
-// exclusive prefix of a 0/1 flag over the block (thread order), and the block total
-__device__ __forceinline__ int block_excl_scan(bool flag, int* wsum, int& total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const unsigned long long bal = __ballot(flag);
-  const int in_wave = __popcll(bal & ((1ull << lane) - 1ull));
-  __syncthreads();
-  if (lane == 0) wsum[wave] = __popcll(bal);
-  __syncthreads();
-  int before = 0;
-  total = 0;
-  for (int w = 0; w < kChooseWaves; ++w) {
-    const int v = wsum[w];
-    before += (w < wave) ? v : 0;
-    total += v;
-  }
-  return before + in_wave;
-}
-
 __global__ __launch_bounds__(kChooseThreads) void choose_points_kernel(
     const unsigned char* __restrict__ mask, int S, int N, const float* __restrict__ depth, int H, int W,
     const int* __restrict__ frame, const int* __restrict__ rc, const float* __restrict__ K4, float depth_scale,
     const long long* __restrict__ seed, int stream_id, long long* __restrict__ choose, float* __restrict__ cloud,
     float* __restrict__ xmap, float* __restrict__ ymap, int* __restrict__ count_out) {
-  __shared__ int wsum[kChooseWaves];
-  __shared__ int hist[256];
-  __shared__ int sel_state[2];  // threshold key, ties to take
   const int b = blockIdx.x;
   const int tid = threadIdx.x;
-  const int SS = S * S;
-  const unsigned char* mb = mask + (size_t)b * SS;
-  const unsigned long long base = ((unsigned long long)seed[0] * 0x9E3779B97F4A7C15ull) ^
-                                  ((unsigned long long)(stream_id + 1) << 48) ^ ((unsigned long long)b << 24);
-
-  // pass A: number of mask pixels
-  int count = 0;
-  for (int p0 = 0; p0 < SS; p0 += kChooseThreads) {
-    const int p = p0 + tid;
-    int tot;
-    block_excl_scan(p < SS && mb[p] != 0, wsum, tot);
-    count += tot;
-  }
+  long long* cb = choose + (size_t)b * N;
+  const int count = choose_select(mask + (size_t)b * S * S, S * S, N, choose_key_base(seed, stream_id, b), cb);
   if (tid == 0) count_out[b] = count;
-  if (count == 0) {  // the reference drops such a sample (choose error, :679-681); zeros here
-    for (int j = tid; j < N; j += kChooseThreads) {
-      choose[(size_t)b * N + j] = 0;
-      xmap[(size_t)b * N + j] = 0.f;
-      ymap[(size_t)b * N + j] = 0.f;
-      cloud[((size_t)b * N + j) * 3 + 0] = 0.f;
-      cloud[((size_t)b * N + j) * 3 + 1] = 0.f;
-      cloud[((size_t)b * N + j) * 3 + 2] = 0.f;
-    }
+  if (count == 0) {
+    choose_zero_outputs(b, N, choose, cloud, xmap, ymap);
     return;
   }
-
-  // radix select: the N-th smallest key over ranks [0, count)
-  unsigned thr = 0xFFFFFFFFu;
-  int need = N;
-  const bool subset = count > N;
-  if (subset) {
-    unsigned prefix = 0, pmask = 0;
-    for (int pass = 0; pass < 4; ++pass) {
-      const int shift = 24 - 8 * pass;
-      for (int i = tid; i < 256; i += kChooseThreads) hist[i] = 0;
-      __syncthreads();
-      for (int i = tid; i < count; i += kChooseThreads) {
-        const unsigned k = mix32(base + (unsigned long long)i);
-        if ((k & pmask) == prefix) atomicAdd(&hist[(k >> shift) & 255u], 1);
-      }
-      __syncthreads();
-      if (tid == 0) {
-        int acc = 0, d = 0;
-        for (; d < 256; ++d) {
-          if (acc + hist[d] >= need) break;
-          acc += hist[d];
-        }
-        sel_state[0] = d;
-        sel_state[1] = need - acc;
-      }
-      __syncthreads();
-      prefix |= (unsigned)sel_state[0] << shift;
-      pmask |= 255u << shift;
-      need = sel_state[1];
-      __syncthreads();
-    }
-    thr = prefix;  // keys < thr all taken, plus the first `need` ranks with key == thr
-  }
-
-  // pass B: selected mask pixels in row-major order
-  int rank0 = 0, tie0 = 0, out0 = 0;
-  long long* cb = choose + (size_t)b * N;
-  for (int p0 = 0; p0 < SS; p0 += kChooseThreads) {
-    const int p = p0 + tid;
-    const bool m = p < SS && mb[p] != 0;
-    int tot;
-    const int r = rank0 + block_excl_scan(m, wsum, tot);
-    rank0 += tot;
-    bool take = m, tie = false;
-    unsigned k = 0;
-    if (subset && m) {
-      k = mix32(base + (unsigned long long)r);
-      take = k < thr;
-      tie = k == thr;
-    }
-    int ttot;
-    const int tr = tie0 + block_excl_scan(tie, wsum, ttot);
-    tie0 += ttot;
-    take = take || (tie && tr < need);
-    int stot;
-    const int slot = out0 + block_excl_scan(take, wsum, stot);
-    out0 += stot;
-    if (take && slot < N) cb[slot] = p;
-  }
-  __syncthreads();
-  // wrap padding (np.pad(..., 'wrap')): slot j >= count repeats slot j % count
-  for (int j = count + tid; j < N; j += kChooseThreads) cb[j] = cb[j % count];
-  __syncthreads();
 
   // chosen pixels -> full-frame maps and the back-projected cloud, float32 arithmetic in the
   // reference's order: pt2 = depth / scale; pt0 = (x - cx) * pt2 / fx; pt1 = (y - cy) * pt2 / fy

@@ -6,7 +6,9 @@ builds the crop in numpy (`_load_data`, :603-771): square-box snap, crop, ImageN
 normalisation, mask, random `choose`, back-projected cloud. Here the box snap stays on the host
 (scalar integer logic, `get_square_bbox` below restates :890-961) and the per-pixel work runs for
 a whole bucket of equal-size crops at once in two HIP launches (krrn_crop_inputs_u8,
-krrn_choose_points). The frames live on the GPU.
+krrn_choose_points). The frames live on the GPU. `resize=T` (the reference's Data.RESIZE path, _load_resize_data
+:339-601, by this project's own definition) resamples every crop to T x T instead, in the same two
+steps (krrn_crop_inputs_resize_u8, krrn_choose_points_resize), so crops of any side share one batch.
 
 `root` = a LineMOD tree in the reference's layout (Linemod_preprocessed): per object
 `data/XX/{test,train}.txt` (image ids), `data/XX/gt.yml` (cam_R_m2c, cam_t_m2c in mm, obj_bb;
@@ -184,13 +186,22 @@ def synthetic_frames(F: int, seed: int = 0, objlist: Sequence[int] = (6,), H: in
 
 def build_inputs(frames: Dict[str, torch.Tensor], frame_idx: Sequence[int], boxes: Sequence[Tuple[int, int, int, int]],
                  num_point: int, K4: torch.Tensor, seed: torch.Tensor, stream_id: int = 0,
-                 depth_scale: float = 1.0, obj_mask: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+                 depth_scale: float = 1.0, obj_mask: Optional[torch.Tensor] = None,
+                 resize: Optional[int] = None) -> Dict[str, torch.Tensor]:
     """The per-pixel half of _load_data for crops of one size on the GPU: img_croped, choose,
-    cloud, x/y_map_choosed, plus the point mask and its pixel count per crop."""
+    cloud, x/y_map_choosed, plus the point mask and its pixel count per crop.
+    resize=T (default None: the above, unchanged) takes boxes of mixed sides and resamples every crop to T x T
+    (krrn_crop_inputs_resize_u8, krrn_choose_points_resize): the same keys at side T, x/y_map_choosed
+    the resized pixels' centres in full-frame coordinates, plus resize_scale f32 [B] = S_b / T and resize_intrinsic
+    f32 [B, 4] = (fx / s, fy / s, (cx - c0 + 0.5) / s - 0.5, (cy - r0 + 0.5) / s - 0.5), the pinhole under which the
+    crop's resized pixel indices project (the reference's key; nothing here reads it)."""
     rgb, depth, ml = frames["rgb"], frames["depth"], frames["mask_label"]
     dev = rgb.device
     F, H, W = depth.shape
     B = len(frame_idx)
+    if resize is not None:
+        return _build_inputs_resize(frames, frame_idx, boxes, num_point, K4, seed, stream_id, depth_scale, obj_mask,
+                                    int(resize))
     sizes = {rmax - rmin for rmin, rmax, _, _ in boxes} | {cmax - cmin for _, _, cmin, cmax in boxes}
     if len(sizes) != 1:
         raise ValueError(f"one crop size per batch (bucket by get_square_bbox first), got {sorted(sizes)}")
@@ -213,6 +224,61 @@ def build_inputs(frames: Dict[str, torch.Tensor], frame_idx: Sequence[int], boxe
               ptr(seed), int(stream_id), ptr(choose), ptr(cloud), ptr(xm), ptr(ym), ptr(cnt), st)
     return {"img_croped": img, "choose": choose, "cloud": cloud, "x_map_choosed": xm, "y_map_choosed": ym,
             "point_mask": mask.view(B, 1, S, S), "mask_count": cnt}
+
+
+def _build_inputs_resize(frames, frame_idx, boxes, num_point, K4, seed, stream_id, depth_scale, obj_mask,
+                         T: int) -> Dict[str, torch.Tensor]:
+    """build_inputs(resize=T): the device reads each crop's side, so the windows are checked here, from the boxes."""
+    rgb, depth, ml = frames["rgb"], frames["depth"], frames["mask_label"]
+    dev = rgb.device
+    F, H, W = depth.shape
+    B = len(frame_idx)
+    if T < 1:
+        raise ValueError(f"resize must be a positive size, got {T}")
+    if len(boxes) != B or tuple(K4.shape) != (B, 4):
+        raise ValueError(f"one box and one K4 row per crop: {B} crops, {len(boxes)} boxes, K4 {tuple(K4.shape)}")
+    for f, (rmin, rmax, cmin, cmax) in zip(frame_idx, boxes):
+        S = rmax - rmin
+        if cmax - cmin != S or not 1 <= S <= min(H, W):
+            raise ValueError(f"a resized crop's window is a square of side 1..{min(H, W)}, got box "
+                             f"{(rmin, rmax, cmin, cmax)}")
+        if rmin < 0 or cmin < 0 or rmax > H or cmax > W or not 0 <= int(f) < F:
+            raise ValueError(f"box {(rmin, rmax, cmin, cmax)} of frame {f} lies outside the {F} frames of {H} x {W}")
+    side = [b[1] - b[0] for b in boxes]
+    fi = h2d(torch.tensor(list(frame_idx), dtype=torch.int32), dev)
+    rc = h2d(torch.tensor([[b[0], b[2]] for b in boxes], dtype=torch.int32), dev)
+    sd = h2d(torch.tensor(side, dtype=torch.int32), dev)
+    img = torch.empty((B, 3, T, T), dtype=torch.float32, device=dev)
+    mask = torch.empty((B, T * T), dtype=torch.uint8, device=dev)
+    st = stream_ptr(dev)
+    _lib.call("krrn_crop_inputs_resize_u8", ptr(rgb), ptr(depth), ptr(ml), ptr(obj_mask), F, H, W, ptr(fi), ptr(rc),
+              ptr(sd), B, T, ptr(img), ptr(mask), st)
+    N = num_point
+    choose = torch.empty((B, 1, N), dtype=torch.int64, device=dev)
+    cloud = torch.empty((B, N, 3), dtype=torch.float32, device=dev)
+    xm = torch.empty((B, N, 1), dtype=torch.float32, device=dev)
+    ym = torch.empty((B, N, 1), dtype=torch.float32, device=dev)
+    cnt = torch.empty((B,), dtype=torch.int32, device=dev)
+    scale, intr = resize_intrinsic(K4, boxes, T)
+    K4 = h2d(K4, dev, torch.float32)
+    _lib.call("krrn_choose_points_resize", ptr(mask), B, T, N, ptr(depth), H, W, ptr(fi), ptr(rc), ptr(sd), ptr(K4),
+              float(depth_scale), ptr(seed), int(stream_id), ptr(choose), ptr(cloud), ptr(xm), ptr(ym), ptr(cnt), st)
+    return {"img_croped": img, "choose": choose, "cloud": cloud, "x_map_choosed": xm, "y_map_choosed": ym,
+            "point_mask": mask.view(B, 1, T, T), "mask_count": cnt,
+            "resize_scale": h2d(torch.from_numpy(scale.astype(np.float32)), dev),
+            "resize_intrinsic": h2d(torch.from_numpy(intr.astype(np.float32)), dev)}
+
+
+def resize_intrinsic(K4, boxes: Sequence[Tuple[int, int, int, int]], T: int) -> Tuple[np.ndarray, np.ndarray]:
+    """(resize_scale [B], resize_intrinsic [B, 4]) of windows `boxes` resampled to side T, in f64 on the host:
+    s = S_b / T, and resized pixel index u' = (u - c0 + 0.5) / s - 0.5 of frame pixel u, so fx' = fx / s,
+    cx' = (cx - c0 + 0.5) / s - 0.5 (rows alike)."""
+    k = torch.as_tensor(K4).detach().cpu().double().numpy().reshape(-1, 4)
+    s = np.array([(b[1] - b[0]) / float(T) for b in boxes], np.float64)
+    r0 = np.array([b[0] for b in boxes], np.float64)
+    c0 = np.array([b[2] for b in boxes], np.float64)
+    intr = np.stack([k[:, 0] / s, k[:, 1] / s, (k[:, 2] - c0 + 0.5) / s - 0.5, (k[:, 3] - r0 + 0.5) / s - 0.5], 1)
+    return s, intr
 
 
 def ply_vtx(path: str) -> np.ndarray:
@@ -386,14 +452,23 @@ class PoseDataset(torch.utils.data.Dataset):
     det_per_target="inst_count" (default "best": the above) makes one item of each of a target's `inst_count` best
     detections instead, so that an image may hold an object several times (bop_scene.BopTree). An item's GT keys are
     then a provisional association by box IoU: they feed the per-crop ADD records and the map losses only, and no
-    BOP recall reads them (evaluate.test_epoch(..., bop=True) asks for match=True on such a dataset)."""
+    BOP recall reads them (evaluate.test_epoch(..., bop=True) asks for match=True on such a dataset).
+
+    resize=T (default None: nothing changes; a multiple of 40, at least 40) resamples every crop to T x T on the GPU
+    (build_inputs(resize=T)): crop_size(i) is T for every crop, so BucketBatcher, bucket_shard, the
+    pipeline and test_epoch see one bucket, one plan and full batches whatever the boxes' sides. batch() then also
+    carries resize_scale and resize_intrinsic; `bbox` stays the source window in frame coordinates, x/y_map_choosed
+    are the resized pixels' centres in the frame, and the cloud is made of the frame's own depth pixels, so PnP,
+    verification, refinement and the result files read what they always read. Works on every layout, with or without
+    detections; refused (ValueError) with gt_maps=True: the GT maps are not resampled."""
 
     def __init__(self, mode: str = "test", num_point: int = 1000, add_noise: bool = False, root: Optional[str] = None,
                  noise_trans: float = 0.0, num_kps: int = 8, cls_type: Optional[str] = None, cfg=CONFIG,
                  num_frames: int = 256, seed: int = 0, sizes: Optional[Sequence[int]] = None,
                  n_model_pts: int = 2600, io_threads: int = 8, gt_maps: bool = False, meshes: bool = False,
                  layout: str = "linemod", split: str = "test", targets: Optional[str] = None, min_visib: float = 0.1,
-                 masks: str = "png", detections=None, det_min_score: float = 0.0, det_per_target: str = "best"):
+                 masks: str = "png", detections=None, det_min_score: float = 0.0, det_per_target: str = "best",
+                 resize: Optional[int] = None):
         if layout not in ("linemod", "bop"):
             raise ValueError(f"layout must be 'linemod' or 'bop', got {layout!r}")
         if masks not in ("png", "render"):
@@ -402,6 +477,14 @@ class PoseDataset(torch.utils.data.Dataset):
             raise ValueError("detections are BOP detection files: they need layout='bop'")
         if detections is not None and masks == "render":
             raise ValueError("detections bring their own masks: they cannot be combined with masks='render'")
+        if resize is not None:
+            if gt_maps:
+                raise ValueError("resize with gt_maps=True is not built: the GT maps are rendered at the frame's "
+                                 "resolution and are not resampled")
+            if int(resize) != resize or resize < 40 or resize % 40:
+                raise ValueError(f"resize must be a multiple of 40 that is at least 40 (the sizes the model is "
+                                 f"exercised at); other sizes are not built, got {resize!r}")
+        self.resize = None if resize is None else int(resize)
         self.layout, self.masks = layout, masks
         self.detections = detections is not None
         self.mode, self.num_point, self.cfg, self.root = mode, num_point, cfg, root
@@ -455,6 +538,9 @@ class PoseDataset(torch.utils.data.Dataset):
         return len(self.boxes)
 
     def crop_size(self, i: int) -> int:
+        """The side of crop i as the network sees it: its snapped box's, or `resize` for every crop."""
+        if self.resize is not None:
+            return self.resize
         rmin, rmax, _, _ = self.boxes[i]
         return rmax - rmin
 
@@ -607,7 +693,7 @@ class PoseDataset(torch.utils.data.Dataset):
                                frame_hw=tuple(fr["depth"].shape[1:]))
         seed, sid = self._draw_for(device)
         out = build_inputs(fr, fidx, boxes, self.num_point, K4, seed, stream_id=sid,
-                           obj_mask=maps["cover_frame"] if maps is not None else None)
+                           obj_mask=maps["cover_frame"] if maps is not None else None, resize=self.resize)
         info = self.obj_info
         ext = [np.array(info[m[0]]["size"]) / 1000.0 for m in metas]
         lfb = [np.array(info[m[0]]["min"]) / 1000.0 for m in metas]

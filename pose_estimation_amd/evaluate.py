@@ -429,7 +429,8 @@ def test_epoch(model: KRRN, dataset: PoseDataset, bs: int = 64, device=None, opt
     pixels (channel cls_id + 1 wins) into a full-frame plane and encodes it on the GPU; rank 0 builds the result rows
     exactly as `bop_csv` writes them, pairs them with the runs by crop and writes write_detections(seg_json,
     bop_scene.net_mask_rows(...)): a row's bbox is its mask's tight box, a crop without a set pixel gives no row and
-    counts as "empty". "seg" is added as above; no other key changes.
+    counts as "empty". "seg" is added as above; no other key changes. A dataset built with resize is refused
+    (ValueError): the paste does not resample. Everything else here runs on such a dataset unchanged.
     `coco` (off by default: nothing changes; needs seg_json, else ValueError, and the tree's scene_gt_coco.json, which
     bop_scene.write_gt_coco writes) scores the file just written with COCO's average precision: rank 0 adds one key,
     "coco" = bop_scene.eval_coco((root, split), the rows written, device, "segm"); no other key changes. It runs where
@@ -441,6 +442,9 @@ def test_epoch(model: KRRN, dataset: PoseDataset, bs: int = 64, device=None, opt
     if coco and not seg_json:
         raise ValueError("coco=True scores the segmentation file this epoch writes: it needs seg_json")
     if net:
+        if getattr(dataset, "resize", None) is not None:
+            raise ValueError("seg_source='net' on a dataset built with resize is not built: the paste places the "
+                             "crop's pixels one to one and does not resample them to the source window")
         if not seg_json:
             raise ValueError("seg_source='net' writes the network's masks to a file: it needs seg_json")
         _require(dataset, "seg_source='net' writes BOP's scene / image ids: it needs a PoseDataset with layout='bop'",
