@@ -524,6 +524,28 @@ int krrn_choose_points_resize(const unsigned char* mask, int B, int T, int N, co
                               const long long* seed, int stream_id, long long* choose, float* cloud, float* xmap,
                               float* ymap, int* count, void* stream);
 
+/* The zoom-in pass's windows (this project's own rule): per crop b the square window of its H x W frame
+ * that holds the projection of its model points pts f32 [B][P][3] (metres) under the pose R f64 [B][9] row-major,
+ * t f64 [B][3] and the pinhole K4 f32 [B][4], as rc int32 [B][2] = (r0, c0) and side int32 [B] = S in the form
+ * the two entry points above read from device memory, so that a pose computed on the GPU re-crops without a
+ * read-back. All f64, every product and sum rounded on its own (no FMA contraction):
+ * per point X = ((R00 x + R01 y) + R02 z) + t0, Y and Z alike, u = (fx X) / Z + cx, v = (fy Y) / Z + cy. A point is
+ * bad unless Z > 0 (NaN is not) and u and v are finite; this is tested per point, not on the extremes.
+ * status int32 [B]: 1 = some point is bad; else 2 = the projection misses the frame (umax < 0, umin > W - 1,
+ * vmax < 0 or vmin > H - 1, the extremes over the points); else 0 and
+ *   e = max(umax - umin, vmax - vmin) * pad, S = clamp(ceil(e), min_side, min(H, W)),
+ *   c0 = clamp(floor((umin + umax) * 0.5 - S * 0.5 + 1.0), 0, W - S), r0 alike from v and H,
+ * clamped in f64 before the conversion to int: the window is shifted into the frame and never shrunk. With
+ * status != 0 the window is the previous one, (rc_in [B][2], side_in [B]) copied. In every case
+ * bbox f32 [B][4] = (r0, r0 + S, c0, c0 + S), scale f32 [B] = (float)(S / T) and intr f32 [B][4] =
+ * (fx / s, fy / s, (cx - c0 + 0.5) / s - 0.5, (cy - r0 + 0.5) / s - 0.5) with s = S / T in f64 from the f32 K4, cast
+ * once: dataset.resize_intrinsic's values bit for bit. One block per crop, no atomics, no workspace; graph-capturable.
+ * 1 <= B <= 65535, P >= 1, T >= 1, H, W >= 1, 1 <= min_side <= min(H, W), pad finite and > 0 (KRRN_ESHAPE
+ * otherwise, before any launch). */
+int krrn_pose_windows_f64(const float* pts, int P, const double* R, const double* t, const float* K4, int H, int W,
+                          int T, double pad, int min_side, const int* rc_in, const int* side_in, int B, int* rc,
+                          int* side, float* bbox, float* scale, float* intr, int* status, void* stream);
+
 /* Farthest point sampling (tools/script/sample_model.py:35-48): per set b of
  * pts [B][n][3], out_idx int32 [B][n_samples] = start at 0, then repeatedly the argmax (lowest
  * index on ties) of the running min distance to the selected set; distances as numpy computes

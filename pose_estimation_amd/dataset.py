@@ -62,6 +62,7 @@ from .config import CONFIG, LM_OBJLIST, OBJ_DICT, SYM_OBJ, models_info
 from .raster import N_REGIONS, finish_maps, region_points, render_maps
 from .runtime import h2d, ptr, stream_ptr
 from .synthetic import LM_K, rand_rotation
+from .zoom import pose_windows
 
 # batchdataset.py:823
 BORDER_LIST = [-1] + list(range(40, 640, 40)) + [640]
@@ -69,6 +70,9 @@ BORDER_LIST = [-1] + list(range(40, 640, 40)) + [640]
 LM_CROP_HIST = {40: 3, 80: 3025, 120: 4889, 160: 3659, 200: 1402, 240: 403, 280: 41, 320: 3}
 # krrn_choose_points takes stream ids 0 .. 65534 (include/krrn_hip.h)
 CHOOSE_STREAMS = 65535
+# the keys PoseDataset.zoom_batch replaces (it adds zoom_status); every other key is the first batch's own tensor
+ZOOM_KEYS = ("img_croped", "choose", "cloud", "x_map_choosed", "y_map_choosed", "point_mask", "mask_count", "bbox",
+             "resize_scale", "resize_intrinsic", "zoom_rc", "zoom_side", "zoom_status")
 
 
 def get_square_bbox(bbox, height_px: int = 480, width_px: int = 640) -> Tuple[int, int, int, int]:
@@ -248,6 +252,37 @@ def _build_inputs_resize(frames, frame_idx, boxes, num_point, K4, seed, stream_i
     fi = h2d(torch.tensor(list(frame_idx), dtype=torch.int32), dev)
     rc = h2d(torch.tensor([[b[0], b[2]] for b in boxes], dtype=torch.int32), dev)
     sd = h2d(torch.tensor(side, dtype=torch.int32), dev)
+    scale, intr = resize_intrinsic(K4, boxes, T)
+    out = build_inputs_windows(frames, fi, rc, sd, num_point, K4, seed, stream_id, depth_scale, obj_mask, T)
+    out["resize_scale"] = h2d(torch.from_numpy(scale.astype(np.float32)), dev)
+    out["resize_intrinsic"] = h2d(torch.from_numpy(intr.astype(np.float32)), dev)
+    return out
+
+
+def build_inputs_windows(frames: Dict[str, torch.Tensor], fi: torch.Tensor, rc: torch.Tensor, side: torch.Tensor,
+                         num_point: int, K4: torch.Tensor, seed: torch.Tensor, stream_id: int, depth_scale: float,
+                         obj_mask: Optional[torch.Tensor], T: int) -> Dict[str, torch.Tensor]:
+    """The two launches of the resized input path (krrn_crop_inputs_resize_u8, krrn_choose_points_resize) for windows
+    that live on the device: fi int32 [B] each crop's frame, rc int32 [B, 2] = (r0, c0) and side int32 [B], GPU tensors
+    that the kernels read themselves, so windows computed on the GPU (zoom.pose_windows) feed them without a
+    read-back. No host-side window check: the kernels treat a window the frame does not hold as an empty crop (zeros,
+    an empty mask, count 0). Returns build_inputs(resize=T)'s keys at side T except resize_scale / resize_intrinsic,
+    which belong to whoever made the windows."""
+    rgb, depth, ml = frames["rgb"], frames["depth"], frames["mask_label"]
+    if not (rgb.is_cuda and depth.is_cuda and ml.is_cuda and fi.is_cuda and rc.is_cuda and side.is_cuda
+            and seed.is_cuda and (obj_mask is None or obj_mask.is_cuda)):
+        raise RuntimeError("build_inputs_windows runs on the HIP path only (the frames, fi / rc / side and the seed "
+                           "must be GPU tensors)")
+    dev = rgb.device
+    F, H, W = depth.shape
+    B = int(fi.shape[0])
+    T = int(T)
+    if T < 1:
+        raise ValueError(f"resize must be a positive size, got {T}")
+    if tuple(rc.shape) != (B, 2) or tuple(side.shape) != (B,) or tuple(K4.shape) != (B, 4):
+        raise ValueError(f"one window and one K4 row per crop: {B} crops, rc {tuple(rc.shape)}, side "
+                         f"{tuple(side.shape)}, K4 {tuple(K4.shape)}")
+    fi, rc, sd = (h2d(x, dev, torch.int32) for x in (fi, rc, side))
     img = torch.empty((B, 3, T, T), dtype=torch.float32, device=dev)
     mask = torch.empty((B, T * T), dtype=torch.uint8, device=dev)
     st = stream_ptr(dev)
@@ -259,14 +294,11 @@ def _build_inputs_resize(frames, frame_idx, boxes, num_point, K4, seed, stream_i
     xm = torch.empty((B, N, 1), dtype=torch.float32, device=dev)
     ym = torch.empty((B, N, 1), dtype=torch.float32, device=dev)
     cnt = torch.empty((B,), dtype=torch.int32, device=dev)
-    scale, intr = resize_intrinsic(K4, boxes, T)
     K4 = h2d(K4, dev, torch.float32)
     _lib.call("krrn_choose_points_resize", ptr(mask), B, T, N, ptr(depth), H, W, ptr(fi), ptr(rc), ptr(sd), ptr(K4),
               float(depth_scale), ptr(seed), int(stream_id), ptr(choose), ptr(cloud), ptr(xm), ptr(ym), ptr(cnt), st)
     return {"img_croped": img, "choose": choose, "cloud": cloud, "x_map_choosed": xm, "y_map_choosed": ym,
-            "point_mask": mask.view(B, 1, T, T), "mask_count": cnt,
-            "resize_scale": h2d(torch.from_numpy(scale.astype(np.float32)), dev),
-            "resize_intrinsic": h2d(torch.from_numpy(intr.astype(np.float32)), dev)}
+            "point_mask": mask.view(B, 1, T, T), "mask_count": cnt}
 
 
 def resize_intrinsic(K4, boxes: Sequence[Tuple[int, int, int, int]], T: int) -> Tuple[np.ndarray, np.ndarray]:
@@ -460,7 +492,8 @@ class PoseDataset(torch.utils.data.Dataset):
     carries resize_scale and resize_intrinsic; `bbox` stays the source window in frame coordinates, x/y_map_choosed
     are the resized pixels' centres in the frame, and the cloud is made of the frame's own depth pixels, so PnP,
     verification, refinement and the result files read what they always read. Works on every layout, with or without
-    detections; refused (ValueError) with gt_maps=True: the GT maps are not resampled."""
+    detections; refused (ValueError) with gt_maps=True: the GT maps are not resampled. Only such a dataset can cut
+    its crops again about an estimated pose (batch(..., zoom=True), zoom_batch; evaluate.test_epoch(..., zoom=n))."""
 
     def __init__(self, mode: str = "test", num_point: int = 1000, add_noise: bool = False, root: Optional[str] = None,
                  noise_trans: float = 0.0, num_kps: int = 8, cls_type: Optional[str] = None, cfg=CONFIG,
@@ -641,7 +674,8 @@ class PoseDataset(torch.utils.data.Dataset):
                                    "region_point": region_point}
         return self._dev_mesh[key]
 
-    def batch(self, indices: Sequence[int], device, bop: bool = False, verify: bool = False) -> Dict[str, torch.Tensor]:
+    def batch(self, indices: Sequence[int], device, bop: bool = False, verify: bool = False,
+              zoom: bool = False) -> Dict[str, torch.Tensor]:
         """The eval keys of batchdataset.py:730-771 for `indices` (one crop size), collated. With gt_maps
         also the per-pixel GT of :755-759 (xyz, normal, region, mask, multi_cls_mask), mask_obj,
         region_point, coordinate_choosed and depth_render: the object's mesh is rendered under the GT pose
@@ -651,10 +685,18 @@ class PoseDataset(torch.utils.data.Dataset):
         each crop's frame, bop_face_range / bop_vert_range / bop_sym_range int32 [B, 2] its object's ranges in
         the dataset's resident meshes and symmetry sets. The other keys are unchanged. verify=True implies the
         bop=True keys and adds verify_mask u8 [F, H, W], the mask_label frames the crops were cut from (the
-        rendered ones with masks="render"), for pose.select_pose; the crop's box is the `bbox` key."""
+        rendered ones with masks="render"), for pose.select_pose; the crop's box is the `bbox` key.
+        zoom=True (needs a dataset built with resize; ValueError otherwise) adds what zoom_batch needs to cut the crops
+        again: zoom_rgb / zoom_depth / zoom_mask the frames these crops were cut from (the decoded detection masks or
+        the rendered masks where the dataset uses those), zoom_frame int32 [B] each crop's frame, zoom_rc int32 [B, 2]
+        and zoom_side int32 [B] the windows in use, and zoom_depth_scale (a host scalar tensor). They alias bop_depth,
+        bop_frame and verify_mask where those exist. The other keys are unchanged."""
         device = torch.device(device)
         idx = list(indices)
         bop = bop or verify
+        if zoom and self.resize is None:
+            raise ValueError("zoom needs a dataset built with resize: a re-cut window has a side of its own, which "
+                             "only the resized input path takes")
         if bop and not self.meshes:
             raise ValueError("batch(..., bop=True) needs the objects' meshes: build the dataset on a LineMOD tree "
                              "with meshes=True (or gt_maps=True); root=None serves synthetic frames, which have none")
@@ -734,6 +776,37 @@ class PoseDataset(torch.utils.data.Dataset):
         if det is not None:
             out["det_score"] = h2d(torch.tensor([self.tree.items[i]["score"] for i in idx], dtype=torch.float32), device)
             out["det_info"] = det["info"]
+        if zoom:
+            out.update({"zoom_rgb": fr["rgb"], "zoom_depth": fr["depth"], "zoom_mask": fr["mask_label"],
+                        "zoom_frame": out["bop_frame"] if bop else h2d(torch.tensor(fidx, dtype=torch.int32), device),
+                        "zoom_rc": h2d(torch.tensor([[b[0], b[2]] for b in boxes], dtype=torch.int32), device),
+                        "zoom_side": h2d(torch.tensor([b[1] - b[0] for b in boxes], dtype=torch.int32), device),
+                        "zoom_depth_scale": torch.tensor(1.0, dtype=torch.float64)})  # build_inputs' default, above
+        return out
+
+    def zoom_batch(self, data: Dict[str, torch.Tensor], R: torch.Tensor, t: torch.Tensor) -> Dict[str, torch.Tensor]:
+        """The batch `data` (made with batch(..., zoom=True), or by this method) cut again about the pose estimate
+        R [B, 3, 3], t [B, 3] (GPU tensors): zoom.pose_windows turns the poses into windows on the device and
+        build_inputs_windows crops them, with a fresh draw (`_calls` advances and `_draw_for` gives the stream id, as in
+        batch()). Returns a dict like `data` with img_croped, choose, cloud, x_map_choosed, y_map_choosed, point_mask,
+        mask_count, bbox, resize_scale, resize_intrinsic, zoom_rc and zoom_side replaced and zoom_status int32 [B]
+        (zoom.pose_windows' status: a crop whose pose gives no window keeps its previous one) added; every other key
+        is `data`'s own tensor. Queued on the current stream; no host round trip."""
+        if self.resize is None:
+            raise ValueError("zoom needs a dataset built with resize")
+        if "zoom_rc" not in data:
+            raise ValueError("zoom_batch needs a batch made with dataset.batch(indices, device, zoom=True)")
+        device = data["zoom_depth"].device
+        win = pose_windows(data["model_points"], R, t, data["intrinsic"], tuple(data["zoom_depth"].shape[1:]),
+                           data["zoom_rc"], data["zoom_side"], self.resize)
+        self._calls += 1
+        seed, sid = self._draw_for(device)
+        fr = {"rgb": data["zoom_rgb"], "depth": data["zoom_depth"], "mask_label": data["zoom_mask"]}
+        out = dict(data)
+        out.update(build_inputs_windows(fr, data["zoom_frame"], win["rc"], win["side"], self.num_point,
+                                        data["intrinsic"], seed, sid, float(data["zoom_depth_scale"]), None, self.resize))
+        out.update({"bbox": win["bbox"], "resize_scale": win["resize_scale"], "resize_intrinsic": win["resize_intrinsic"],
+                    "zoom_rc": win["rc"], "zoom_side": win["side"], "zoom_status": win["status"]})
         return out
 
     def __getitem__(self, i: int) -> Dict[str, torch.Tensor]:

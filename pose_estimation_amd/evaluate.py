@@ -36,7 +36,7 @@ from .bop import BOP_REC, FRAME_W, TAUS, bop_errors, fold_bop, valid_by_crop
 from . import rle
 from .bop_scene import (_require, eval_coco, eval_results, net_mask_rows, write_detections, write_result_masks,
                         write_results)
-from .dataset import PoseDataset
+from .dataset import ZOOM_KEYS, PoseDataset
 from .krrn import KRRN
 from .loss import map_losses
 from .metric import Metric, add_metric, rt_errors
@@ -83,6 +83,14 @@ class EpochTables(NamedTuple):
         return cls(*(next(tabs) if on else None for on in (True, bop, poses, select)))
 
 
+def _check_zoom(zoom, dataset) -> None:
+    """eval_records' / test_epoch's `zoom`: a number of passes, on a dataset whose input path takes any window."""
+    if isinstance(zoom, bool) or not isinstance(zoom, (int, np.integer)) or zoom < 0:
+        raise ValueError(f"zoom is the number of extra passes, an integer >= 0, got {zoom!r}")
+    if zoom > 0 and getattr(dataset, "resize", None) is None:
+        raise ValueError("zoom needs a dataset built with resize")
+
+
 def _batches(buckets: Dict[int, List[int]], bs: int):
     for S in sorted(buckets):
         idx = buckets[S]
@@ -94,7 +102,7 @@ def _batches(buckets: Dict[int, List[int]], bs: int):
 def eval_records(model: KRRN, dataset: PoseDataset, indices: Dict[int, List[int]], bs: int, device,
                  opt_pose: bool = True, with_loss: bool = True, pose_solver: str = "pnp",
                  refine: Optional[str] = None, bop: bool = False, poses: bool = False,
-                 select: Optional[str] = None, net_masks: bool = False):
+                 select: Optional[str] = None, net_masks: bool = False, zoom: int = 0):
     """Run the eval path over {S: [crop indices]} in batches of <= bs; returns f64 [n, len(REC)]
     (rows in the order evaluated). Every batch's inputs, forward, pose and ADD(-S) are queued on
     the device without a host round trip; the per-crop records are read back once at the end (the
@@ -145,7 +153,20 @@ def eval_records(model: KRRN, dataset: PoseDataset, indices: Dict[int, List[int]
     into a plane of dataset.frame_hw, and rle.encode_gpu encodes the planes; chan and rc are built on the host. The
     runs are read back once the batch's pose step is queued (one read-back per batch, and one more encode for a
     batch in which a mask outgrows the encoder's default slot), so the planes live for one batch only. The return
-    value then ends with a list [(crop, run list, info = the mask's five ints)] in the same row order."""
+    value then ends with a list [(crop, run list, info = the mask's five ints)] in the same row order.
+
+    zoom (0 by default: no extra work is queued and every table is what it was, bit for bit; needs a dataset built
+    with resize, ValueError otherwise, and is refused together with net_masks): the number of zoom-in passes per batch
+    (DESIGN.md §3). Each takes the solver's own pose of the pass before, (base_r, pred_t) with opt_pose and (base_r,
+    base_t) without, i.e. before `refine` and `select`; cuts every crop again about that pose's projection on the pose
+    stream (dataset.zoom_batch: zoom.pose_windows, then dataset.build_inputs_windows; no read-back); runs the forward
+    again on the caller's stream, which waits for the pose stream (the next batch's inputs are still built beside it);
+    and runs the solver again. `refine`, `select`, ADD(-S), the BOP errors and the pose table read the last pass and
+    its batch dict, so select_pose sees the new `bbox`. The return value then ends with an int64 [n] array in the same
+    row order: the last pass's zoom status per crop (zoom.pose_windows), read back in the epoch's single read-back."""
+    _check_zoom(zoom, dataset)
+    if zoom and net_masks:
+        raise ValueError("zoom with net_masks is not built: the paste places the crop's pixels at dataset.boxes")
     if pose_solver not in ("pnp", "umeyama"):
         raise ValueError(f"pose_solver must be 'pnp' or 'umeyama', got {pose_solver!r}")
     if refine not in (None, "icp", "depth"):
@@ -166,6 +187,8 @@ def eval_records(model: KRRN, dataset: PoseDataset, indices: Dict[int, List[int]
     bop_pending = []   # per batch, with bop: bop_errors' dict of device tensors
     sel_pending = []   # per batch, with select: select_pose's dict of device tensors
     net = []           # with net_masks: (crop, run list, info) per crop
+    zoom_pending = []  # per batch, with zoom: the last pass's zoom_status, on the device
+    bkw = {"zoom": True} if zoom else {}
     batches = list(_batches(indices, bs))
     device = torch.device(device)
     dia = torch.tensor(dataset.diameter, dtype=torch.float32).to(device) if refine else None  # [classes], metres
@@ -177,9 +200,10 @@ def eval_records(model: KRRN, dataset: PoseDataset, indices: Dict[int, List[int]
         side.wait_stream(main)  # the inputs' pinned staging and allocations follow earlier work
         with torch.cuda.stream(side):
             if select or refine == "depth":
-                d = dataset.batch(batches[j][1], device, verify=True)
+                d = dataset.batch(batches[j][1], device, verify=True, **bkw)
             else:
-                d = dataset.batch(batches[j][1], device, bop=True) if bop else dataset.batch(batches[j][1], device)
+                d = (dataset.batch(batches[j][1], device, bop=True, **bkw) if bop else
+                     dataset.batch(batches[j][1], device, **bkw))
             ev = torch.cuda.Event()
             ev.record(side)
         return d, ev
@@ -192,6 +216,8 @@ def eval_records(model: KRRN, dataset: PoseDataset, indices: Dict[int, List[int]
             data, ev = nxt
             main.wait_event(ev)
             for v in data.values():
+                if zoom and not v.is_cuda:  # zoom_depth_scale, a host scalar
+                    continue
                 v.record_stream(main)
                 v.record_stream(pstr)
             if j + 1 < len(batches):
@@ -217,6 +243,30 @@ def eval_records(model: KRRN, dataset: PoseDataset, indices: Dict[int, List[int]
                 pred_t.record_stream(pstr)
             with torch.cuda.stream(pstr):
                 base_r, base_t = solve_pose({"xyz": xyz}, data)
+            for _ in range(zoom):
+                # cut again about the solver's own pose (pose stream), forward again (caller's stream, after the pose
+                # stream), solve again (pose stream); the side stream goes on building the next batch's inputs
+                with torch.cuda.stream(pstr):
+                    data = dataset.zoom_batch(data, base_r, pred_t if opt_pose else base_t.reshape(B, 3))
+                    cut = torch.cuda.Event()
+                    cut.record(pstr)
+                main.wait_event(cut)
+                for k in ZOOM_KEYS:  # made on the pose stream, read by the forward on the caller's
+                    data[k].record_stream(main)
+                pred = model(data["img_croped"], data["cloud"], data["choose"], data["cls_id"], opt_pose=opt_pose)
+                xyz = pred["xyz"].clone()
+                pred_t = pred["pred_t"].reshape(B, 3).clone() if opt_pose else None
+                done = torch.cuda.Event()
+                done.record(main)
+                pstr.wait_event(done)
+                xyz.record_stream(pstr)
+                if pred_t is not None:
+                    pred_t.record_stream(pstr)
+                with torch.cuda.stream(pstr):
+                    base_r, base_t = solve_pose({"xyz": xyz}, data)
+            if zoom:
+                zoom_pending.append(data["zoom_status"])
+            with torch.cuda.stream(pstr):
                 fin_r = base_r
                 r0, t0, raw_t = base_r, base_t, pred_t  # the solver's and TBase's own, before any refinement
                 if refine:
@@ -259,6 +309,8 @@ def eval_records(model: KRRN, dataset: PoseDataset, indices: Dict[int, List[int]
     for e in bop_pending + sel_pending:
         for t in e.values():
             t.record_stream(main)
+    for t in zoom_pending:
+        t.record_stream(main)
     # one read-back and one vectorised host pass for the whole epoch: per batch, the rotation /
     # translation errors' six small copies and ~60 CPU ops ran after the GPU had drained (a serial
     # host tail of ~1 ms per batch); every quantity is per crop, so the values are the same
@@ -299,6 +351,9 @@ def eval_records(model: KRRN, dataset: PoseDataset, indices: Dict[int, List[int]
     tabs = EpochTables(*(None if t is None else torch.from_numpy(t) for t in (rec, brec, prec, srec))).legacy()
     if net_masks:
         return (tabs if isinstance(tabs, tuple) else (tabs,)) + (net,)
+    if zoom:
+        zstat = torch.cat(zoom_pending).cpu().numpy().astype(np.int64) if zoom_pending else np.zeros(0, np.int64)
+        return (tabs if isinstance(tabs, tuple) else (tabs,)) + (zstat,)
     return tabs
 
 
@@ -387,7 +442,7 @@ def test_epoch(model: KRRN, dataset: PoseDataset, bs: int = 64, device=None, opt
                group=None, pose_solver: str = "pnp", refine: Optional[str] = None,
                bop: bool = False, bop_csv: Optional[str] = None, select: Optional[str] = None,
                match: bool = False, seg_json: Optional[str] = None, seg_source: str = "render",
-               coco: bool = False) -> Dict[str, object]:
+               coco: bool = False, zoom: int = 0) -> Dict[str, object]:
     """Trainer.test_epoch over `dataset`. world/rank default to the initialised process group
     (1/0 without one). `criterion` enables the per-crop map-loss terms (dis_xyz / dis_mask /
     dis_normal) when the batches carry GT maps, i.e. for a PoseDataset built with gt_maps=True (a
@@ -434,8 +489,17 @@ def test_epoch(model: KRRN, dataset: PoseDataset, bs: int = 64, device=None, opt
     `coco` (off by default: nothing changes; needs seg_json, else ValueError, and the tree's scene_gt_coco.json, which
     bop_scene.write_gt_coco writes) scores the file just written with COCO's average precision: rank 0 adds one key,
     "coco" = bop_scene.eval_coco((root, split), the rows written, device, "segm"); no other key changes. It runs where
-    seg_json runs: the ranks' run lists are not gathered."""
+    seg_json runs: the ranks' run lists are not gathered.
+    `zoom` (0 by default: nothing changes, bit for bit; an integer >= 0, on a dataset built with resize, with
+    world == 1; ValueError otherwise, before any batch is built) is the number of zoom-in passes of eval_records:
+    every crop is cut again about its estimated pose's projection and the network runs again, `zoom` times, and
+    every key above is computed from the last pass. One key is added, "zoom": {"passes": zoom, "recropped" the crops
+    whose last pass cut a new window (zoom.pose_windows' status 0), "kept_bad_pose" those that kept their window because
+    the pose put a point behind the camera or at a non-finite pixel (status 1), "kept_outside" those whose projection
+    missed the frame (status 2)}. Whether the extra passes improve any accuracy figure is unmeasured.
+    seg_source="net" is refused on every dataset built with resize, so it never meets zoom."""
     device = torch.device(device) if device is not None else next(model.parameters()).device
+    _check_zoom(zoom, dataset)
     if seg_source not in ("render", "net"):
         raise ValueError(f"seg_source must be 'render' or 'net', got {seg_source!r}")
     net = seg_source == "net"
@@ -470,12 +534,18 @@ def test_epoch(model: KRRN, dataset: PoseDataset, bs: int = 64, device=None, opt
         raise ValueError(f"rank {rank} outside world {world}")
     if net and world > 1:
         raise ValueError("seg_source='net' runs on one rank: gathering the ranks' run lists is not built")
+    if zoom and world > 1:
+        raise ValueError("zoom runs on one rank: it is not tested across ranks, and the status counts are not gathered")
     sizes = [dataset.crop_size(i) for i in range(len(dataset))]
     mine = kd.bucket_shard(sizes, world, rank)
     want_poses = bool(bop_csv or match or seg_json)
+    zkw = {"zoom": int(zoom)} if zoom else {}
     ret = eval_records(model, dataset, mine, bs, device, opt_pose=opt_pose, with_loss=criterion is not None,
                        pose_solver=pose_solver, refine=refine, bop=bool(bop), poses=want_poses, select=select,
-                       net_masks=net)
+                       net_masks=net, **zkw)
+    zstat = None
+    if zoom:
+        zstat, ret = ret[-1], ret[:-1]
     net_runs = {}
     if net:
         net_runs = {crop: (runs, info) for crop, runs, info in ret[-1]}
@@ -485,6 +555,9 @@ def test_epoch(model: KRRN, dataset: PoseDataset, bs: int = 64, device=None, opt
     gather = lambda t: gather_epoch_records(t, shard_sizes, device, group) if world > 1 else t  # noqa: E731
     metric = Metric(dataset.sym_obj)
     out = fold_records(gather(local.rec), dataset.objlist, dataset.diameter, opt_pose, metric)
+    if zoom:
+        out["zoom"] = {"passes": int(zoom), "recropped": int((zstat == 0).sum()),
+                       "kept_bad_pose": int((zstat == 1).sum()), "kept_outside": int((zstat == 2).sum())}
     det = bool(getattr(dataset, "detections", False))  # a detection-mode dataset: targets without an estimate count
     missed: Dict[int, int] = {}
     for _, _, obj in (dataset.tree.missed if det else ()):
