@@ -208,12 +208,18 @@ int krrn_conv3x3_wino_x3_f32(const float* in, int in_cs, int in_co, int B, int H
  * wino4_weights' U = G g G^T ([cin/8][36][N][8] f32, element xi = 6u + v) split on the host
  * (wino_weights_x3): plane U_mh [cin/8][36][N][2][8] bf16 then plane U_l [cin/8][36][N][2][4]
  * bf16. cin a multiple of 8; in 16-byte aligned with in_cs, in_co multiples of 4; other arguments
- * as krrn_conv3x3_wino_x3_f32 (any out / res channel alignment). */
+ * as krrn_conv3x3_wino_x3_f32 (any out / res channel alignment).
+ * `relu` holds flags: bit 0 = ReLU; bit 1 = `in` is the half-resolution source of
+ * UpsamplingBilinear2d(2) (align_corners = True, krrn.py:56, 78): [B][H / 2][W / 2][in_cs], and the conv
+ * reads its x2 bilinear upsample, which is never formed (the interpolation is folded into the input
+ * transform: V = (B^T Ly) X (B^T Lx)^T over the 4 x 4 source pixels X a 6 x 6 patch touches). H, W stay
+ * the conv's own size and must be even with bit 1 set; any other bit, or an odd size: KRRN_ESHAPE.
+ * Callers passing 0 or 1 get the plain conv. */
 int krrn_conv3x3_wino4_x3_f32(const float* in, int in_cs, int in_co, int B, int H, int W, int cin, const void* U3,
                               int N, int n_store, const float* scale, const float* bias, const float* res, int res_cs,
                               int res_co, float* out, int out_cs, int out_co, int relu, void* stream);
 /* krrn_conv3x3_wino_x3_head_f32 on the F(4x4, 3x3) kernel (U3 as krrn_conv3x3_wino4_x3_f32; cin a
- * multiple of 8, in 16-byte aligned with in_cs, in_co multiples of 4). */
+ * multiple of 8, in 16-byte aligned with in_cs, in_co multiples of 4; `relu` holds the same flags). */
 int krrn_conv3x3_wino4_x3_head_f32(const float* in, int in_cs, int in_co, int B, int H, int W, int cin,
                                    const void* U3, int N, const float* scale, const float* bias, const float* res,
                                    int res_cs, int res_co, int relu, const float* w1, const float* b1, int p1,

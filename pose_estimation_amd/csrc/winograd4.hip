@@ -73,6 +73,18 @@ constexpr int kOffL = 2 * kVMH * 4;              // 73728
 constexpr int kOffR = kOffL + 2 * kVL * 4;       // 110592
 constexpr int kLdsBytes = kOffR + 2 * kRingF * 4;  // 159744
 static_assert(36 * 16 * kET <= kLdsBytes, "epilogue (16 tiles) fits the LDS");
+// UP form (the input is the half-resolution source of UpsamplingBilinear2d(2), align_corners = True): the
+// block is 32 x 1 tiles (128 x 4 output pixels), so the 6 patch rows of every tile are the same 24
+// wave-uniform coefficients of 4 source rows. The ring holds the block's SOURCE window, 4 rows x up to 66
+// columns x 2 channel halves (the patch origins of tiles 31 apart lie < 62 source columns apart, a patch
+// side touches 4), in slot 2 col + col / 2 + h of a row: consecutive tiles' windows start 2 columns = 5
+// slots apart, and 5 t mod 16 is distinct over each 16-lane group of a ds_read_b128 (a tile off that
+// progression, such as tile 0 of a row, whose window starts at column 0 and not -1, can meet one other lane
+// of its group: measured in DESIGN.md section 3).
+constexpr int kUGX = 32, kUGY = 1;
+constexpr int kUR = 4, kUC = 66;                  // source rows / columns of a block's window
+constexpr int kURS = 168;                         // 16-B slots per source row
+static_assert(kUGX * kUGY == kT && 2 * (kUC - 1) + (kUC - 1) / 2 + 1 < kURS && kUR * kURS <= 2 * 512, "source window");
 
 struct Wino4Args {
   const float* in;
@@ -150,7 +162,7 @@ __device__ __forceinline__ constexpr bool at_uses(int u) {
 
 // epilogue: output row I of local tile tl (of the pass's 16), channels ng .. ng + 3;
 // E = [36][16 tiles][64 n] f32
-template <int I, int HP>
+template <int I, int HP, bool UP>
 __device__ __forceinline__ void epi_row(const Wino4Args& a, const char* E, int nq, int tl, int pass, int b, int ty0,
                                         int tx0, int ng, int nb) {
   const char* eb = E + tl * kET + nq * 16;
@@ -170,7 +182,7 @@ __device__ __forceinline__ void epi_row(const Wino4Args& a, const char* E, int n
   y[2] = at_row<2>(t);
   y[3] = at_row<3>(t);
   const int tile = 16 * pass + tl;
-  const int ty = ty0 + (tile >> 4), tx = tx0 + (tile & 15);
+  const int ty = UP ? ty0 : ty0 + (tile >> 4), tx = UP ? tx0 + tile : tx0 + (tile & 15);
   const int oy = 4 * ty + I;
   const int nj = min(4, a.W - 4 * tx);  // output columns of this tile inside the image
   if constexpr (HP > 0) {
@@ -280,28 +292,104 @@ __global__ __launch_bounds__(256) void wino4_head_finish_kernel(const float* __r
     if (o < p1) out[(b * out_c + o) * HW + p] = v[o] + (b1 ? b1[o] : 0.f);
 }
 
-template <int HP>  // 0: conv output stored; 1..4: head form, HP rows of w1
+// UP: the patch d = Ly X Lx^T is linear in the 4 x 4 source pixels X it touches, so
+// V = B^T d B = (B^T Ly) X (B^T Lx)^T = Cy X Cx^T: no upsampled value is ever formed.
+// c[j] = sum over the 6 patch positions p (destination index 4 t - 1 + p, zero outside [0, n_out)) of
+// bt[p] times the weight krrn_src_index gives source pixel base + j there; base = the source index of the
+// first patch position inside the map. A weight whose source falls outside base .. base + 3 would be
+// dropped: it does not happen for 2 n_in = n_out (tests/test_wino4_up2_taps_host.py).
+__device__ __forceinline__ int up_base(int t, int n_in, float sc) {
+  int i0, i1;
+  float l0, l1;
+  krrn_src_index(max(4 * t - 1, 0), n_in, sc, 1, i0, i1, l0, l1);
+  return i0;
+}
+__device__ __forceinline__ void up_coefs(const float (&bt)[6], int t, int n_in, int n_out, float sc, float (&c)[4]) {
+  const int base = up_base(t, n_in, sc);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) c[j] = 0.f;
+#pragma unroll
+  for (int p = 0; p < 6; ++p) {
+    const int x = 4 * t - 1 + p;
+    int i0, i1;
+    float l0, l1;
+    krrn_src_index(min(max(x, 0), n_out - 1), n_in, sc, 1, i0, i1, l0, l1);
+    const bool in = x >= 0 && x < n_out;
+    const float w0 = in ? bt[p] * l0 : 0.f, w1 = in ? bt[p] * l1 : 0.f;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) c[j] += (i0 - base == j ? w0 : 0.f) + (i1 - base == j ? w1 : 0.f);
+  }
+}
+// row k of B^T
+__device__ __forceinline__ void bt_coefs(int k, float (&b)[6]) {
+  switch (k) {
+    case 0: b[0] = 4.f; b[1] = 0.f; b[2] = -5.f; b[3] = 0.f; b[4] = 1.f; b[5] = 0.f; break;
+    case 1: b[0] = 0.f; b[1] = -4.f; b[2] = -4.f; b[3] = 1.f; b[4] = 1.f; b[5] = 0.f; break;
+    case 2: b[0] = 0.f; b[1] = 4.f; b[2] = -4.f; b[3] = -1.f; b[4] = 1.f; b[5] = 0.f; break;
+    case 3: b[0] = 0.f; b[1] = -2.f; b[2] = -1.f; b[3] = 2.f; b[4] = 1.f; b[5] = 0.f; break;
+    case 4: b[0] = 0.f; b[1] = 2.f; b[2] = -1.f; b[3] = -2.f; b[4] = 1.f; b[5] = 0.f; break;
+    default: b[0] = 0.f; b[1] = 4.f; b[2] = 0.f; b[3] = -5.f; b[4] = 0.f; b[5] = 1.f; break;
+  }
+}
+
+// HP 0: conv output stored; 1..4: head form, HP rows of w1. UP: a.in is the (H / 2) x (W / 2) source of the
+// x2 bilinear upsample (align_corners) this conv reads; a.H, a.W stay the conv's own size.
+template <int HP, bool UP>
 __global__ __launch_bounds__(512, 1) void wino_f43_x3_kernel(const Wino4Args a) {
   __shared__ __attribute__((aligned(16))) char smem[kLdsBytes];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int gxn = krrn_cdiv(a.Wt, kGX), gyn = krrn_cdiv(a.Ht, kGY), nbn = krrn_cdiv(a.N, kN);
+  constexpr int GX = UP ? kUGX : kGX, GY = UP ? kUGY : kGY;
+  const int gxn = krrn_cdiv(a.Wt, GX), gyn = krrn_cdiv(a.Ht, GY), nbn = krrn_cdiv(a.N, kN);
   const int per_img = gxn * gyn;
   const int bid = krrn_xcd_remap(blockIdx.x, a.B * per_img * nbn);
   const int sp = bid / nbn, nb = bid - (bid / nbn) * nbn;
   const int b = sp / per_img, r2 = sp - (sp / per_img) * per_img;
   const int by = r2 / gxn, bx = r2 - (r2 / gxn) * gxn;
   const int n0 = nb * kN;
-  const int ty0 = by * kGY, tx0 = bx * kGX;
+  const int ty0 = by * GY, tx0 = bx * GX;
   const int nck = a.cin / kC;
 
   // raw staging: this thread's 3 ring slots t, t + 512, t + 1024 (padding slots load zeros)
   const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc(
       (void*)(a.in + (size_t)b * a.img + a.in_co), (short)0, (int)min(a.img * 4 - (long long)a.in_co * 4, 0x7FFFFFFFLL),
       0x00020000);
-  unsigned roff[3];
+  // UP: the coefficients first (VALU only), before anything the hand-counted vmcnt waits below count
+  constexpr int ND = UP ? 2 : 3;  // LDS-DMA instructions per wave and chunk
+  const int Hi = a.H >> 1, Wi = a.W >> 1;
+  float ucx[4];     // Cx: row tv of B^T Lx for this lane's tile column (set below, with tv)
+  float ucy[6][4];  // Cy = B^T Ly for the block's tile row: wave-uniform, held in SGPRs
+  int urow0 = 0, ucol0 = 0;  // the window's first source row / column
+  float usw = 0.f;
+  if constexpr (UP) {
+    const float ush = (float)(Hi - 1) / (float)(a.H - 1);  // krrn_resize_bilinear_f32's align_corners scale
+    usw = (float)(Wi - 1) / (float)(a.W - 1);
+    urow0 = up_base(ty0, Hi, ush);
+    ucol0 = up_base(tx0, Wi, usw);
 #pragma unroll
-  for (int i = 0; i < 3; ++i) {
+    for (int u = 0; u < 6; ++u) {
+      float bt[6], c[4];
+      bt_coefs(u, bt);
+      up_coefs(bt, ty0, Hi, a.H, ush, c);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) ucy[u][i] = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(c[i])));
+    }
+  }
+  unsigned roff[3];
+  if constexpr (UP) {
+#pragma unroll
+    for (int i = 0; i < ND; ++i) {
+      const int s = 64 * ND * wave + 64 * i + lane;
+      const int r = s / kURS, q = s - (s / kURS) * kURS;
+      const int g5 = q / 5, w5 = q - (q / 5) * 5;
+      const int col = 2 * g5 + (w5 >> 1), hh = w5 & 1;
+      const int iy = urow0 + r, ix = ucol0 + col;
+      const bool ok = r < kUR && w5 < 4 && col < kUC && iy < Hi && ix < Wi;
+      roff[i] = ok ? (unsigned)((((long long)iy * Wi + ix) * a.in_cs + 4 * hh) * 4) : kOOB;
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < (UP ? 0 : 3); ++i) {
     const int s = 192 * wave + 64 * i + lane;  // LDS-DMA: wave instruction i fills slots 64 (3 wave + i) ..
     const int r = s / kRS, q = s - (s / kRS) * kRS;
     const int g4 = q / 9, w9 = q - (q / 9) * 9;
@@ -313,9 +401,9 @@ __global__ __launch_bounds__(512, 1) void wino_f43_x3_kernel(const Wino4Args a) 
   // raw chunk ck straight into ring slot `slot` by LDS-DMA (buffer_load_dwordx4 ... lds: 1 KB per
   // wave instruction, no staging registers); padding slots receive zeros
   auto dma_raw = [&](int ck, int slot) {
-    char* dst = smem + kOffR + slot * (kRingF * 4) + 3 * 1024 * wave;
+    char* dst = smem + kOffR + slot * (kRingF * 4) + ND * 1024 * wave;
 #pragma unroll
-    for (int i = 0; i < 3; ++i)
+    for (int i = 0; i < ND; ++i)
       __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (__attribute__((address_space(3))) void*)(dst + 1024 * i), 16,
                                                roff[i], ck * kC * 4, 0, 0);
   };
@@ -365,7 +453,18 @@ __global__ __launch_bounds__(512, 1) void wino_f43_x3_kernel(const Wino4Args a) 
     default: tcol[0] = 1; tcol[1] = 3; tcol[2] = 5; tcol[3] = 5; tk[0] = 4.f; tk[1] = -5.f; tk[2] = 1.f; tk[3] = 0.f; break;
   }
   const int ttile = lane & 31, th = lane >> 5;
-  const int pbase = (4 * (ttile >> 4)) * kRS + 9 * (ttile & 15) + th;  // patch origin slot
+  int pbase = (4 * (ttile >> 4)) * kRS + 9 * (ttile & 15) + th;  // patch origin slot
+  int podd = 0;
+  if constexpr (UP) {
+    // this lane's 4 source columns start at co of the window (tiles past the map: all-zero coefficients,
+    // any in-window address does); slots of co .. co + 3: +0, +2 + odd, +5, +7 + odd
+    float bt[6];
+    bt_coefs(tv, bt);
+    up_coefs(bt, tx0 + ttile, Wi, a.W, usw, ucx);
+    const int co = min(up_base(tx0 + ttile, Wi, usw) - ucol0, kUC - 4);
+    pbase = 2 * co + (co >> 1) + th;
+    podd = co & 1;
+  }
   const char* tb[4];       // this chunk's tap columns in the ring slot the transform reads
   char* twm = nullptr;     // this lane's V entry of component tv (plane MH)
   char* twl = nullptr;     // (plane L)
@@ -374,8 +473,15 @@ __global__ __launch_bounds__(512, 1) void wino_f43_x3_kernel(const Wino4Args a) 
   auto t_begin = [&](int ck) {  // transform of chunk ck: addresses, and patch row 0's reads
     const int p = ck & 1;
     const char* rb = smem + kOffR + p * (kRingF * 4) + 16 * pbase;
+    if constexpr (UP) {
+      tb[0] = rb;
+      tb[1] = rb + 16 * (2 + podd);
+      tb[2] = tb[0] + 16 * 5;
+      tb[3] = tb[1] + 16 * 5;
+    } else {
 #pragma unroll
-    for (int t = 0; t < 4; ++t) tb[t] = rb + 16 * (2 * tcol[t] + (tcol[t] >> 2));
+      for (int t = 0; t < 4; ++t) tb[t] = rb + 16 * (2 * tcol[t] + (tcol[t] >> 2));
+    }
     twm = smem + p * (kVMH * 4) + tv * 1024 + 16 * lane;
     twl = smem + kOffL + p * (kVL * 4) + tv * 512 + 8 * lane;
 #pragma unroll
@@ -383,6 +489,28 @@ __global__ __launch_bounds__(512, 1) void wino_f43_x3_kernel(const Wino4Args a) 
   };
   // step s < 6: e[s] from row s's taps, then row s + 1's reads; step 6 + u: output u
   auto t_step = [&](int s) {
+    if constexpr (UP) {
+      // steps 0..3: e[i] = sum_j cx[j] X[i][j] of source row i; step 4 + u: V[u][tv] = sum_i cy[u][i] e[i]
+      if (s < 4) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+          te[s][e] = __builtin_fmaf(ucx[3], td[3][e], __builtin_fmaf(ucx[2], td[2][e], __builtin_fmaf(ucx[1], td[1][e], ucx[0] * td[0][e])));
+        if (s < 3) {
+#pragma unroll
+          for (int t = 0; t < 4; ++t) td[t] = *reinterpret_cast<const f32x4*>(tb[t] + (s + 1) * kURS * 16);
+        }
+        return;
+      }
+      const int u = s - 4;
+      f32x4 x;
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        x[e] = __builtin_fmaf(ucy[u][3], te[3][e], __builtin_fmaf(ucy[u][2], te[2][e], __builtin_fmaf(ucy[u][1], te[1][e], ucy[u][0] * te[0][e])));
+      const u32x6 ch = split3(x);
+      *reinterpret_cast<u32x4*>(twm + 6 * u * 1024) = u32x4{ch[0], ch[1], ch[2], ch[3]};
+      *reinterpret_cast<u32x2*>(twl + 6 * u * 512) = u32x2{ch[4], ch[5]};
+      return;
+    }
     if (s < 6) {
 #pragma unroll
       for (int e = 0; e < 4; ++e)
@@ -413,7 +541,9 @@ __global__ __launch_bounds__(512, 1) void wino_f43_x3_kernel(const Wino4Args a) 
     *reinterpret_cast<u32x2*>(twl + 6 * u * 512) = u32x2{ch[4], ch[5]};
   };
   // which transform steps run after component k's MFMAs (the VALU work beside the matrix pipe)
-  constexpr int kStep0[10] = {0, 1, 2, 3, 4, 5, 7, 9, 11, 12};  // steps kStep0[k] .. kStep0[k + 1] - 1
+  // steps kStep0[k] .. kStep0[k + 1] - 1 (UP: 4 source rows, then the 6 outputs)
+  constexpr int kStep0[10] = {0, 1, 2, 3, 4, 5, UP ? 6 : 7, UP ? 8 : 9, UP ? 9 : 11, UP ? 10 : 12};
+  constexpr int kSteps = UP ? 10 : 12;
 
   auto comp_of = [&](int k) { return 6 * (cu0 + k / 3) + cv0 + k % 3; };
   // one chunk: M(ck) on V[ck & 1], interleaved with T(ck + 1) into V[(ck + 1) & 1]; the raw input
@@ -472,13 +602,13 @@ __global__ __launch_bounds__(512, 1) void wino_f43_x3_kernel(const Wino4Args a) 
 #pragma unroll
   for (int k = 0; k < 3; ++k) load_w(0, k);
   if (nck > 1)
-    asm volatile("s_waitcnt vmcnt(9)\n\ts_barrier" ::: "memory");
+    asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(ND + 6) : "memory");
   else
     asm volatile("s_waitcnt vmcnt(6)\n\ts_barrier" ::: "memory");
   if (wave < 6) {
     t_begin(0);
 #pragma unroll
-    for (int st = 0; st < 12; ++st) t_step(st);
+    for (int st = 0; st < kSteps; ++st) t_step(st);
   }
   asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)\n\ts_barrier" ::: "memory");
 
@@ -514,10 +644,10 @@ __global__ __launch_bounds__(512, 1) void wino_f43_x3_kernel(const Wino4Args a) 
       const int tl = 4 * ((wave >> 2) + 2 * it) + etl;
       const int ng = n0 + 4 * enq;
       switch (ei) {
-        case 0: epi_row<0, HP>(a, smem, enq, tl, pass, b, ty0, tx0, ng, nb); break;
-        case 1: epi_row<1, HP>(a, smem, enq, tl, pass, b, ty0, tx0, ng, nb); break;
-        case 2: epi_row<2, HP>(a, smem, enq, tl, pass, b, ty0, tx0, ng, nb); break;
-        default: epi_row<3, HP>(a, smem, enq, tl, pass, b, ty0, tx0, ng, nb); break;
+        case 0: epi_row<0, HP, UP>(a, smem, enq, tl, pass, b, ty0, tx0, ng, nb); break;
+        case 1: epi_row<1, HP, UP>(a, smem, enq, tl, pass, b, ty0, tx0, ng, nb); break;
+        case 2: epi_row<2, HP, UP>(a, smem, enq, tl, pass, b, ty0, tx0, ng, nb); break;
+        default: epi_row<3, HP, UP>(a, smem, enq, tl, pass, b, ty0, tx0, ng, nb); break;
       }
     }
     __syncthreads();
@@ -535,12 +665,14 @@ KRRN_API int krrn_conv3x3_wino4_x3_f32(const float* in, int in_cs, int in_co, in
   if (cin < kC || (cin % kC) || in_co + cin > in_cs) return KRRN_EALIGN;
   if (!krrn_aligned16(U3) || (((uintptr_t)in) & 15u) || (in_cs & 3) || (in_co & 3)) return KRRN_EALIGN;
   if (out_co + n_store > out_cs) return KRRN_ESHAPE;
+  const bool up = relu & 2;  // `in` is the (H / 2) x (W / 2) source of the x2 upsample
+  if ((relu & ~3) || (up && ((H | W) & 1))) return KRRN_ESHAPE;
   Wino4Args a;
   a.in = in; a.in_cs = in_cs; a.in_co = in_co; a.B = B; a.H = H; a.W = W; a.cin = cin;
-  a.img = (long long)H * W * in_cs;
+  a.img = up ? (long long)(H / 2) * (W / 2) * in_cs : (long long)H * W * in_cs;
   a.U3 = U3; a.N = N; a.n_store = n_store; a.scale = scale; a.bias = bias;
   a.res = res; a.res_cs = res_cs; a.res_co = res_co;
-  a.out = out; a.out_cs = out_cs; a.out_co = out_co; a.relu = relu;
+  a.out = out; a.out_cs = out_cs; a.out_co = out_co; a.relu = relu & 1;
   a.Ht = (H + 3) / 4; a.Wt = (W + 3) / 4;
   const bool ov = !(out_cs & 3) && !(out_co & 3) && krrn_aligned16(out);
   const bool rv = !res || (!(res_cs & 3) && !(res_co & 3) && krrn_aligned16(res));
@@ -550,9 +682,10 @@ KRRN_API int krrn_conv3x3_wino4_x3_f32(const float* in, int in_cs, int in_co, in
   // 32-bit buffer offsets: one image, and the MH plane (records x 16 B)
   const long long nrec = (long long)(cin / kC) * 36 * N * 2;
   if (a.img * 4 >= 0x7FFF0000LL || nrec * 16 >= 0x7FFF0000LL) return KRRN_ESHAPE;
-  const long long rb = (long long)B * krrn_cdiv(a.Ht, kGY) * krrn_cdiv(a.Wt, kGX) * krrn_cdiv(N, kN);
+  const long long rb = (long long)B * krrn_cdiv(a.Ht, up ? kUGY : kGY) * krrn_cdiv(a.Wt, up ? kUGX : kGX) * krrn_cdiv(N, kN);
   if (rb > 0x7fffffffLL) return KRRN_ESHAPE;
-  hipLaunchKernelGGL(wino_f43_x3_kernel<0>, dim3((unsigned)rb), dim3(512), 0, (hipStream_t)stream, a);
+  if (up) hipLaunchKernelGGL((wino_f43_x3_kernel<0, true>), dim3((unsigned)rb), dim3(512), 0, (hipStream_t)stream, a);
+  else hipLaunchKernelGGL((wino_f43_x3_kernel<0, false>), dim3((unsigned)rb), dim3(512), 0, (hipStream_t)stream, a);
   return krrn_launch_status();
 }
 
@@ -568,25 +701,29 @@ KRRN_API int krrn_conv3x3_wino4_x3_head_f32(const float* in, int in_cs, int in_c
   if (!krrn_aligned16(w1) || !krrn_aligned16(part)) return KRRN_EALIGN;
   if ((scale && !krrn_aligned16(scale)) || (bias && !krrn_aligned16(bias))) return KRRN_EALIGN;
   if (res && ((res_cs & 3) || (res_co & 3) || !krrn_aligned16(res))) return KRRN_EALIGN;
+  const bool up = relu & 2;  // as in krrn_conv3x3_wino4_x3_f32
+  if ((relu & ~3) || (up && ((H | W) & 1))) return KRRN_ESHAPE;
   Wino4Args a;
   a.in = in; a.in_cs = in_cs; a.in_co = in_co; a.B = B; a.H = H; a.W = W; a.cin = cin;
-  a.img = (long long)H * W * in_cs;
+  a.img = up ? (long long)(H / 2) * (W / 2) * in_cs : (long long)H * W * in_cs;
   a.U3 = U3; a.N = N; a.n_store = N; a.scale = scale; a.bias = bias;
   a.res = res; a.res_cs = res_cs; a.res_co = res_co;
-  a.out = nullptr; a.out_cs = 0; a.out_co = 0; a.relu = relu; a.vec = 1;
+  a.out = nullptr; a.out_cs = 0; a.out_co = 0; a.relu = relu & 1; a.vec = 1;
   a.Ht = (H + 3) / 4; a.Wt = (W + 3) / 4;
   a.w1 = w1; a.part = part;
   const long long nrec = (long long)(cin / kC) * 36 * N * 2;
   if (a.img * 4 >= 0x7FFF0000LL || nrec * 16 >= 0x7FFF0000LL) return KRRN_ESHAPE;
   const int nbn = krrn_cdiv(N, kN);
-  const long long rb = (long long)B * krrn_cdiv(a.Ht, kGY) * krrn_cdiv(a.Wt, kGX) * nbn;
+  const long long rb = (long long)B * krrn_cdiv(a.Ht, up ? kUGY : kGY) * krrn_cdiv(a.Wt, up ? kUGX : kGX) * nbn;
   const long long M = (long long)B * H * W;
   const long long fb = (M + 255) / 256;
   if (rb > 0x7fffffffLL || fb > 0x7fffffffLL) return KRRN_ESHAPE;
   hipStream_t s = (hipStream_t)stream;
   // p1 <= 3 (nml_final of one class) forms 3 dot products per pixel, p1 = 4 all four
-  if (p1 <= 3) hipLaunchKernelGGL(wino_f43_x3_kernel<3>, dim3((unsigned)rb), dim3(512), 0, s, a);
-  else hipLaunchKernelGGL(wino_f43_x3_kernel<4>, dim3((unsigned)rb), dim3(512), 0, s, a);
+  if (p1 <= 3 && up) hipLaunchKernelGGL((wino_f43_x3_kernel<3, true>), dim3((unsigned)rb), dim3(512), 0, s, a);
+  else if (p1 <= 3) hipLaunchKernelGGL((wino_f43_x3_kernel<3, false>), dim3((unsigned)rb), dim3(512), 0, s, a);
+  else if (up) hipLaunchKernelGGL((wino_f43_x3_kernel<4, true>), dim3((unsigned)rb), dim3(512), 0, s, a);
+  else hipLaunchKernelGGL((wino_f43_x3_kernel<4, false>), dim3((unsigned)rb), dim3(512), 0, s, a);
   const int st = krrn_launch_status();
   if (st != KRRN_OK) return st;
   hipLaunchKernelGGL(wino4_head_finish_kernel, dim3((unsigned)fb), dim3(256), 0, s, part, nbn, M, H * W, b1, p1, out,

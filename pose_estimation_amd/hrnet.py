@@ -214,20 +214,35 @@ class _Builder:
         t = self.plan.buf((self.B, H, W, cs))
         return Act(t, self.B, H, W, cs, 0, c)
 
+    def up2_view(self, x: Act, spec) -> Optional[Act]:
+        """x as the conv after UpsamplingBilinear2d(2) sees it, without the upsampled map: the same buffer
+        with the doubled size, for the F(4x4) Winograd launch that reads the half-resolution source (bit 1
+        of its `relu` flags). None where that conv does not take the F(4x4) path at the doubled size."""
+        v = Act(x.t, x.B, 2 * x.H, 2 * x.W, x.cs, x.co, x.c)
+        if ops.wino_eligible(spec, v.B * v.H * v.W) and ops.wino4_eligible(spec, v, v.H, v.W):
+            return v
+        return None
+
     def conv(self, x: Act, conv: nn.Module, bn: Optional[nn.Module], out: Optional[Act] = None,
-             res: Optional[Act] = None, relu: bool = False, cin_map=None) -> Act:
+             res: Optional[Act] = None, relu: bool = False, cin_map=None, up2: bool = False) -> Act:
+        """up2: the conv reads UpsamplingBilinear2d(2)(x): inside the F(4x4) launch where that runs
+        (up2_view), else from the materialised map (upsample2)."""
         if isinstance(conv, nn.ConvTranspose2d):
             spec = ops.make_convT(conv, bn, self.dev, cin_map=cin_map, cin_p=x.cp)
         else:
             spec = ops.make_conv(conv, bn, self.dev, cin_map=cin_map, cin_p=x.cp)
         self.specs.append(spec)
+        if up2:
+            v = self.up2_view(x, spec)
+            up2 = v is not None
+            x = v if up2 else self.upsample2(x)
         Ho, Wo = ops.conv_out_hw(spec, x.H, x.W)
         if out is None:
             out = self.act(Ho, Wo, spec.cout)
         assert (out.H, out.W) == (Ho, Wo) and out.cp >= pad4(spec.cout)
         wino = ops.wino_eligible(spec, x.B * Ho * Wo)  # stride 1, pad 1: (Ho, Wo) == (x.H, x.W)
         if wino and ops.wino4_eligible(spec, x, Ho, Wo):
-            self.emit_wino(x, conv, spec, out, res, relu, f4=True, cin_map=cin_map)
+            self.emit_wino(x, conv, spec, out, res, relu, f4=True, cin_map=cin_map, up2=up2)
         elif wino and x.cs % 2 == 0 and x.co % 2 == 0:
             self.emit_wino(x, conv, spec, out, res, relu, f4=False, cin_map=cin_map)
         elif ops.small_conv_eligible(spec, x):
@@ -252,16 +267,22 @@ class _Builder:
                        mfma_flops=pipe * 6 / 16, mfma_bf16_flops=pipe * 6)
 
     def conv_head(self, x: Act, conv: nn.Module, bn: Optional[nn.Module], final: nn.Conv2d, out: torch.Tensor,
-                  n_store: int) -> bool:
+                  n_store: int, up2: bool = False) -> bool:
         """relu(bn(conv(x))) -> final (1x1 + bias) into the NCHW map `out` (channels < n_store) as
         one split-Winograd launch plus a partial-sum pass (krrn_conv3x3_wino_x3_head_f32), for a final
         conv with at most 4 outputs (nml_final with one class, krrn.py:80-84, 98). False (nothing
-        emitted) when it does not apply."""
+        emitted) when it does not apply. up2: as in conv()."""
         if not (isinstance(conv, nn.Conv2d) and tuple(final.kernel_size) == (1, 1)
                 and tuple(final.stride) == (1, 1) and final.in_channels == conv.out_channels
                 and n_store <= min(4, final.out_channels) and x.cs % 2 == 0 and x.co % 2 == 0):
             return False
         spec = ops.make_conv(conv, bn, self.dev, cin_p=x.cp)
+        if up2:
+            if not ops.wino_eligible(spec, 4 * x.B * x.H * x.W):
+                return False
+            v = self.up2_view(x, spec)
+            up2 = v is not None
+            x = v if up2 else self.upsample2(x)
         M = x.B * x.H * x.W
         if not ops.wino_eligible(spec, M):
             return False
@@ -280,14 +301,16 @@ class _Builder:
                     flops=2.0 * spec.cin * spec.cout * 9 * M + 2.0 * spec.cout * n_store * M)
         self.plan.add("krrn_conv3x3_wino4_x3_head_f32" if f4 else "krrn_conv3x3_wino_x3_head_f32", ptr(x.t), x.cs,
                       x.co, x.B, x.H, x.W, spec.cin_p, ptr(U), np_,
-                      ptr(spec.scale), ptr(spec.bias), ptr(None), 0, 0, 1, ptr(w1), ptr(b1), n_store, ptr(part),
+                      ptr(spec.scale), ptr(spec.bias), ptr(None), 0, 0, 1 | (2 if up2 else 0), ptr(w1), ptr(b1), n_store, ptr(part),
                       ptr(out), out.shape[1], meta=meta)
         return True
 
     def upsample2(self, x: Act) -> Act:
         """UpsamplingBilinear2d(scale 2)(x) (krrn.py:56, 78; align_corners=True) materialised for the
-        conv after it. Blending the upsample into the split Winograd's input staging instead was
-        measured slower and removed."""
+        conv after it, where that conv runs on the F(2x2) Winograd or a direct kernel. The F(4x4)
+        Winograd reads the half-resolution map itself (up2_view): the upsample is folded into its
+        transform matrices, no upsampled value is formed. (Interpolating every staged value inside the
+        F(2x2) staging was measured slower and removed: DESIGN.md section 4, round 4.)"""
         up = self.act(2 * x.H, 2 * x.W, x.c)
         self.resize(x, up, align=True)
         return up
@@ -332,16 +355,18 @@ class _Builder:
                                 K=spec.cin_p * spec.ksize ** 2, splits=1, mfma_flops=p["mfma_flops"]))
 
     def emit_wino(self, x: Act, conv: nn.Conv2d, spec, out: Act, res: Optional[Act], relu: bool, f4: bool,
-                  cin_map=None):
+                  cin_map=None, up2: bool = False):
         """Fused Winograd on split-bf16 operands: F(4x4,3x3) (krrn_conv3x3_wino4_x3_f32) when f4, else
-        F(2x2,3x3) (krrn_conv3x3_wino_x3_f32)."""
+        F(2x2,3x3) (krrn_conv3x3_wino_x3_f32). up2 (f4 only): x is an up2_view, the launch reads the
+        half-resolution buffer."""
+        assert f4 or not up2
         U, meta = self.wino_problem(x, conv, spec, f4, cin_map)
         np_ = meta["N"]
         meta.update(flops=2.0 * spec.cin * spec.cout * 9 * meta["M"], tag="conv_wino")
         self.plan.add("krrn_conv3x3_wino4_x3_f32" if f4 else "krrn_conv3x3_wino_x3_f32", ptr(x.t), x.cs, x.co, x.B,
                       x.H, x.W, spec.cin_p, ptr(U), np_, np_, ptr(spec.scale), ptr(spec.bias),
                       ptr(res.t) if res is not None else ptr(None), res.cs if res is not None else 0,
-                      res.co if res is not None else 0, ptr(out.t), out.cs, out.co, int(relu), meta=meta)
+                      res.co if res is not None else 0, ptr(out.t), out.cs, out.co, int(relu) | (2 if up2 else 0), meta=meta)
 
     def emit_convT_s2(self, x: Act, spec, out: Act, relu: bool, tag: str = "conv"):
         """A stride-2 transposed conv with 128 outputs (the deconv, myhrnet.py:314-326; XYZNet's first

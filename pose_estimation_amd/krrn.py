@@ -233,17 +233,20 @@ class KRRNPlan:
     def _head_tail(self, bld: _Builder, x: Act, convs, final: nn.Conv2d, out: torch.Tensor, n_store: int):
         """A head's full-resolution tail (krrn.py:56-65 / 78-84): UpsamplingBilinear2d(x2) ->
         [conv3x3 + BN + ReLU] x len(convs) -> the final 1x1 (+ bias) into the NCHW map `out`; a
-        final with at most 4 outputs runs inside the last conv's launch (_Builder.conv_head).
+        final with at most 4 outputs runs inside the last conv's launch (_Builder.conv_head). The
+        first conv reads the half-resolution map x itself where it runs on the F(4x4) Winograd (the
+        upsample folded into its input transform: no resize launch, no upsampled buffer); on the
+        F(2x2) and direct paths the upsampled map is materialised (_Builder.upsample2).
         Running the tail in crop chunks through reused chunk buffers (the upsampled map kept in the
         Infinity Cache) measured 0.8 % slower."""
         spec = ops.make_conv(final, None, self.plan.device, cin_p=pad4(convs[-1][0].out_channels))
         bld.specs.append(spec)
-        h = bld.upsample2(x)
+        h = x
         for i, (conv, bn) in enumerate(convs):
             # the last conv and the final 1x1 as one launch where the final is narrow (bld.conv_head)
-            if i == len(convs) - 1 and bld.conv_head(h, conv, bn, final, out, n_store):
+            if i == len(convs) - 1 and bld.conv_head(h, conv, bn, final, out, n_store, up2=i == 0):
                 return
-            h = bld.conv(h, conv, bn, relu=True)
+            h = bld.conv(h, conv, bn, relu=True, up2=i == 0)
         self._nchw_conv(h, spec, out, n_store)
 
     def _nchw_conv(self, x: Act, spec, out: torch.Tensor, n_store: int):
