@@ -470,34 +470,11 @@ int krrn_add_metric_f32(const float* pred_r, const float* pred_t, const float* m
                         const long long* cls_id, const int* sym, int nsym, int B, int P, double* ws, double* out,
                         void* stream);
 
-/* On-GPU input construction, replacing PoseDataset._load_data's per-sample numpy
- * work (dataset/linemod/batchdataset.py:603-771) for B crops of one snapped square size S.
+/* On-GPU input construction, replacing PoseDataset._load_data's per-sample numpy work
+ * (dataset/linemod/batchdataset.py:603-771) and, by this project's own definition, its Data.RESIZE
+ * path (_load_resize_data, :339-601), for B crops resampled to one size T.
  * Frames: rgb u8 [F][H][W][3], depth f32 [F][H][W], mask_label u8 [F][H][W], optional obj_mask u8
- * [F][H][W] (the reference's mask_obj from the GT coordinate map, :662; NULL = all ones); crop b
- * reads frame frame[b] at rows rc[2b] .. +S, cols rc[2b+1] .. +S.
- * krrn_crop_inputs_u8: img f32 [B][3][S][S] = (float(u8 / 255.) - mean) / std (ImageNet, :70, 722,
- * 744); mask u8 [B][S*S] = mask_label != 0 && depth != 0 (&& obj_mask != 0) (:662-666). */
-int krrn_crop_inputs_u8(const unsigned char* rgb, const float* depth, const unsigned char* mask_label,
-                        const unsigned char* obj_mask, int F, int H, int W, const int* frame, const int* rc, int B,
-                        int S, float* img, unsigned char* mask, void* stream);
-
-/* choose (:667-679): the crop's mask pixels in row-major order; more than N -> a uniformly random
- * order-preserving N-subset (the N smallest of counter-hash keys of (seed, stream_id, crop, rank),
- * radix-selected; the reference draws it with np.random.shuffle), fewer -> wrap-padded to N.
- * Then x_map / y_map = full-frame column / row (:712-715) and cloud [B][N][3] = ((x - cx) * z / fx,
- * (y - cy) * z / fy, z) with z = depth / depth_scale, f32 arithmetic in the reference's order
- * (:718-721); K4 [B][4] = fx, fy, cx, cy. count [B] = mask pixels (0 -> zeros everywhere: the
- * reference drops such a sample). choose int64 [B][N] (crop-local r*S + c).
- * 0 <= stream_id <= 65534 (KRRN_ESHAPE otherwise, before any launch): the id enters the key's top 16 bits
- * as stream_id + 1, so ids further apart would draw the same subsets. A caller that needs more draws per
- * seed than that advances the seed (PoseDataset.batch does). */
-int krrn_choose_points(const unsigned char* mask, int B, int S, int N, const float* depth, int H, int W,
-                       const int* frame, const int* rc, const float* K4, float depth_scale, const long long* seed,
-                       int stream_id, long long* choose, float* cloud, float* xmap, float* ymap, int* count,
-                       void* stream);
-
-/* The same two steps for crops resampled to one network size T: the reference's Data.RESIZE path
- * (_load_resize_data, dataset/linemod/batchdataset.py:339-601) by this project's own definition.
+ * [F][H][W] (the reference's mask_obj from the GT coordinate map, :662; NULL = all ones).
  * Crop b is the S_b x S_b window of frame[b] at rows rc[2b] .., cols rc[2b+1] .., S_b = side[b] (int32 [B], read
  * on the device: one launch mixes sides). All index arithmetic is integer. Output pixel j of T sits at window
  * coordinate ((2j+1) S_b - T) / (2T) (cv2.resize's half-pixel centres; rows alike): nx = (2j+1) S_b - T, D = 2T,
@@ -505,30 +482,48 @@ int krrn_choose_points(const unsigned char* mask, int B, int S, int N, const flo
  * S_b - 1): the border is the window's own edge (the reference resizes the cut window).
  * krrn_crop_inputs_resize_u8: img f32 [B][3][T][T]: per channel on the raw u8 values, in f64 with every product and
  * sum rounded on its own, top = (1 - wx) a[ya][xa] + wx a[ya][xb], bot likewise on row yb, p = (1 - wy) top + wy bot;
- * then (float(p / 255.) - mean) / std as krrn_crop_inputs_u8. Plain bilinear also when S_b > T (INTER_LINEAR; no area
- * averaging). mask u8 [B][T*T] = krrn_crop_inputs_u8's predicate at the nearest source pixel of the centre,
- * (r0 + ((2i+1) S_b) / D, c0 + ((2j+1) S_b) / D) by integer division, always inside the window. The reference's
- * 'resize' branch resizes the whole frame, not the window, for mask, coordinate and region: not copied.
- * With S_b == T both outputs equal krrn_crop_inputs_u8's bit for bit. 1 <= T <= 4096, 1 <= B <= 65535 (KRRN_ESHAPE
- * otherwise, before any launch). The host cannot see side[b] or rc: the caller keeps every window inside the
- * frame (dataset.build_inputs checks its boxes); a window that is not gives a crop of zeros with an empty mask. */
+ * then (float(p / 255.) - mean) / std (ImageNet, :70, 722, 744). Plain bilinear also when S_b > T (INTER_LINEAR; no
+ * area averaging). mask u8 [B][T*T] = mask_label != 0 && depth != 0 (&& obj_mask != 0) (:662-666) at the nearest
+ * source pixel of the centre, (r0 + ((2i+1) S_b) / D, c0 + ((2j+1) S_b) / D) by integer division, always inside the
+ * window. The reference's 'resize' branch resizes the whole frame, not the window, for mask, coordinate and region:
+ * not copied. 1 <= T <= 4096, 1 <= B <= 65535 (KRRN_ESHAPE otherwise, before any launch). The host cannot see
+ * side[b] or rc: the caller keeps every window inside the frame (dataset.build_inputs checks its boxes); a window
+ * that is not gives a crop of zeros with an empty mask. */
 int krrn_crop_inputs_resize_u8(const unsigned char* rgb, const float* depth, const unsigned char* mask_label,
                                const unsigned char* obj_mask, int F, int H, int W, const int* frame, const int* rc,
                                const int* side, int B, int T, float* img, unsigned char* mask, void* stream);
 
-/* choose over the T*T mask exactly as krrn_choose_points (the same keys of (seed, stream_id, crop, rank), order,
- * wrap padding, zeros and count 0 for an empty mask; choose int64 [B][N] = i*T + j). For a chosen pixel (i, j):
- * x_map = (float)((double)c0 + (double)nx / (double)D), y_map likewise: the resized pixel's centre in full-frame
- * coordinates, generally fractional, which is what krrn_pnp_ransac_f32 reads; cloud = the back-projection of the
- * nearest source pixel (sr, sc) above with the frame's own K4 in krrn_choose_points' f32 order (z = depth[sr][sc] /
- * depth_scale, ((float)sc - cx) z / fx, ((float)sr - cy) z / fy). The reference (:551-553) truncates bilinear x / y
- * maps to int16 to index the depth and (:526) moves the principal point to OUT_SIZE / 2: not copied. With
- * S_b == T every output equals krrn_choose_points' bit for bit. Limits as above, N >= 1, depth_scale != 0,
- * 0 <= stream_id <= 65534; a window outside the frame gives count 0 and zeros. */
+/* choose (:667-679) over the T*T mask: its pixels in row-major order; more than N -> a uniformly random
+ * order-preserving N-subset (the N smallest of counter-hash keys of (seed, stream_id, crop, rank),
+ * radix-selected; the reference draws it with np.random.shuffle), fewer -> wrap-padded to N. choose int64 [B][N] =
+ * i*T + j; count [B] = mask pixels (0 -> zeros everywhere: the reference drops such a sample). For a chosen pixel
+ * (i, j): x_map = (float)((double)c0 + (double)nx / (double)D), y_map likewise: the resized pixel's centre in
+ * full-frame coordinates (:712-715), generally fractional, which is what krrn_pnp_ransac_f32 reads; cloud [B][N][3] =
+ * the back-projection of the nearest source pixel (sr, sc) above with the frame's own K4 [B][4] = fx, fy, cx, cy,
+ * f32 arithmetic in the reference's order (:718-721): z = depth[sr][sc] / depth_scale, ((float)sc - cx) z / fx,
+ * ((float)sr - cy) z / fy. The reference (:551-553) truncates bilinear x / y maps to int16 to index the depth and
+ * (:526) moves the principal point to OUT_SIZE / 2: not copied. Limits as above, N >= 1, depth_scale != 0; a window
+ * outside the frame gives count 0 and zeros.
+ * 0 <= stream_id <= 65534 (KRRN_ESHAPE otherwise, before any launch): the id enters the key's top 16 bits
+ * as stream_id + 1, so ids further apart would draw the same subsets. A caller that needs more draws per
+ * seed than that advances the seed (PoseDataset.batch does). */
 int krrn_choose_points_resize(const unsigned char* mask, int B, int T, int N, const float* depth, int H, int W,
                               const int* frame, const int* rc, const int* side, const float* K4, float depth_scale,
                               const long long* seed, int stream_id, long long* choose, float* cloud, float* xmap,
                               float* ymap, int* count, void* stream);
+
+/* Crops at their own snapped square size S: the same with every side == S and T = S, by the same kernels. The
+ * weights are then 0, the nearest pixel is (i, j) and x_map / y_map are the full-frame column / row: img f32
+ * [B][3][S][S], mask u8 [B][S*S], choose = crop-local r*S + c. 1 <= S <= min(H, W), 1 <= B <= 65535 for the crop,
+ * B, N >= 1 (KRRN_ESHAPE otherwise); a window the frame does not hold (a bad rc row) is an empty crop here too: an
+ * image of zeros, an empty mask, count 0 and zero outputs. */
+int krrn_crop_inputs_u8(const unsigned char* rgb, const float* depth, const unsigned char* mask_label,
+                        const unsigned char* obj_mask, int F, int H, int W, const int* frame, const int* rc, int B,
+                        int S, float* img, unsigned char* mask, void* stream);
+int krrn_choose_points(const unsigned char* mask, int B, int S, int N, const float* depth, int H, int W,
+                       const int* frame, const int* rc, const float* K4, float depth_scale, const long long* seed,
+                       int stream_id, long long* choose, float* cloud, float* xmap, float* ymap, int* count,
+                       void* stream);
 
 /* The zoom-in pass's windows (this project's own rule): per crop b the square window of its H x W frame
  * that holds the projection of its model points pts f32 [B][P][3] (metres) under the pose R f64 [B][9] row-major,

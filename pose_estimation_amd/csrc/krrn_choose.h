@@ -1,6 +1,6 @@
-// The `choose` selection of the input kernels, stated once: inputs.hip (krrn_choose_points, crops at their own
-// size) and inputs_resize.hip (krrn_choose_points_resize, crops resampled to one size) pick the same pixels of a
-// u8 mask row and differ only in what they make of a chosen pixel. One workgroup of kChooseThreads threads per
+// The `choose` selection of the input kernels, stated once: inputs.hip's krrn_choose_points (crops at their own
+// size) and krrn_choose_points_resize (crops resampled to one size) pick the same pixels of a u8 mask row through
+// the one choose_points_kernel. One workgroup of kChooseThreads threads per
 // crop: block-wide ballot scans keep the row-major order, and the random subset is the N smallest of per-rank
 // 32-bit hash keys found by a 4-pass radix select (ties broken by rank), so no sort and no workspace. Integer and
 // comparison code only, so the per-file -ffp-contract flags of the Makefile cannot change what a helper computes.

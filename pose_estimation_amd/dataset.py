@@ -188,6 +188,43 @@ def synthetic_frames(F: int, seed: int = 0, objlist: Sequence[int] = (6,), H: in
     return {k: np.stack(v) for k, v in out.items()}
 
 
+def _stage_windows(frame_idx: Sequence[int], boxes: Sequence[Tuple[int, int, int, int]], dev):
+    """(fi int32 [B], rc int32 [B, 2] = (r0, c0), side int32 [B]) of the boxes' windows, on `dev`: what the input
+    kernels read. One upload; the three are contiguous views of it."""
+    fi, B = list(frame_idx), len(boxes)
+    rc = [v for b in boxes for v in (b[0], b[2])]
+    w = h2d(torch.tensor(fi + rc + [b[1] - b[0] for b in boxes], dtype=torch.int32), dev)
+    return w[:len(fi)], w[len(fi):len(fi) + 2 * B].view(B, 2), w[len(fi) + 2 * B:]
+
+
+def _launch_inputs(frames, fi, rc, side, out_side: int, num_point: int, K4, seed, stream_id, depth_scale,
+                   obj_mask) -> Dict[str, torch.Tensor]:
+    """The two launches of the input path for windows staged on the device (fi, rc, side: _stage_windows), at output
+    side `out_side`. side=None: every window's side is out_side (krrn_crop_inputs_u8, krrn_choose_points); else the
+    kernels read side[b] (krrn_crop_inputs_resize_u8, krrn_choose_points_resize)."""
+    rgb, depth, ml = frames["rgb"], frames["depth"], frames["mask_label"]
+    dev = rgb.device
+    F, H, W = depth.shape
+    B, T, N = int(fi.shape[0]), out_side, num_point
+    crop, pick, sd = (("krrn_crop_inputs_u8", "krrn_choose_points", ()) if side is None else
+                      ("krrn_crop_inputs_resize_u8", "krrn_choose_points_resize", (ptr(side),)))
+    img = torch.empty((B, 3, T, T), dtype=torch.float32, device=dev)
+    mask = torch.empty((B, T * T), dtype=torch.uint8, device=dev)
+    st = stream_ptr(dev)
+    _lib.call(crop, ptr(rgb), ptr(depth), ptr(ml), ptr(obj_mask), F, H, W, ptr(fi), ptr(rc), *sd, B, T, ptr(img),
+              ptr(mask), st)
+    choose = torch.empty((B, 1, N), dtype=torch.int64, device=dev)
+    cloud = torch.empty((B, N, 3), dtype=torch.float32, device=dev)
+    xm = torch.empty((B, N, 1), dtype=torch.float32, device=dev)
+    ym = torch.empty((B, N, 1), dtype=torch.float32, device=dev)
+    cnt = torch.empty((B,), dtype=torch.int32, device=dev)
+    K4 = h2d(K4, dev, torch.float32)
+    _lib.call(pick, ptr(mask), B, T, N, ptr(depth), H, W, ptr(fi), ptr(rc), *sd, ptr(K4), float(depth_scale),
+              ptr(seed), int(stream_id), ptr(choose), ptr(cloud), ptr(xm), ptr(ym), ptr(cnt), st)
+    return {"img_croped": img, "choose": choose, "cloud": cloud, "x_map_choosed": xm, "y_map_choosed": ym,
+            "point_mask": mask.view(B, 1, T, T), "mask_count": cnt}
+
+
 def build_inputs(frames: Dict[str, torch.Tensor], frame_idx: Sequence[int], boxes: Sequence[Tuple[int, int, int, int]],
                  num_point: int, K4: torch.Tensor, seed: torch.Tensor, stream_id: int = 0,
                  depth_scale: float = 1.0, obj_mask: Optional[torch.Tensor] = None,
@@ -199,43 +236,21 @@ def build_inputs(frames: Dict[str, torch.Tensor], frame_idx: Sequence[int], boxe
     the resized pixels' centres in full-frame coordinates, plus resize_scale f32 [B] = S_b / T and resize_intrinsic
     f32 [B, 4] = (fx / s, fy / s, (cx - c0 + 0.5) / s - 0.5, (cy - r0 + 0.5) / s - 0.5), the pinhole under which the
     crop's resized pixel indices project (the reference's key; nothing here reads it)."""
-    rgb, depth, ml = frames["rgb"], frames["depth"], frames["mask_label"]
-    dev = rgb.device
-    F, H, W = depth.shape
-    B = len(frame_idx)
     if resize is not None:
         return _build_inputs_resize(frames, frame_idx, boxes, num_point, K4, seed, stream_id, depth_scale, obj_mask,
-                                    int(resize))
+                                    int(resize))[0]
     sizes = {rmax - rmin for rmin, rmax, _, _ in boxes} | {cmax - cmin for _, _, cmin, cmax in boxes}
     if len(sizes) != 1:
         raise ValueError(f"one crop size per batch (bucket by get_square_bbox first), got {sorted(sizes)}")
-    S = sizes.pop()
-    fi = h2d(torch.tensor(list(frame_idx), dtype=torch.int32), dev)
-    rc = h2d(torch.tensor([[b[0], b[2]] for b in boxes], dtype=torch.int32), dev)
-    img = torch.empty((B, 3, S, S), dtype=torch.float32, device=dev)
-    mask = torch.empty((B, S * S), dtype=torch.uint8, device=dev)
-    st = stream_ptr(dev)
-    _lib.call("krrn_crop_inputs_u8", ptr(rgb), ptr(depth), ptr(ml), ptr(obj_mask), F, H, W, ptr(fi), ptr(rc), B, S,
-              ptr(img), ptr(mask), st)
-    N = num_point
-    choose = torch.empty((B, 1, N), dtype=torch.int64, device=dev)
-    cloud = torch.empty((B, N, 3), dtype=torch.float32, device=dev)
-    xm = torch.empty((B, N, 1), dtype=torch.float32, device=dev)
-    ym = torch.empty((B, N, 1), dtype=torch.float32, device=dev)
-    cnt = torch.empty((B,), dtype=torch.int32, device=dev)
-    K4 = h2d(K4, dev, torch.float32)
-    _lib.call("krrn_choose_points", ptr(mask), B, S, N, ptr(depth), H, W, ptr(fi), ptr(rc), ptr(K4), float(depth_scale),
-              ptr(seed), int(stream_id), ptr(choose), ptr(cloud), ptr(xm), ptr(ym), ptr(cnt), st)
-    return {"img_croped": img, "choose": choose, "cloud": cloud, "x_map_choosed": xm, "y_map_choosed": ym,
-            "point_mask": mask.view(B, 1, S, S), "mask_count": cnt}
+    fi, rc, _ = _stage_windows(frame_idx, boxes, frames["rgb"].device)
+    return _launch_inputs(frames, fi, rc, None, sizes.pop(), num_point, K4, seed, stream_id, depth_scale, obj_mask)
 
 
-def _build_inputs_resize(frames, frame_idx, boxes, num_point, K4, seed, stream_id, depth_scale, obj_mask,
-                         T: int) -> Dict[str, torch.Tensor]:
-    """build_inputs(resize=T): the device reads each crop's side, so the windows are checked here, from the boxes."""
-    rgb, depth, ml = frames["rgb"], frames["depth"], frames["mask_label"]
-    dev = rgb.device
-    F, H, W = depth.shape
+def _build_inputs_resize(frames, frame_idx, boxes, num_point, K4, seed, stream_id, depth_scale, obj_mask, T: int):
+    """build_inputs(resize=T): the device reads each crop's side, so the windows are checked here, from the boxes.
+    Returns (build_inputs' dict, the staged windows (fi, rc, side)); the latter is for PoseDataset.batch(zoom=True)."""
+    dev = frames["rgb"].device
+    F, H, W = frames["depth"].shape
     B = len(frame_idx)
     if T < 1:
         raise ValueError(f"resize must be a positive size, got {T}")
@@ -248,15 +263,12 @@ def _build_inputs_resize(frames, frame_idx, boxes, num_point, K4, seed, stream_i
                              f"{(rmin, rmax, cmin, cmax)}")
         if rmin < 0 or cmin < 0 or rmax > H or cmax > W or not 0 <= int(f) < F:
             raise ValueError(f"box {(rmin, rmax, cmin, cmax)} of frame {f} lies outside the {F} frames of {H} x {W}")
-    side = [b[1] - b[0] for b in boxes]
-    fi = h2d(torch.tensor(list(frame_idx), dtype=torch.int32), dev)
-    rc = h2d(torch.tensor([[b[0], b[2]] for b in boxes], dtype=torch.int32), dev)
-    sd = h2d(torch.tensor(side, dtype=torch.int32), dev)
+    win = _stage_windows(frame_idx, boxes, dev)
     scale, intr = resize_intrinsic(K4, boxes, T)
-    out = build_inputs_windows(frames, fi, rc, sd, num_point, K4, seed, stream_id, depth_scale, obj_mask, T)
+    out = build_inputs_windows(frames, *win, num_point, K4, seed, stream_id, depth_scale, obj_mask, T)
     out["resize_scale"] = h2d(torch.from_numpy(scale.astype(np.float32)), dev)
     out["resize_intrinsic"] = h2d(torch.from_numpy(intr.astype(np.float32)), dev)
-    return out
+    return out, win
 
 
 def build_inputs_windows(frames: Dict[str, torch.Tensor], fi: torch.Tensor, rc: torch.Tensor, side: torch.Tensor,
@@ -273,8 +285,6 @@ def build_inputs_windows(frames: Dict[str, torch.Tensor], fi: torch.Tensor, rc: 
             and seed.is_cuda and (obj_mask is None or obj_mask.is_cuda)):
         raise RuntimeError("build_inputs_windows runs on the HIP path only (the frames, fi / rc / side and the seed "
                            "must be GPU tensors)")
-    dev = rgb.device
-    F, H, W = depth.shape
     B = int(fi.shape[0])
     T = int(T)
     if T < 1:
@@ -282,23 +292,8 @@ def build_inputs_windows(frames: Dict[str, torch.Tensor], fi: torch.Tensor, rc: 
     if tuple(rc.shape) != (B, 2) or tuple(side.shape) != (B,) or tuple(K4.shape) != (B, 4):
         raise ValueError(f"one window and one K4 row per crop: {B} crops, rc {tuple(rc.shape)}, side "
                          f"{tuple(side.shape)}, K4 {tuple(K4.shape)}")
-    fi, rc, sd = (h2d(x, dev, torch.int32) for x in (fi, rc, side))
-    img = torch.empty((B, 3, T, T), dtype=torch.float32, device=dev)
-    mask = torch.empty((B, T * T), dtype=torch.uint8, device=dev)
-    st = stream_ptr(dev)
-    _lib.call("krrn_crop_inputs_resize_u8", ptr(rgb), ptr(depth), ptr(ml), ptr(obj_mask), F, H, W, ptr(fi), ptr(rc),
-              ptr(sd), B, T, ptr(img), ptr(mask), st)
-    N = num_point
-    choose = torch.empty((B, 1, N), dtype=torch.int64, device=dev)
-    cloud = torch.empty((B, N, 3), dtype=torch.float32, device=dev)
-    xm = torch.empty((B, N, 1), dtype=torch.float32, device=dev)
-    ym = torch.empty((B, N, 1), dtype=torch.float32, device=dev)
-    cnt = torch.empty((B,), dtype=torch.int32, device=dev)
-    K4 = h2d(K4, dev, torch.float32)
-    _lib.call("krrn_choose_points_resize", ptr(mask), B, T, N, ptr(depth), H, W, ptr(fi), ptr(rc), ptr(sd), ptr(K4),
-              float(depth_scale), ptr(seed), int(stream_id), ptr(choose), ptr(cloud), ptr(xm), ptr(ym), ptr(cnt), st)
-    return {"img_croped": img, "choose": choose, "cloud": cloud, "x_map_choosed": xm, "y_map_choosed": ym,
-            "point_mask": mask.view(B, 1, T, T), "mask_count": cnt}
+    fi, rc, side = (h2d(x, rgb.device, torch.int32) for x in (fi, rc, side))
+    return _launch_inputs(frames, fi, rc, side, T, num_point, K4, seed, stream_id, depth_scale, obj_mask)
 
 
 def resize_intrinsic(K4, boxes: Sequence[Tuple[int, int, int, int]], T: int) -> Tuple[np.ndarray, np.ndarray]:
@@ -734,8 +729,11 @@ class PoseDataset(torch.utils.data.Dataset):
                                boxes, torch.stack([mesh["region"][m[0]] for m in metas]),
                                frame_hw=tuple(fr["depth"].shape[1:]))
         seed, sid = self._draw_for(device)
-        out = build_inputs(fr, fidx, boxes, self.num_point, K4, seed, stream_id=sid,
-                           obj_mask=maps["cover_frame"] if maps is not None else None, resize=self.resize)
+        if self.resize is None:
+            out = build_inputs(fr, fidx, boxes, self.num_point, K4, seed, stream_id=sid,
+                               obj_mask=maps["cover_frame"] if maps is not None else None)
+        else:  # build_inputs(resize=), and the windows it staged for zoom=True below (no maps: resize refuses gt_maps)
+            out, win = _build_inputs_resize(fr, fidx, boxes, self.num_point, K4, seed, sid, 1.0, None, self.resize)
         info = self.obj_info
         ext = [np.array(info[m[0]]["size"]) / 1000.0 for m in metas]
         lfb = [np.array(info[m[0]]["min"]) / 1000.0 for m in metas]
@@ -778,10 +776,8 @@ class PoseDataset(torch.utils.data.Dataset):
             out["det_info"] = det["info"]
         if zoom:
             out.update({"zoom_rgb": fr["rgb"], "zoom_depth": fr["depth"], "zoom_mask": fr["mask_label"],
-                        "zoom_frame": out["bop_frame"] if bop else h2d(torch.tensor(fidx, dtype=torch.int32), device),
-                        "zoom_rc": h2d(torch.tensor([[b[0], b[2]] for b in boxes], dtype=torch.int32), device),
-                        "zoom_side": h2d(torch.tensor([b[1] - b[0] for b in boxes], dtype=torch.int32), device),
-                        "zoom_depth_scale": torch.tensor(1.0, dtype=torch.float64)})  # build_inputs' default, above
+                        "zoom_frame": out["bop_frame"] if bop else win[0], "zoom_rc": win[1], "zoom_side": win[2],
+                        "zoom_depth_scale": torch.tensor(1.0, dtype=torch.float64)})  # the build's, above
         return out
 
     def zoom_batch(self, data: Dict[str, torch.Tensor], R: torch.Tensor, t: torch.Tensor) -> Dict[str, torch.Tensor]:

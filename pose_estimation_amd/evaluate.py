@@ -98,7 +98,6 @@ def _batches(buckets: Dict[int, List[int]], bs: int):
             yield S, idx[lo:lo + bs]
 
 
-@torch.no_grad()
 def eval_records(model: KRRN, dataset: PoseDataset, indices: Dict[int, List[int]], bs: int, device,
                  opt_pose: bool = True, with_loss: bool = True, pose_solver: str = "pnp",
                  refine: Optional[str] = None, bop: bool = False, poses: bool = False,
@@ -164,6 +163,18 @@ def eval_records(model: KRRN, dataset: PoseDataset, indices: Dict[int, List[int]
     and runs the solver again. `refine`, `select`, ADD(-S), the BOP errors and the pose table read the last pass and
     its batch dict, so select_pose sees the new `bbox`. The return value then ends with an int64 [n] array in the same
     row order: the last pass's zoom status per crop (zoom.pose_windows), read back in the epoch's single read-back."""
+    tabs, net, zstat = _eval_epoch(model, dataset, indices, bs, device, opt_pose, with_loss, pose_solver, refine, bop,
+                                   poses, select, net_masks, zoom)
+    extras = tuple(x for x in (net, zstat) if x is not None)
+    if not extras:
+        return tabs.legacy()
+    return tuple(t for t in tabs if t is not None) + extras
+
+
+@torch.no_grad()
+def _eval_epoch(model, dataset, indices, bs, device, opt_pose, with_loss, pose_solver, refine, bop, poses, select,
+                net_masks, zoom):
+    """eval_records' epoch: (EpochTables, the net_masks run list or None, the zoom status array or None)."""
     _check_zoom(zoom, dataset)
     if zoom and net_masks:
         raise ValueError("zoom with net_masks is not built: the paste places the crop's pixels at dataset.boxes")
@@ -208,6 +219,21 @@ def eval_records(model: KRRN, dataset: PoseDataset, indices: Dict[int, List[int]
             ev.record(side)
         return d, ev
 
+    def solve(pred, data, B):
+        """Clone what the pose step reads from the plan's output buffers (the next forward of the same shape rewrites
+        them), hand the copies over to the pose stream and solve there: (base_r, base_t, pred_t)."""
+        xyz = pred["xyz"].clone()
+        pred_t = pred["pred_t"].reshape(B, 3).clone() if opt_pose else None
+        done = torch.cuda.Event()
+        done.record(main)
+        pstr.wait_event(done)
+        xyz.record_stream(pstr)
+        if pred_t is not None:
+            pred_t.record_stream(pstr)
+        with torch.cuda.stream(pstr):
+            base_r, base_t = solve_pose({"xyz": xyz}, data)
+        return base_r, base_t, pred_t
+
     nxt = build(0) if batches else None
     views = model.return_views
     model.return_views = True
@@ -232,17 +258,7 @@ def eval_records(model: KRRN, dataset: PoseDataset, indices: Dict[int, List[int]
             lc = None
             if with_loss and "xyz" in data and "multi_cls_mask" in data:
                 lc = map_losses(pred, data, per_crop=True)  # [B, 8]: xyz, normal, region, mask, counts
-            # copies of what the pose step reads from the plan's output buffers
-            xyz = pred["xyz"].clone()
-            pred_t = pred["pred_t"].reshape(B, 3).clone() if opt_pose else None
-            done = torch.cuda.Event()
-            done.record(main)
-            pstr.wait_event(done)
-            xyz.record_stream(pstr)
-            if pred_t is not None:
-                pred_t.record_stream(pstr)
-            with torch.cuda.stream(pstr):
-                base_r, base_t = solve_pose({"xyz": xyz}, data)
+            base_r, base_t, pred_t = solve(pred, data, B)
             for _ in range(zoom):
                 # cut again about the solver's own pose (pose stream), forward again (caller's stream, after the pose
                 # stream), solve again (pose stream); the side stream goes on building the next batch's inputs
@@ -254,16 +270,7 @@ def eval_records(model: KRRN, dataset: PoseDataset, indices: Dict[int, List[int]
                 for k in ZOOM_KEYS:  # made on the pose stream, read by the forward on the caller's
                     data[k].record_stream(main)
                 pred = model(data["img_croped"], data["cloud"], data["choose"], data["cls_id"], opt_pose=opt_pose)
-                xyz = pred["xyz"].clone()
-                pred_t = pred["pred_t"].reshape(B, 3).clone() if opt_pose else None
-                done = torch.cuda.Event()
-                done.record(main)
-                pstr.wait_event(done)
-                xyz.record_stream(pstr)
-                if pred_t is not None:
-                    pred_t.record_stream(pstr)
-                with torch.cuda.stream(pstr):
-                    base_r, base_t = solve_pose({"xyz": xyz}, data)
+                base_r, base_t, pred_t = solve(pred, data, B)
             if zoom:
                 zoom_pending.append(data["zoom_status"])
             with torch.cuda.stream(pstr):
@@ -348,13 +355,11 @@ def eval_records(model: KRRN, dataset: PoseDataset, indices: Dict[int, List[int]
             brec[:, 2:2 + T] = torch.cat([e["vsd"] for e in bop_pending]).cpu().numpy()
             brec[:, 2 + T] = torch.cat([e["mssd"] for e in bop_pending]).cpu().numpy()
             brec[:, 3 + T] = torch.cat([e["mspd"] for e in bop_pending]).cpu().numpy()
-    tabs = EpochTables(*(None if t is None else torch.from_numpy(t) for t in (rec, brec, prec, srec))).legacy()
-    if net_masks:
-        return (tabs if isinstance(tabs, tuple) else (tabs,)) + (net,)
+    zstat = None
     if zoom:
         zstat = torch.cat(zoom_pending).cpu().numpy().astype(np.int64) if zoom_pending else np.zeros(0, np.int64)
-        return (tabs if isinstance(tabs, tuple) else (tabs,)) + (zstat,)
-    return tabs
+    return (EpochTables(*(None if t is None else torch.from_numpy(t) for t in (rec, brec, prec, srec))),
+            net if net_masks else None, zstat)
 
 
 def fold_records(records: torch.Tensor, objlist: Sequence[int], diameter: Sequence[float], opt_pose: bool,
@@ -539,18 +544,9 @@ def test_epoch(model: KRRN, dataset: PoseDataset, bs: int = 64, device=None, opt
     sizes = [dataset.crop_size(i) for i in range(len(dataset))]
     mine = kd.bucket_shard(sizes, world, rank)
     want_poses = bool(bop_csv or match or seg_json)
-    zkw = {"zoom": int(zoom)} if zoom else {}
-    ret = eval_records(model, dataset, mine, bs, device, opt_pose=opt_pose, with_loss=criterion is not None,
-                       pose_solver=pose_solver, refine=refine, bop=bool(bop), poses=want_poses, select=select,
-                       net_masks=net, **zkw)
-    zstat = None
-    if zoom:
-        zstat, ret = ret[-1], ret[:-1]
-    net_runs = {}
-    if net:
-        net_runs = {crop: (runs, info) for crop, runs, info in ret[-1]}
-        ret = ret[:-1]
-    local = EpochTables.of(ret, bop, want_poses, select)
+    local, runs, zstat = _eval_epoch(model, dataset, mine, bs, device, opt_pose, criterion is not None, pose_solver,
+                                     refine, bool(bop), want_poses, select, net, int(zoom))
+    net_runs = {crop: (r, info) for crop, r, info in runs or ()}
     shard_sizes = [sum(len(v) for v in kd.bucket_shard(sizes, world, r).values()) for r in range(world)]
     gather = lambda t: gather_epoch_records(t, shard_sizes, device, group) if world > 1 else t  # noqa: E731
     metric = Metric(dataset.sym_obj)

@@ -84,9 +84,9 @@ class _FakeSet:
         return self.sizes[i]
 
 
-def _fake_records(model, dataset, indices, bs, device, opt_pose=True, with_loss=True, **solver):
-    """Deterministic per-crop records (a function of the crop id only), in evaluation order; the pose
-    solver's keywords are accepted and ignored."""
+def _fake_epoch(model, dataset, indices, bs, device, *options):
+    """Deterministic per-crop records (a function of the crop id only), in evaluation order, as evaluate._eval_epoch
+    returns them; the epoch's options are accepted and ignored."""
     from pose_estimation_amd import evaluate as ev
     rows = []
     for S, idx in ev._batches(indices, bs):
@@ -103,14 +103,15 @@ def _fake_records(model, dataset, indices, bs, device, opt_pose=True, with_loss=
             r[ev._R["t_f"]] *= 0.1
             r[ev._R["valid"]] = 1.0
             rows.append(r)
-    return torch.stack(rows) if rows else torch.zeros((0, len(ev.REC)), dtype=torch.float64)
+    rec = torch.stack(rows) if rows else torch.zeros((0, len(ev.REC)), dtype=torch.float64)
+    return ev.EpochTables(rec), None, None
 
 
 def _epoch_worker(rank, world, port, n, q):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world),
                       LOCAL_RANK=str(rank))
     from pose_estimation_amd import evaluate as ev
-    ev.eval_records = _fake_records
+    ev._eval_epoch = _fake_epoch
     kd.init_from_env("gloo")
     out = ev.test_epoch(None, _FakeSet(n), bs=4, device="cpu")
     q.put((rank, out))
@@ -123,12 +124,12 @@ def test_gloo_world2_sharded_epoch_matches_single():
     crop order, plus the all_reduce tally check) gives the world-1 result exactly."""
     from pose_estimation_amd import evaluate as ev
     n = 37
-    saved = ev.eval_records
-    ev.eval_records = _fake_records
+    saved = ev._eval_epoch
+    ev._eval_epoch = _fake_epoch
     try:
         ref = ev.test_epoch(None, _FakeSet(n), bs=4, device="cpu", world=1, rank=0)
     finally:
-        ev.eval_records = saved
+        ev._eval_epoch = saved
     assert ref["test_count"] == n
     world = 2
     ctx = mp.get_context("spawn")

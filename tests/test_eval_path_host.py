@@ -136,6 +136,36 @@ def test_epoch_tables_legacy_return(n, with_bop, with_poses, with_sel):
     assert EpochTables.of(out, with_bop, with_poses, with_sel) == bundle     # test_epoch's way back, by field name
 
 
+@pytest.mark.parametrize("extra", ["plain", "net_masks", "zoom"])
+@pytest.mark.parametrize("with_bop, with_poses, with_sel", list(itertools.product([False, True], repeat=3)))
+def test_eval_records_return_shape(monkeypatch, extra, with_bop, with_poses, with_sel):
+    """eval_records' documented return over a stubbed epoch: the tables that were asked for in the order rec, bop,
+    poses, sel, rec alone as a lone tensor, and the net_masks run list or the zoom status array last."""
+    from pose_estimation_amd import evaluate
+    tab = lambda cols, fill: torch.full((2, len(cols)), fill, dtype=torch.float64)  # noqa: E731
+    rec, brec, prec, srec = tab(REC, 1.0), tab(bop.BOP_REC, 2.0), tab(POSE_REC, 3.0), tab(SEL_REC, 4.0)
+    runs, zstat = [(0, [3, 1], [0] * 5), (1, [4], [0] * 5)], torch.zeros(2, dtype=torch.int64).numpy()
+    seen = []
+
+    def stub(model, dataset, indices, bs, device, opt_pose, with_loss, pose_solver, refine, bop, poses, select,
+             net_masks, zoom):
+        seen.append((bop, poses, select, net_masks, zoom))
+        return (EpochTables(rec, brec if bop else None, prec if poses else None, srec if select else None),
+                runs if net_masks else None, zstat if zoom else None)
+
+    monkeypatch.setattr(evaluate, "_eval_epoch", stub)
+    out = evaluate.eval_records(None, None, {}, 2, "cpu", bop=with_bop, poses=with_poses,
+                                select="depth" if with_sel else None, net_masks=extra == "net_masks",
+                                zoom=1 if extra == "zoom" else 0)
+    assert seen == [(with_bop, with_poses, "depth" if with_sel else None, extra == "net_masks", int(extra == "zoom"))]
+    want = [rec] + [t for t, on in ((brec, with_bop), (prec, with_poses), (srec, with_sel)) if on]
+    want += {"plain": [], "net_masks": [runs], "zoom": [zstat]}[extra]
+    if len(want) == 1:
+        assert out is rec                                         # the bare case: a lone tensor, not a tuple of one
+    else:
+        assert isinstance(out, tuple) and len(out) == len(want) and all(a is b for a, b in zip(out, want))
+
+
 class _OnGpu(torch.Tensor):
     """A host tensor that claims to be on the GPU: the operand checks come before anything touches a device."""
     is_cuda = True

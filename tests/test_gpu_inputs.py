@@ -323,3 +323,77 @@ def test_crop_inputs_rejects(dev):
     for null in (0, 1, 2, 4, 5, 6, 7):  # obj_mask (3) may be NULL
         st, img, mask = _crop_call(dev, sc, np.ones((1, 12, 14), np.uint8), [0], [(0, 0)], 9, null=null)
         assert st == EARG and img.untouched() and mask.untouched(), null
+
+
+# ---- windows the frame does not hold, through both pairs of entry points ----
+
+# (frame, r0, c0, side) on two 16 x 16 frames: past the right edge, past the bottom, above the top, side 0, and a good
+# window. Every address a missing guard would compute still lies inside the two-frame tensors.
+OUTSIDE = [(0, 0, 12, 8), (0, 12, 0, 8), (1, -4, 0, 8), (0, 4, 4, 0), (0, 4, 4, 8)]
+
+
+@pytest.mark.parametrize("pair", ["native", "resized"])
+def test_window_outside_the_frame_is_an_empty_crop(dev, pair):
+    """A bad rc row (and, for the resized pair, a bad side) gives an image of zeros, an empty mask, count 0 and zero
+    choose / cloud / maps; the good crop beside them is tests/resize_ref.py's bit for bit; no guard is written. The
+    label mask is all ones, so a crop read from a window that is not there would not come out empty."""
+    from tests import resize_ref as R
+    F, H, W, T, N = 2, 16, 16, 8, 5
+    crops = [c for c in OUTSIDE if pair == "resized" or c[3] == T]
+    B = len(crops)
+    sc = _scene(F, H, W, seed=21)
+    sc["mask_label"][:] = 255
+    k4 = _k4(B)
+    ins = [_dev(dev, sc[k]) for k in ("rgb", "depth", "mask_label")] + [
+        _dev(dev, np.array([c[0] for c in crops], np.int32)), _dev(dev, np.array([c[1:3] for c in crops], np.int32)),
+        _dev(dev, np.array([c[3] for c in crops], np.int32)), _dev(dev, k4),
+        torch.tensor([77], dtype=torch.int64, device=dev)]
+    rgb, depth, ml, frame, rc, side, kd, seed = [P(t.data_ptr()) for t in ins]
+    out = {"img": Guarded(dev, (B, 3, T, T), torch.float32), "mask": Guarded(dev, (B, T * T), torch.uint8),
+           "choose": Guarded(dev, (B, N), torch.int64), "cloud": Guarded(dev, (B, N, 3), torch.float32),
+           "xmap": Guarded(dev, (B, N), torch.float32), "ymap": Guarded(dev, (B, N), torch.float32),
+           "count": Guarded(dev, (B,), torch.int32)}
+    o = {k: P(v.ptr) for k, v in out.items()}
+    lib, st = _lib.lib(), stream_ptr(dev)
+    sd = (side,) if pair == "resized" else ()
+    crop_fn, pick_fn = ((lib.krrn_crop_inputs_resize_u8, lib.krrn_choose_points_resize) if pair == "resized" else
+                        (lib.krrn_crop_inputs_u8, lib.krrn_choose_points))
+    assert crop_fn(rgb, depth, ml, P(0), F, H, W, frame, rc, *sd, B, T, o["img"], o["mask"], st) == 0
+    assert pick_fn(o["mask"], B, T, N, depth, H, W, frame, rc, *sd, kd, 2.0, seed, 9, o["choose"], o["cloud"],
+                   o["xmap"], o["ymap"], o["count"], st) == 0
+    torch.cuda.synchronize()
+    got = {k: v.get() for k, v in out.items()}  # get() asserts both guards of each output
+    for b in range(B - 1):
+        assert (got["img"][b] == 0.0).all() and (got["mask"][b] == 0).all() and got["count"][b] == 0, b
+        assert (got["choose"][b] == 0).all() and (got["cloud"][b] == 0.0).all(), b
+        assert (got["xmap"][b] == 0.0).all() and (got["ymap"][b] == 0.0).all(), b
+    f, r0, c0, S = crops[-1]
+    ref = R.crop(sc["rgb"][f], sc["depth"][f], sc["mask_label"][f], r0, c0, S, T, N, k4[B - 1], 2.0, seed=77,
+                 stream_id=9, index=B - 1)
+    assert ref["count"] > N
+    for k, r in ref.items():
+        g = got[k][B - 1]
+        assert np.array_equal(g.view(np.uint32), r.view(np.uint32)) if g.dtype == np.float32 else np.array_equal(g, r), k
+
+
+def test_zoom_batch_keys_are_the_staged_windows(dev, tmp_path, monkeypatch):
+    """batch(zoom=True) hands on the window tensors the resized build staged (one upload per batch), and zoom_frame is
+    bop_frame's own tensor where that key exists."""
+    import mesh_tree
+    from pose_estimation_amd import dataset
+    staged = []
+    stage = dataset._stage_windows
+    monkeypatch.setattr(dataset, "_stage_windows", lambda *a: staged.append(stage(*a)) or staged[-1])
+    ds = PoseDataset("test", 100, False, None, 0.0, 8, cls_type="all", num_frames=4, sizes=[80, 120], n_model_pts=32,
+                     resize=40)
+    data = ds.batch([0, 1, 2, 3], dev, zoom=True)
+    assert len(staged) == 1 and all(data[k] is t for k, t in zip(("zoom_frame", "zoom_rc", "zoom_side"), staged[0]))
+    assert data["zoom_frame"].tolist() == [0, 1, 2, 3]
+    assert data["zoom_rc"].tolist() == [[b[0], b[2]] for b in ds.boxes]
+    assert data["zoom_side"].tolist() == [b[1] - b[0] for b in ds.boxes]
+    mesh_tree.write_tree(str(tmp_path), objs=(6,), per_obj=(4,))
+    ds = PoseDataset("test", 100, False, str(tmp_path), 0.0, 8, cls_type="cat", n_model_pts=150, meshes=True, resize=40)
+    data = ds.batch([0, 1, 2, 3], dev, bop=True, zoom=True)
+    assert len(staged) == 2 and data["zoom_frame"] is data["bop_frame"]
+    assert data["zoom_rc"] is staged[1][1] and data["zoom_side"] is staged[1][2]
+    assert data["zoom_rc"].tolist() == [[b[0], b[2]] for b in ds.boxes]
