@@ -929,6 +929,64 @@ int krrn_pose_refine_depth_f32(const float* verts, int Vtot, const int* faces, i
                                double damp, int B, void* ws, float* R, float* t, int* passes, int* pairs, float* rmse,
                                int* status, void* stream);
 
+/* Whole scenes in one z-buffer: every instance of a frame drawn under its own pose, one object hiding another (this
+ * project's own definition; tests/scene_ref.py restates it in numpy f64). verts f32 [Vtot][3], faces int32 [Ftot][3]
+ * (global vertex indices) and face_range int32 [N][2] as krrn_bop_vsd_f32 takes them, one range per instance; R f64
+ * [N][9] row-major, t f64 [N][3] metres, K4 f32 [N][4] = (fx, fy, cx, cy): one pose and one camera per instance;
+ * inst_range int32 [F][2] = (first instance, count) of frame f. For frame f and the integer pixel p = (col, row) of
+ * the H x W frame, in f64 without FMA contraction:
+ *   D_n(p), face_n(p)  the depth and the winning face of instance n's faces rendered under (R[n], t[n], K4[n])
+ *                      exactly as VSD renders (the same device function: near plane 1e-3, both windings, the
+ *                      inclusive bounding-box test, strict < on depth so equal depths go to the lowest face index)
+ *   winner(p)          walking the frame's instances in increasing n, the one with the smallest D_n(p) under a
+ *                      strict <: equal depths go to the lowest instance index
+ *   inst  int32 [F][H][W]  the winner's index n in the whole list, -1 where no instance covers p
+ *   depth f32 [F][H][W]    (float)D_winner(p), 0 where none
+ *   shade u8 [F][H][W]     nrm = the winning face's camera-frame normal as krrn_raster_maps_f32 defines it (flat;
+ *                          zero for a degenerate face); lam = fmin(fmax(-nrm[2], 0.0), 1.0); s = 64.0 + 191.0 lam;
+ *                          shade = (unsigned char)(int)(s + 0.5); 0 where none
+ * Every element of the three planes is written: the caller does no memset. Two launches: one block per instance
+ * writes its projected vertices' bounding box to ws (krrn_scene_render_ws(N) ints); one block per 16 x 16 tile of a
+ * frame skips the instances whose box misses the tile (which changes no output: the box is the outward-rounded hull,
+ * in the walk's own bits, of every vertex a kept face can have), walks the others, keeps each pixel's best hit in
+ * registers, and stores. No atomics, no block waits for another, nothing is read back, and a frame's planes do not
+ * depend on the rest of the batch, bit for bit. Host checks, before any HIP call: null pointer or overlapping buffers
+ * KRRN_EARG; N < 0, F < 1, Vtot < 1, Ftot < 0, H or W <= 0, H W > INT32_MAX KRRN_ESHAPE; N == 0 still writes the
+ * empty planes. inst_range and face_range are device memory and guarded by the kernel as in VSD, against N and Ftot: a
+ * negative first or count, or a first beyond the array, is an empty range; a range is cut at the array's end. */
+int krrn_scene_render_ws(int N, long long* n_ints);
+int krrn_scene_render_f64(const float* verts, int Vtot, const int* faces, int Ftot, const int* face_range,
+                          const double* R, const double* t, const float* K4, const int* inst_range, int N, int F,
+                          int H, int W, int* ws, int* inst, float* depth, unsigned char* shade, void* stream);
+
+/* The picture of a rendered scene on its frame, integer work only. rgb u8 [F][H][W][3]; est int32 [F][H][W] and shade
+ * u8 [F][H][W]: krrn_scene_render_f64's inst and shade planes; tint u8 [N][3]: a colour per instance; gt int32
+ * [F][H][W] (optional): a second id plane, drawn as outlines only; out u8 [F][H][W][3]. An id of est outside [0, N)
+ * counts as -1 everywhere. Per pixel p:
+ *   c = rgb[p]
+ *   if e = est[p] >= 0:  lit_k = (tint[e][k] shade[p] + 127) / 255;  c_k = (c_k (256 - alpha) + lit_k alpha + 128) >> 8
+ *   edge_L(p) = L[p] >= 0 and some q with |dx|, |dy| <= radius inside the frame has L[q] != L[p]
+ *   if edge_est(p):  c = tint[est[p]]
+ *   if gt and edge_gt(p):  c = (gt_r, gt_g, gt_b)
+ *   out[p] = c
+ * Host checks, before any HIP call: null pointer (gt exempt) or out overlapping an input KRRN_EARG; N < 0, F < 1, H or
+ * W <= 0, H W > INT32_MAX, alpha outside 0..256, radius outside 1..4, a colour outside 0..255 KRRN_ESHAPE. */
+int krrn_scene_overlay_u8(const unsigned char* rgb, const int* est, const unsigned char* shade,
+                          const unsigned char* tint, int N, int alpha, int radius, const int* gt, int gt_r, int gt_g,
+                          int gt_b, int F, int H, int W, unsigned char* out, void* stream);
+
+/* The signed difference between a rendered and an observed depth plane as colours. ren / obs f32 [F][H][W]; out u8
+ * [F][H][W][3]. Per pixel, in f64 without FMA contraction: r = ren, o = obs / depth_scale;
+ *   r > 0 and o > 0:  e = r - o;  k = (int)(fmin(fabs(e) / tol, 1.0) 255.0 + 0.5);
+ *                     e > 0 (255, 255 - k, 255 - k): the model is behind the observed surface (hidden, or too far);
+ *                     e < 0 (255 - k, 255 - k, 255);  e == 0 white
+ *   else r > 0:       (128, 128, 128): rendered where nothing is observed
+ *   else:             black
+ * A NaN is never > 0. Host checks, before any HIP call: null pointer or out overlapping an input KRRN_EARG; F < 1, H
+ * or W <= 0, H W > INT32_MAX, tol not finite or not > 0, depth_scale == 0 KRRN_ESHAPE. */
+int krrn_scene_depth_diff_u8(const float* ren, const float* obs, double depth_scale, double tol, int F, int H, int W,
+                             unsigned char* out, void* stream);
+
 /* BPnP forward (lib/network/dnn/BPnP.py:43-44, cv2.solvePnP(SOLVEPNP_ITERATIVE,
  * useExtrinsicGuess=True)): Levenberg-Marquardt on sum_i ||pi(z_i; y) - x_i||^2 per crop, f64,
  * from y_init. pts2d [B][n][2] pixels; pts3d [n][3] shared (z_per_crop = 0) or [B][n][3];

@@ -49,6 +49,13 @@ mask IoUs taken from the run lists on the GPU (rle.iou) and the per-image matchi
     write_gt_coco("/data/mine", "test", device)
     res = eval_coco(("/data/mine", "test"), read_detections("krrn_mine-test_seg.json"), "cuda:0")   # AP, AP50, AR100, ...
 
+Pictures of a result file. vis_results(dataset, rows, out_dir, device) is the counterpart of the toolkit's
+vis_est_poses: every image's estimates are rendered into one z-buffer (scene.render), blended over the RGB image in
+their objects' colours with outlines, the ground truth's outlines on top, and written as PNGs; diff=True adds the
+rendered against the observed depth. evaluate.test_epoch(vis_dir=...) does it for an epoch's own estimates.
+
+    vis_results(ds, read_results("krrn_tless-test.csv"), "vis", "cuda:0", diff=True)   # vis/000001/000000.png, ..._diff.png
+
 Out of scope: binary PLY, polygon segmentations, keypoints."""
 from __future__ import annotations
 
@@ -643,6 +650,83 @@ def write_result_masks(path, dataset, rows, device, chunk_images: int = 32, delt
     det, stats = result_masks(dataset, rows, device, chunk_images, delta)
     write_detections(path, det)
     return det, stats
+
+
+def _render_frames(mesh, frames, H: int, W: int):
+    """scene.render of per-frame lists of (object, R f64 [9], t f64 [3] metres, K4), each frame's list its instances in
+    order, over dataset._mesh_for's `mesh`: (scene.render's result, the instances' objects in the whole list's order)."""
+    from . import scene as kscene
+    flat = [e for fr in frames for e in fr]
+    first = list(accumulate((len(fr) for fr in frames), initial=0))
+    res = kscene.render(mesh["verts"], mesh["faces"], [mesh["range"][o] for o, _, _, _ in flat],
+                        np.stack([r for _, r, _, _ in flat]) if flat else np.zeros((0, 9)),
+                        np.stack([t for _, _, t, _ in flat]) if flat else np.zeros((0, 3)),
+                        np.asarray([k for _, _, _, k in flat], np.float32).reshape(-1, 4),
+                        [(a, len(fr)) for a, fr in zip(first, frames)], H, W)
+    return res, [o for o, _, _, _ in flat]
+
+
+def vis_results(dataset, rows, out_dir: str, device, gt: bool = True, diff: bool = False, chunk_images: int = 8,
+                alpha: int = 128, radius: int = 1, tol: float = 0.02, overwrite: bool = False) -> Dict[str, int]:
+    """Pictures of estimated poses on their frames, the counterpart of the BOP toolkit's vis_est_poses: result rows as
+    read_results returns them (t in millimetres) are drawn over the RGB image they belong to. `dataset` is a
+    PoseDataset(layout="bop", meshes=True).
+
+    Per chunk of at most `chunk_images` distinct images, RGB and depth are read once per image (tree.read_image). Each
+    image's rows become its instances, in row order, and scene.render draws them into one z-buffer, one object hiding
+    another; scene.overlay blends them over the image, each in scene.palette's colour of its object id, lit by the flat
+    shade, with weight alpha / 256 and an outline `radius` pixels wide. With `gt` the image's kept GT instances
+    (tree.instances) are rendered as a second scene, and the outlines of its instance map are drawn on top in green.
+    With `diff` scene.depth_diff colours the rendered depth against the observed one (metres, so depth_scale = 1.0),
+    saturated at `tol`. Only the finished u8 images come back to the host.
+
+    Written with PIL: {out_dir}/{scene:06d}/{im:06d}.png and, with `diff`, {im:06d}_diff.png. An existing file is
+    refused unless overwrite=True (FileExistsError, before anything is written). Returns {"images": the images written,
+    "drawn": the rows drawn on them, "ignored": the rows whose image or object the tree does not hold}."""
+    from PIL import Image
+    from . import scene as kscene
+    from .runtime import h2d
+    device = torch.device(device)
+    _require(dataset, "vis_results needs a PoseDataset with layout='bop' and meshes=True", layout=True, meshes=True)
+    tree = dataset.tree
+    mesh = dataset._mesh_for(device)
+    cam = {_key(it)[:2]: (it["K4"], float(it["depth_scale"])) for it in tree.instances}
+    by_image, ignored = _rows_by(rows, 2, lambda k: k[:2] in cam and k[2] in mesh["range"])
+    images = list(by_image)
+    paths = {key: os.path.join(out_dir, f"{key[0]:06d}", f"{key[1]:06d}") for key in images}
+    for key in images:
+        for suffix in (".png",) + (("_diff.png",) if diff else ()):
+            _refuse(paths[key] + suffix, overwrite)
+    truth: Dict[Tuple[int, int], List[Dict[str, object]]] = {}
+    for it in tree.instances if gt else ():
+        truth.setdefault(_key(it)[:2], []).append(it)
+
+    step = max(1, int(chunk_images))
+    drawn = 0
+    for lo in range(0, len(images), step):
+        ims = images[lo:lo + step]
+        read = [tree.read_image(sc, im, cam[(sc, im)][1]) for sc, im in ims]
+        rgb = h2d(torch.from_numpy(np.stack([r for r, _ in read])), device)
+        H, W = int(rgb.shape[1]), int(rgb.shape[2])
+        est, objs = _render_frames(mesh, [[(int(rows[r]["obj_id"]), *_row_pose(rows[r]), cam[key][0])
+                                            for r in by_image[key]] for key in ims], H, W)
+        outline = None
+        if gt:
+            outline = _render_frames(mesh, [[(int(it["obj"]), np.asarray(it["R"], np.float64).reshape(9),
+                                              np.asarray(it["t"], np.float64), it["K4"]) for it in truth.get(key, ())]
+                                            for key in ims], H, W)[0]["inst"]
+        pics = [kscene.overlay(rgb, est["inst"], est["shade"], kscene.palette(objs), alpha, radius, gt=outline)]
+        if diff:
+            obs = h2d(torch.from_numpy(np.stack([d for _, d in read])), device)
+            pics.append(kscene.depth_diff(est["depth"], obs, 1.0, tol))
+        host = [p.cpu().numpy() for p in pics]
+        for f, key in enumerate(ims):
+            os.makedirs(os.path.dirname(paths[key]), exist_ok=True)
+            Image.fromarray(host[0][f]).save(paths[key] + ".png")
+            if diff:
+                Image.fromarray(host[1][f]).save(paths[key] + "_diff.png")
+            drawn += len(by_image[key])
+    return {"images": len(images), "drawn": drawn, "ignored": ignored}
 
 
 def net_mask_rows(rows, runs, info, H: int, W: int):

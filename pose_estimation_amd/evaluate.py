@@ -34,8 +34,8 @@ import torch.distributed as dist
 from . import distributed as kd
 from .bop import BOP_REC, FRAME_W, TAUS, bop_errors, fold_bop, valid_by_crop
 from . import rle
-from .bop_scene import (_require, eval_coco, eval_results, net_mask_rows, write_detections, write_result_masks,
-                        write_results)
+from .bop_scene import (_require, eval_coco, eval_results, net_mask_rows, vis_results, write_detections,
+                        write_result_masks, write_results)
 from .dataset import ZOOM_KEYS, PoseDataset
 from .krrn import KRRN
 from .loss import map_losses
@@ -447,7 +447,8 @@ def test_epoch(model: KRRN, dataset: PoseDataset, bs: int = 64, device=None, opt
                group=None, pose_solver: str = "pnp", refine: Optional[str] = None,
                bop: bool = False, bop_csv: Optional[str] = None, select: Optional[str] = None,
                match: bool = False, seg_json: Optional[str] = None, seg_source: str = "render",
-               coco: bool = False, zoom: int = 0) -> Dict[str, object]:
+               coco: bool = False, zoom: int = 0, vis_dir: Optional[str] = None,
+               vis_diff: bool = False) -> Dict[str, object]:
     """Trainer.test_epoch over `dataset`. world/rank default to the initialised process group
     (1/0 without one). `criterion` enables the per-crop map-loss terms (dis_xyz / dis_mask /
     dis_normal) when the batches carry GT maps, i.e. for a PoseDataset built with gt_maps=True (a
@@ -502,7 +503,13 @@ def test_epoch(model: KRRN, dataset: PoseDataset, bs: int = 64, device=None, opt
     whose last pass cut a new window (zoom.pose_windows' status 0), "kept_bad_pose" those that kept their window because
     the pose put a point behind the camera or at a non-finite pixel (status 1), "kept_outside" those whose projection
     missed the frame (status 2)}. Whether the extra passes improve any accuracy figure is unmeasured.
-    seg_source="net" is refused on every dataset built with resize, so it never meets zoom."""
+    seg_source="net" is refused on every dataset built with resize, so it never meets zoom.
+    `vis_dir` (None by default: nothing is queued, and every key is what it was, bit for bit; needs a dataset with
+    layout="bop" and meshes=True and world == 1, which is all one GPU can test; ValueError otherwise, before any batch is
+    built) draws the epoch's estimates on their frames: after the epoch the result rows, exactly as `bop_csv` writes
+    them, go through bop_scene.vis_results(dataset, rows, vis_dir, device, diff=vis_diff), which writes one PNG per
+    image that has a row (and with `vis_diff` one of the rendered against the observed depth). One key is added, "vis":
+    what vis_results returned; no other key changes."""
     device = torch.device(device) if device is not None else next(model.parameters()).device
     _check_zoom(zoom, dataset)
     if seg_source not in ("render", "net"):
@@ -531,6 +538,9 @@ def test_epoch(model: KRRN, dataset: PoseDataset, bs: int = 64, device=None, opt
                          "provisionally: bop=True needs match=True on it")
     if bop_csv:
         _require(dataset, "bop_csv writes BOP's scene / image ids: it needs a PoseDataset with layout='bop'", layout=True)
+    if vis_dir:
+        _require(dataset, "vis_dir draws the estimates on a BOP tree's frames: it needs a PoseDataset with layout='bop' "
+                 "and meshes=True", layout=True, meshes=True)
     if world is None:
         world = dist.get_world_size(group) if dist.is_initialized() else 1
     if rank is None:
@@ -541,9 +551,11 @@ def test_epoch(model: KRRN, dataset: PoseDataset, bs: int = 64, device=None, opt
         raise ValueError("seg_source='net' runs on one rank: gathering the ranks' run lists is not built")
     if zoom and world > 1:
         raise ValueError("zoom runs on one rank: it is not tested across ranks, and the status counts are not gathered")
+    if vis_dir and world > 1:
+        raise ValueError("vis_dir runs on one rank: it is not tested across ranks")
     sizes = [dataset.crop_size(i) for i in range(len(dataset))]
     mine = kd.bucket_shard(sizes, world, rank)
-    want_poses = bool(bop_csv or match or seg_json)
+    want_poses = bool(bop_csv or match or seg_json or vis_dir)
     local, runs, zstat = _eval_epoch(model, dataset, mine, bs, device, opt_pose, criterion is not None, pose_solver,
                                      refine, bool(bop), want_poses, select, net, int(zoom))
     net_runs = {crop: (r, info) for crop, r, info in runs or ()}
@@ -603,6 +615,8 @@ def test_epoch(model: KRRN, dataset: PoseDataset, bs: int = 64, device=None, opt
             if world > 1:
                 dist.broadcast_object_list(res, src=0, group=group)
             out["bop"] = res[0]
+        if vis_dir:
+            out["vis"] = vis_results(dataset, rows, vis_dir, device, diff=bool(vis_diff))
     if world > 1:
         # the ranks' own crop / success tallies, summed, must equal the gathered table's
         key = "add_f" if opt_pose else "add_b"
