@@ -777,6 +777,55 @@ int krrn_bop_match_f64(const double* score, int Etot, const double* err, long lo
                        const int* n_top, int G, int GTtot, int max_est, int max_gt, int* match, int* tp,
                        void* stream);
 
+/* What BOP's calc_model_info script computes for O object models at once: the diameter (squared) and the axis-aligned
+ * box. verts f32 [Vtot][3] in any unit; vert_range int32 [O][2] = (first vertex, count), device memory; max_v: the
+ * caller's bound on the counts, from which the grid is sized (as max_est / max_gt above). Per object o, in f64 without
+ * FMA contraction:
+ *   d2[o]     = max over the object's vertex pairs (i, j) of ((dx dx + dy dy) + dz dz), dx = (double)x_i - (double)x_j;
+ *               the walk takes a term with > starting from 0.0, so a NaN term never wins and 0 or 1 vertices give 0.0
+ *   box[o][6] = per axis the minimum (x, y, z), then the maximum (x, y, z), over the object's vertices, taken with < / >
+ *               from +inf / -inf: a NaN coordinate is ignored and an empty range leaves +inf / -inf
+ * The root is not taken: the diameter is sqrt(d2[o]) on the host. The kernels guard the ranges: a negative first or
+ * count, a count above max_v or a range reaching past Vtot is an empty range (not cut). max and min do not depend on
+ * order, so any decomposition gives the same bits. Here: one block per object for the box; for d2 up to 512 blocks
+ * per object stride over row tiles of 256 vertices held in registers while the column vertices pass through LDS 1024
+ * at a time, the column tiles below the diagonal skipped, and each block's maximum is folded with an integer
+ * atomicMax on the bit pattern of the non-negative double (order-free; no floating-point atomics, no workspace). An
+ * object's outputs do not depend on what else is in the batch, bit for bit. Host checks, before any HIP call: null or
+ * overlapping buffers KRRN_EARG; O outside 1..65535, Vtot or max_v < 1 KRRN_ESHAPE. */
+int krrn_model_extent_f64(const float* verts, int Vtot, const int* vert_range, int O, int max_v, double* d2,
+                          double* box, void* stream);
+
+/* How well each declared symmetry maps an object's mesh onto itself. verts / faces / face_range as
+ * krrn_raster_maps_f32 (faces index into verts; a face with an index outside [0, Vtot) is skipped); vert_range int32
+ * [O][2]; syms f64 [NStot][12] = row-major S then St (bop.symmetry_set rows, in the vertices' unit), sym_range int32
+ * [O][2]; max_v / max_f: the caller's bounds on the vertex / face counts. The ranges are device memory and guarded as
+ * in krrn_model_extent_f64 (a bad range is an empty one). Per symmetry s of object o, in f64 without FMA contraction:
+ *   res2[s] = max over the object's vertices p of  min over the object's faces of dist2(S p, triangle)
+ *   S p = ((S0 x + S1 y) + S2 z) + St; every dot product u.v = (ux vx + uy vy) + uz vz; the corners a, b, c are the
+ *   f32 vertices widened to f64. The closest point q, the first test that holds deciding:
+ *     ab = b - a, ac = c - a, ap = p - a; d1 = ab.ap, d2 = ac.ap;      d1 <= 0 && d2 <= 0           -> q = a
+ *     bp = p - b; d3 = ab.bp, d4 = ac.bp;                              d3 >= 0 && d4 <= d3          -> q = b
+ *     vc = d1 d4 - d3 d2;                                              vc <= 0 && d1 >= 0 && d3 <= 0 -> q = a + (d1 / (d1 - d3)) ab
+ *     cp = p - c; d5 = ab.cp, d6 = ac.cp;                              d6 >= 0 && d5 <= d6          -> q = c
+ *     vb = d5 d2 - d1 d6;                                              vb <= 0 && d2 >= 0 && d6 <= 0 -> q = a + (d2 / (d2 - d6)) ac
+ *     va = d3 d6 - d5 d4;  va <= 0 && d4 - d3 >= 0 && d5 - d6 >= 0  -> q = b + ((d4 - d3) / ((d4 - d3) + (d5 - d6))) (c - b)
+ *     otherwise den = 1.0 / ((va + vb) + vc);                          q = (a + ab (vb den)) + ac (vc den)
+ *   dist2 = (p - q).(p - q). A triangle collapsed to a point, or to a line with three distinct corners, gives a finite
+ *   point; with a == b the third case can divide 0 by 0, and the NaN distance never wins the face walk.
+ * The face walk takes a distance with < from +inf (a NaN never wins), the vertex walk with > from 0.0; a vertex none of
+ * whose distances is finite (a NaN vertex) contributes +inf, so broken input shows as an infinite residual. No vertices
+ * give 0.0; vertices with an empty (or bad) face range give +inf. Every res2[s] that an object owns is written by the
+ * call; the objects' symmetry ranges must not overlap (the lowest object wins), and a symmetry that no object's
+ * sym_range owns keeps what the buffer held. One block per (symmetry, tile of 256 vertices) with the transformed
+ * vertices in registers, the faces' nine f64 coordinates staged through LDS 256 at a time, and the same integer
+ * atomicMax fold: order-free, so a symmetry's residual does not depend on what else is in the batch, bit for bit.
+ * Host checks, before any HIP call: null (faces only with Ftot > 0) or overlapping buffers KRRN_EARG; O, Vtot, NStot,
+ * max_v, max_f < 1, Ftot < 0, or NStot x min(ceil(max_v / 256), 256) > 2^23 KRRN_ESHAPE. */
+int krrn_symmetry_residual_f64(const float* verts, int Vtot, const int* faces, int Ftot, const int* vert_range,
+                               const int* face_range, const double* syms, int NStot, const int* sym_range, int O,
+                               int max_v, int max_f, double* res2, void* stream);
+
 /* IoU of P pairs of run-length encoded masks, from the run lists alone: no plane is decoded and no H or W is
  * needed (a mask is its runs). counts int32 [n_counts]: the run lengths of the n masks, concatenated; offs int32
  * [n + 1] (device memory): mask i owns counts[offs[i] .. offs[i + 1]), as krrn_rle_decode_u8 takes them; pair int32

@@ -28,16 +28,18 @@ Drop-in API (the reference's names):
                                           segmentation result files, mask IoU from the run lists on the GPU
     scene.render / scene.overlay / bop_scene.vis_results / test_epoch(vis_dir=...)  all instances of a frame in one
                                           z-buffer, and the estimates drawn on their frames (this project's own)
+    models.extent / models.symmetry_residual / bop_scene.write_models_info / check_models_info  model diameters and
+                                          boxes (BOP's calc_model_info) and a check of the declared symmetries
 """
 from .config import CONFIG, Cfg, make_config  # noqa: F401
 from .krrn import KRRN  # noqa: F401
 from . import bpnp, dataset, fps  # noqa: F401
 from .loss import KRRNLoss  # noqa: F401
-from . import bop, coco, depth_refine, icp, raster, rle, scene, verify  # noqa: F401
+from . import bop, coco, depth_refine, icp, models, raster, rle, scene, verify  # noqa: F401
 from .pose import (add_icp_ops, add_umeyama_ops, get_pose, get_pose_umeyama, refine_pose_depth,  # noqa: F401
                    refine_pose_icp, select_pose)
 from .umeyama import estimateSimilarityTransform  # noqa: F401
 
 __all__ = ["KRRN", "KRRNLoss", "get_pose", "get_pose_umeyama", "add_umeyama_ops", "estimateSimilarityTransform",
-           "bop", "coco", "depth_refine", "icp", "raster", "rle", "scene", "verify", "refine_pose_depth", "refine_pose_icp", "select_pose",
+           "bop", "coco", "depth_refine", "icp", "models", "raster", "rle", "scene", "verify", "refine_pose_depth", "refine_pose_icp", "select_pose",
            "add_icp_ops", "make_config", "CONFIG", "Cfg"]

@@ -3,6 +3,7 @@ format of LM-O, YCB-V, T-LESS ... as published): the index of a tree, the GPU co
 calc_gt_masks / calc_gt_info scripts, and BOP's result CSV.
 
     tree = BopTree("/data/lmo", split="test", targets="/data/lmo/test_targets_bop19.json", meshes=True)
+    write_models_info("/data/mine", device)                      # for a tree that ships no models/models_info.json
     write_gt_info("/data/mine", "test", device, masks=True)      # for a tree that ships no scene_gt_info.json
     write_gt_coco("/data/mine", "test", device)                  # scene_gt_coco.json: COCO ground truth, RLE masks
     write_results("krrn_lmo-test.csv", rows); rows = read_results("krrn_lmo-test.csv")
@@ -56,7 +57,14 @@ rendered against the observed depth. evaluate.test_epoch(vis_dir=...) does it fo
 
     vis_results(ds, read_results("krrn_tless-test.csv"), "vis", "cuda:0", diff=True)   # vis/000001/000000.png, ..._diff.png
 
-Out of scope: binary PLY, polygon segmentations, keypoints."""
+Model facts. model_info(root, device) is the counterpart of the toolkit's calc_model_info: every model's diameter (the
+maximum over all vertex pairs, models.extent on the GPU) and box; write_models_info writes them as
+models/models_info.json, and check_models_info(root, device) sets an existing file beside its PLYs: the diameter and
+box differences and, per declared symmetry, how far it moves the mesh off itself (models.symmetry_residual).
+
+    write_models_info("/data/mine", device); rep = check_models_info("/data/tless", device)   # rep[obj]["residual"]
+
+Out of scope: binary PLY, polygon segmentations, keypoints, finding symmetries."""
 from __future__ import annotations
 
 import json
@@ -564,6 +572,115 @@ def write_gt_coco(root: str, split: str, device, visib: bool = True, min_visib: 
         with open(cpath, "w") as f:
             json.dump(coco, f)
         out[sc] = coco
+    return out
+
+
+MODEL_KEYS = ("diameter", "min_x", "min_y", "min_z", "size_x", "size_y", "size_z")   # calc_model_info's seven
+
+
+def _model_ids(root: str) -> List[int]:
+    """The ids of the models/obj_%06d.ply files of a tree, sorted."""
+    names = os.listdir(os.path.join(root, "models"))
+    return sorted(int(n[4:10]) for n in names if len(n) == 14 and n.startswith("obj_") and n.endswith(".ply")
+                  and n[4:10].isdigit())
+
+
+def _stage_models(root: str, objs: Sequence[int], device, faces: bool):
+    """The models of `objs` on `device`, concatenated: (verts f32 [Vtot, 3] metres as every loader of the project
+    holds them (ply_vtx / 1000 rounded to f32), faces int32 [Ftot, 3] into verts or None, vert_range, face_range as
+    host int32 [O, 2])."""
+    from .dataset import ply_faces, ply_vtx
+    from .runtime import h2d
+    vs, fs, vr, fr = [], [], [], []
+    v0 = f0 = 0
+    for obj in objs:
+        p = os.path.join(root, "models", f"obj_{int(obj):06d}.ply")
+        v = (ply_vtx(p) / 1000.0).astype(np.float32).reshape(-1, 3)
+        f = ply_faces(p).astype(np.int32).reshape(-1, 3) if faces else np.zeros((0, 3), np.int32)
+        vs.append(v), fs.append(f + v0), vr.append((v0, len(v))), fr.append((f0, len(f)))
+        v0, f0 = v0 + len(v), f0 + len(f)
+    verts = h2d(torch.from_numpy(np.concatenate(vs).reshape(-1, 3)), device)
+    tri = h2d(torch.from_numpy(np.concatenate(fs).reshape(-1, 3).astype(np.int32)), device) if faces else None
+    return verts, tri, torch.tensor(vr, dtype=torch.int32).reshape(-1, 2), torch.tensor(fr, dtype=torch.int32).reshape(-1, 2)
+
+
+def _model_entries(objs: Sequence[int], ext) -> Dict[int, Dict[str, float]]:
+    """models.extent's result (metres) as models_info.json entries (millimetres): every number is the f64 metre value
+    x 1000.0, and size = max x 1000 - min x 1000."""
+    out = {}
+    for j, obj in enumerate(objs):
+        lo = [float(x) * 1000.0 for x in ext["min"][j].tolist()]
+        hi = [float(x) * 1000.0 for x in ext["max"][j].tolist()]
+        out[int(obj)] = {"diameter": float(ext["diameter"][j]) * 1000.0, "min_x": lo[0], "min_y": lo[1], "min_z": lo[2],
+                         "size_x": hi[0] - lo[0], "size_y": hi[1] - lo[1], "size_z": hi[2] - lo[2]}
+    return out
+
+
+def model_info(root: str, device, objs: Optional[Sequence[int]] = None) -> Dict[int, Dict[str, float]]:
+    """The GPU counterpart of BOP's calc_model_info: {obj: {"diameter", "min_x", "min_y", "min_z", "size_x", "size_y",
+    "size_z"}} in the files' millimetres, as Python floats, for every models/obj_%06d.ply of `root` (or those named).
+    The PLYs are read with dataset.ply_vtx (ASCII only: a binary PLY keeps raising its ValueError), all objects go
+    through one models.extent call, concatenated, and the diameter is the maximum over all vertex pairs (no
+    subsampling). The numbers describe the vertices that the project renders and scores with, load_models' f32 metres
+    (the file's millimetres / 1000), scaled back by 1000 in f64: they agree with the file's own decimals to f32
+    rounding (a few 1e-8 of the value)."""
+    from . import models
+    objs = _model_ids(root) if objs is None else [int(o) for o in objs]
+    if not objs:
+        return {}
+    verts, _, vr, _ = _stage_models(root, objs, device, faces=False)
+    return _model_entries(objs, models.extent(verts, vr))
+
+
+def write_models_info(root: str, device, overwrite: bool = False) -> Dict[int, Dict[str, object]]:
+    """Writes models/models_info.json (BOP's format, millimetres) from model_info(root, device): the one file without
+    which BopTree does not open a tree. Refuses an existing file unless overwrite=True (FileExistsError, before
+    anything is computed); with overwrite=True an existing file's `symmetries_discrete` / `symmetries_continuous` are
+    carried over per object, since neither this nor calc_model_info produces them. Returns the written entries."""
+    path = os.path.join(root, "models", "models_info.json")
+    _refuse(path, overwrite)
+    old = _load_json(path) if os.path.exists(path) else {}
+    out: Dict[int, Dict[str, object]] = {}
+    for obj, e in model_info(root, device).items():
+        out[obj] = dict(e)
+        for k in ("symmetries_discrete", "symmetries_continuous"):
+            if k in old.get(obj, {}):
+                out[obj][k] = old[obj][k]
+    _save_json(path, out)
+    return out
+
+
+def check_models_info(root: str, device, syms: bool = True) -> Dict[int, Dict[str, object]]:
+    """Compares a tree's models/models_info.json with its PLYs, per object that the file lists: {"diameter_file",
+    "diameter" (computed as model_info does), "extent_diff": the largest absolute difference of the six min_* / size_*
+    numbers, all millimetres} and, with syms=True (which needs the PLYs' faces), {"residual": the list of
+    models.symmetry_residual of every member of bop.symmetry_set(...) of the file's entry (the identity first) as a
+    fraction of the computed diameter, "worst": the index of the largest}. It reports and does not judge: no
+    threshold, nothing raised. An exact symmetry of the mesh gives 0, a symmetry of the shape that the mesh
+    approximates about its tessellation's sag, a wrong entry (mm / m mix-up, wrong axis, offset off the axis) a
+    sizeable fraction."""
+    from . import models
+    info = _load_json(os.path.join(root, "models", "models_info.json"))
+    objs = sorted(info)
+    if not objs:
+        return {}
+    verts, tri, vr, fr = _stage_models(root, objs, device, faces=syms)
+    calc = _model_entries(objs, models.extent(verts, vr))
+    out: Dict[int, Dict[str, object]] = {}
+    for obj in objs:
+        e, c = info[obj], calc[obj]
+        out[obj] = {"diameter_file": float(e["diameter"]), "diameter": c["diameter"],
+                    "extent_diff": max(abs(float(e[k]) - c[k]) for k in MODEL_KEYS[1:])}
+    if syms:
+        sets = [bop.symmetry_set(info[o].get("symmetries_discrete"), info[o].get("symmetries_continuous")) for o in objs]
+        first = [0] + list(accumulate(len(s) for s in sets))
+        sr = torch.tensor([(first[j], len(s)) for j, s in enumerate(sets)], dtype=torch.int32)
+        res = models.symmetry_residual(verts, tri, vr, fr, torch.from_numpy(np.concatenate(sets)), sr).tolist()
+        for j, obj in enumerate(objs):
+            dia_m = out[obj]["diameter"] / 1000.0
+            frac = [r / dia_m for r in res[first[j]:first[j + 1]]]
+            out[obj]["residual"] = frac
+            out[obj]["worst"] = max(range(len(frac)), key=lambda i: frac[i])
     return out
 
 
