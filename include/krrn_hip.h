@@ -826,6 +826,41 @@ int krrn_symmetry_residual_f64(const float* verts, int Vtot, const int* faces, i
                                const int* face_range, const double* syms, int NStot, const int* sym_range, int O,
                                int max_v, int max_f, double* res2, void* stream);
 
+/* n points drawn uniformly on the surface of each of O triangle meshes (area-weighted face choice, then the
+ * square-root barycentric map: the reference's tools/script/sample_model.py random_point), with the face's flat normal.
+ * verts f32 [Vtot][3] / faces int32 [Ftot][3] as krrn_symmetry_residual_f64; face_range int32 [O][2], device memory,
+ * guarded as in krrn_model_extent_f64 (a bad range is an empty one) with max_f the caller's bound on the face counts;
+ * row_id int32 [O], each >= 0: the generator row of each object (an object's samples depend on its row, the seed and
+ * stream_id only, not on its place in the call). cum f64 [O][max_f]: caller-owned workspace and output; pts, nrm f32
+ * [O][n][3]; face int32 [O][n]; status int32 [O]. Per object of F faces, in f64 without FMA contraction, every product
+ * and sum rounded on its own:
+ *   weight   face k (numbered within the range) with corners a, b, c widened to f64: e1 = b - a, e2 = c - a,
+ *            N = (e1y e2z - e1z e2y, e1z e2x - e1x e2z, e1x e2y - e1y e2x), A2 = (Nx Nx + Ny Ny) + Nz Nz,
+ *            w_k = sqrt(A2) if A2 > 0 && A2 < inf, else 0 (a NaN corner falls out through the comparison); a face with
+ *            an index outside [0, Vtot) has w_k = 0
+ *   cum      in tiles of 256 faces: within tile j, run starts at 0 and takes run = run + w_k in face order;
+ *            cum[k] = base_j + run with base_0 = 0 and base_{j+1} = base_j + (tile j's last run). Non-decreasing by
+ *            construction; total = cum[F - 1], and the surface area is total / 2
+ *   draws    sample i: r_q = the generator's value 4 i + q of (seed, stream_id, row_id[o]), q = 0..3 (the generator
+ *            of krrn_randperm_i32)
+ *   face     m = ((r0 << 32) | r1) >> 11 (53 bits), target = ((double)m * 2^-53) * total; the sample's face is the
+ *            first k with cum[k] > target, or F - 1 if none (only a total that is not finite gets there): a face of
+ *            weight 0 is never chosen
+ *   point    u1 = (double)r2 * 2^-32, u2 = (double)r3 * 2^-32, s = sqrt(u1); wa = 1 - s, wb = s * (1 - u2), wc = s * u2;
+ *            per axis p = (wa a + wb b) + wc c, cast once to f32
+ *   normal   N / w_k per component, cast once to f32 (the flat normal in the faces' winding)
+ * total == 0 (an empty or bad range, or only faces of weight 0) gives status 1, pts = nrm = 0 and face = -1; otherwise
+ * status 0. (A face reached through `none` whose index leaves [0, Vtot) keeps pts = nrm = 0.) Three launches: a thread
+ * per face stores w_k into cum; one block per object forms the tile runs (a thread per tile) and walks the tile bases
+ * in order; a thread per sample draws, searches its object's cum row by bisection and stores. No atomics, no
+ * floating-point value combined across lanes, no workspace beyond cum, no read-back: bit-reproducible, and an
+ * object's outputs do not depend on what else is in the batch. Host checks, before any HIP call: a null buffer (faces
+ * only with Ftot > 0) KRRN_EARG; O outside 1..65535, Vtot < 1, Ftot < 0, max_f < 1 or n outside 1..2^28 (4 i + 3 stays
+ * inside 32 bits) KRRN_ESHAPE. */
+int krrn_surface_sample_f64(const float* verts, int Vtot, const int* faces, int Ftot, const int* face_range,
+                            const int* row_id, int O, int max_f, int n, long long seed, unsigned int stream_id,
+                            double* cum, float* pts, float* nrm, int* face, int* status, void* stream);
+
 /* IoU of P pairs of run-length encoded masks, from the run lists alone: no plane is decoded and no H or W is
  * needed (a mask is its runs). counts int32 [n_counts]: the run lengths of the n masks, concatenated; offs int32
  * [n + 1] (device memory): mask i owns counts[offs[i] .. offs[i + 1]), as krrn_rle_decode_u8 takes them; pair int32

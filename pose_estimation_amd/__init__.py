@@ -30,6 +30,8 @@ Drop-in API (the reference's names):
                                           z-buffer, and the estimates drawn on their frames (this project's own)
     models.extent / models.symmetry_residual / bop_scene.write_models_info / check_models_info  model diameters and
                                           boxes (BOP's calc_model_info) and a check of the declared symmetries
+    models.sample_surface / bop_scene.write_models_eval / PoseDataset(model_points="surface")  model points drawn
+                                          uniformly on the mesh surface, then FPS (tools/script/sample_model.py:35-76)
 """
 from .config import CONFIG, Cfg, make_config  # noqa: F401
 from .krrn import KRRN  # noqa: F401

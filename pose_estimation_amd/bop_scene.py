@@ -64,6 +64,12 @@ box differences and, per declared symmetry, how far it moves the mesh off itself
 
     write_models_info("/data/mine", device); rep = check_models_info("/data/tless", device)   # rep[obj]["residual"]
 
+Resampled models. write_models_eval(root, device, n=...) writes models_eval/obj_%06d.ply: n points drawn uniformly on
+each model's surface with their normals (models.sample_surface: area-weighted faces, FPS thinning), in the model's own
+unit, as ASCII PLY without faces.
+
+    write_models_eval("/data/mine", device, n=4096)
+
 Out of scope: binary PLY, polygon segmentations, keypoints, finding symmetries."""
 from __future__ import annotations
 
@@ -165,13 +171,20 @@ class BopTree:
     same instance). That association is provisional: it feeds only those columns, and no BOP recall reads it
     (eval_results matches estimates to instances by their pose errors). A target with fewer qualifying rows than
     `inst_count` adds its key to `missed` once per missing estimate, so len(items) + len(missed) is the sum of
-    `inst_count`; `det_stats` keeps its meaning ("used" = the rows that became items)."""
+    `inst_count`; `det_stats` keeps its meaning ("used" = the rows that became items).
+
+    model_points: "vertices" (the random vertex subset above, which refuses a model with fewer than n_model_pts
+    vertices) or "surface" (needs meshes=True): `model_points` stays empty here and PoseDataset fills it with
+    models.sample_surface's points before its first batch."""
 
     def __init__(self, root: str, split: str = "test", targets: Optional[str] = None,
                  objlist: Optional[Sequence[int]] = None, n_model_pts: int = 2600, seed: int = 0, meshes: bool = False,
-                 min_visib: float = 0.1, detections=None, det_min_score: float = 0.0, det_per_target: str = "best"):
+                 min_visib: float = 0.1, detections=None, det_min_score: float = 0.0, det_per_target: str = "best",
+                 model_points: str = "vertices"):
         if det_per_target not in ("best", "inst_count"):
             raise ValueError(f"det_per_target must be 'best' or 'inst_count', got {det_per_target!r}")
+        if model_points == "surface" and not meshes:
+            raise ValueError("model_points='surface' samples the model points on the objects' meshes: it needs meshes=True")
         self.root, self.split = root, split
         self.det_per_target = det_per_target
         self.missed: List[Tuple[int, int, int]] = []
@@ -233,6 +246,8 @@ class BopTree:
             oi = self.info.get(obj, {})
             if meshes:
                 self.symmetries[obj] = bop.symmetry_set(oi.get("symmetries_discrete"), oi.get("symmetries_continuous"))
+            if model_points == "surface":  # PoseDataset samples them on the mesh before its first batch
+                continue
             if len(pts) < n_model_pts:
                 raise ValueError(f"obj_{obj:06d}.ply has {len(pts)} vertices < num_pt_mesh_large = {n_model_pts}")
             if len(pts) > n_model_pts:
@@ -585,17 +600,17 @@ def _model_ids(root: str) -> List[int]:
                   and n[4:10].isdigit())
 
 
-def _stage_models(root: str, objs: Sequence[int], device, faces: bool):
+def _stage_models(root: str, objs: Sequence[int], device, faces: bool, unit: float = 1000.0):
     """The models of `objs` on `device`, concatenated: (verts f32 [Vtot, 3] metres as every loader of the project
-    holds them (ply_vtx / 1000 rounded to f32), faces int32 [Ftot, 3] into verts or None, vert_range, face_range as
-    host int32 [O, 2])."""
+    holds them (ply_vtx / 1000 rounded to f32; unit=1.0 keeps the file's own f32 values), faces int32 [Ftot, 3] into
+    verts or None, vert_range, face_range as host int32 [O, 2])."""
     from .dataset import ply_faces, ply_vtx
     from .runtime import h2d
     vs, fs, vr, fr = [], [], [], []
     v0 = f0 = 0
     for obj in objs:
         p = os.path.join(root, "models", f"obj_{int(obj):06d}.ply")
-        v = (ply_vtx(p) / 1000.0).astype(np.float32).reshape(-1, 3)
+        v = (ply_vtx(p) / unit).astype(np.float32).reshape(-1, 3)
         f = ply_faces(p).astype(np.int32).reshape(-1, 3) if faces else np.zeros((0, 3), np.int32)
         vs.append(v), fs.append(f + v0), vr.append((v0, len(v))), fr.append((f0, len(f)))
         v0, f0 = v0 + len(v), f0 + len(f)
@@ -648,6 +663,43 @@ def write_models_info(root: str, device, overwrite: bool = False) -> Dict[int, D
                 out[obj][k] = old[obj][k]
     _save_json(path, out)
     return out
+
+
+def write_models_eval(root: str, device, n: int = 4096, oversample: int = 4, seed: int = 0, overwrite: bool = False,
+                      objs: Optional[Sequence[int]] = None) -> Dict[int, str]:
+    """Writes models_eval/obj_%06d.ply for every models/obj_%06d.ply of `root` (or those named): n points drawn
+    uniformly on the model's surface with their flat normals (models.sample_surface, thinned by FPS from n x oversample
+    candidates), the resampled models that BOP evaluates on. The samples are taken on the file's own f32 vertices, so
+    the output is in the model's own unit. Each file is ASCII with `x y z nx ny nz` per vertex and `element face 0`,
+    every number printed with 9 significant digits: dataset.ply_vtx reads back the sampled f32 bits. The generator row
+    is the object id, so one object written alone gets the same file as in a full write. Refuses an existing file
+    unless overwrite=True (FileExistsError, before anything is computed); a model without area raises ValueError
+    before anything is written. The PLYs are read with dataset.ply_vtx / ply_faces (ASCII only). Returns {obj: path}."""
+    from . import models
+    objs = _model_ids(root) if objs is None else [int(o) for o in objs]
+    out_dir = os.path.join(root, "models_eval")
+    paths = {obj: os.path.join(out_dir, f"obj_{obj:06d}.ply") for obj in objs}
+    for path in paths.values():
+        _refuse(path, overwrite)
+    if not objs:
+        return {}
+    verts, tri, _, fr = _stage_models(root, objs, device, faces=True, unit=1.0)
+    s = models.sample_surface(verts, tri, fr, n, seed=seed, row_id=torch.tensor(objs, dtype=torch.int32),
+                              oversample=oversample)
+    status = s["status"].cpu().tolist()
+    bad = [obj for obj, st in zip(objs, status) if st != 0]
+    if bad:
+        raise ValueError(f"models without surface area (no faces, or only degenerate ones): {bad}")
+    rows = torch.cat([s["points"], s["normals"]], dim=2).cpu().numpy()
+    os.makedirs(out_dir, exist_ok=True)
+    for j, obj in enumerate(objs):
+        head = ["ply", "format ascii 1.0", "comment surface samples of models/obj_%06d.ply" % obj,
+                f"element vertex {n}"] + [f"property float {k}" for k in ("x", "y", "z", "nx", "ny", "nz")] + [
+                "element face 0", "property list uchar int vertex_indices", "end_header"]
+        with open(paths[obj], "w") as f:
+            f.write("\n".join(head) + "\n")
+            f.write("".join(" ".join("%.9g" % x for x in row) + "\n" for row in rows[j]))
+    return paths
 
 
 def check_models_info(root: str, device, syms: bool = True) -> Dict[int, Dict[str, object]]:

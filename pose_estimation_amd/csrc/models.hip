@@ -26,6 +26,7 @@
 // bit-reproducible, and an object's or a symmetry's do not depend on what else is in the batch.
 #include <math.h>
 
+#include "krrn_range.h"   // mod_range
 #include "krrn_raster.h"  // Span, rast_overlap
 
 namespace {
@@ -37,15 +38,6 @@ constexpr int kResRows = 256;      // vertex tile of the residual (models.py RES
 constexpr int kResFaces = 256;     // face tile staged in LDS as f64 [kResFaces][9] (18 KiB) (models.py RESIDUAL_C)
 constexpr int kResMaxTiles = 256;  // vertex-tile blocks per symmetry, striding
 constexpr int kModWaves = 4;
-
-// a (first, count) range of device memory: negative, longer than the caller's bound or reaching past `total` is an
-// empty range (not cut: a range that leaves the array is the caller's mistake, and half an object has no diameter)
-__device__ __forceinline__ void mod_range(const int* range, int o, int total, int bound, long long& first, int& count) {
-  first = range[2 * o];
-  const long long n = range[2 * o + 1];
-  const bool ok = first >= 0 && n >= 0 && n <= bound && first + n <= total;
-  count = ok ? (int)n : 0;
-}
 
 __device__ __forceinline__ double mod_shfl_down(double v, int off) {
   return __longlong_as_double(__shfl_down(__double_as_longlong(v), off));

@@ -9,22 +9,9 @@
 //   krrn_rng_advance      seed += 1 (last node of a replayed step).
 // The 64-bit seed lives in device memory; `stream` separates independent draws.
 #include "krrn_common.h"
+#include "krrn_rng.h"  // mix64, rand32
 
 namespace {
-
-__device__ __forceinline__ unsigned long long mix64(unsigned long long z) {
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-
-__device__ __forceinline__ unsigned int rand32(unsigned long long seed, unsigned int stream, unsigned int row,
-                                               unsigned int i) {
-  const unsigned long long a = mix64(seed ^ (0xD1B54A32D192ED03ull * (stream + 1)));
-  const unsigned long long b = mix64(a + 0x632BE59BD9B4E019ull * (row + 1));
-  return (unsigned int)(mix64(b + i) >> 32);
-}
 
 constexpr int kPermMax = 4096;
 

@@ -59,6 +59,7 @@ from . import rle as _rle
 from .bop import symmetry_set
 from .bop_scene import BopTree
 from .config import CONFIG, LM_OBJLIST, OBJ_DICT, SYM_OBJ, models_info
+from .models import FPS_MAX, sample_surface
 from .raster import N_REGIONS, finish_maps, region_points, render_maps
 from .runtime import h2d, ptr, stream_ptr
 from .synthetic import LM_K, rand_rotation
@@ -378,7 +379,7 @@ class _LinemodTree:
     pose and detection box from gt.yml; frames are read on demand."""
 
     def __init__(self, root: str, mode: str, objlist: Sequence[int], n_model_pts: int, seed: int,
-                 meshes: bool = False):
+                 meshes: bool = False, model_points: str = "vertices"):
         import yaml
         self.root, self.mode = root, mode
         self.items: List[Dict[str, object]] = []
@@ -420,6 +421,8 @@ class _LinemodTree:
                 self.mesh[obj] = (pts.astype(np.float32), tri)
                 oi = tree_info.get(obj, {})
                 self.symmetries[obj] = symmetry_set(oi.get("symmetries_discrete"), oi.get("symmetries_continuous"))
+            if model_points == "surface":  # PoseDataset samples them on the mesh before its first batch
+                continue
             if len(pts) < n_model_pts:
                 # the reference's random.sample(range(len(pts)), len(pts) - num_pt_mesh_large) raises here
                 # too (batchdataset.py:700-704): every crop's ADD(-S) runs over exactly n_model_pts points
@@ -488,7 +491,15 @@ class PoseDataset(torch.utils.data.Dataset):
     are the resized pixels' centres in the frame, and the cloud is made of the frame's own depth pixels, so PnP,
     verification, refinement and the result files read what they always read. Works on every layout, with or without
     detections; refused (ValueError) with gt_maps=True: the GT maps are not resampled. Only such a dataset can cut
-    its crops again about an estimated pose (batch(..., zoom=True), zoom_batch; evaluate.test_epoch(..., zoom=n))."""
+    its crops again about an estimated pose (batch(..., zoom=True), zoom_batch; evaluate.test_epoch(..., zoom=n)).
+
+    model_points="surface" (default "vertices": nothing changes; needs meshes=True or gt_maps=True, ValueError
+    otherwise; both layouts): the n_model_pts model points of every object are drawn uniformly on its mesh's surface
+    instead of being a random subset of its vertices (models.sample_surface with generator row = the object id and
+    `seed`, thinned by FPS from surface_oversample times as many candidates). A model with fewer vertices than
+    n_model_pts then opens, which the default mode refuses, and the points follow the shape, not the tessellation.
+    They are sampled on the device of the first batch, before it is built, and kept as the tree's model_points;
+    `target`, ADD(-S), ICP and the zoom windows read them as they read the vertex subset."""
 
     def __init__(self, mode: str = "test", num_point: int = 1000, add_noise: bool = False, root: Optional[str] = None,
                  noise_trans: float = 0.0, num_kps: int = 8, cls_type: Optional[str] = None, cfg=CONFIG,
@@ -496,9 +507,11 @@ class PoseDataset(torch.utils.data.Dataset):
                  n_model_pts: int = 2600, io_threads: int = 8, gt_maps: bool = False, meshes: bool = False,
                  layout: str = "linemod", split: str = "test", targets: Optional[str] = None, min_visib: float = 0.1,
                  masks: str = "png", detections=None, det_min_score: float = 0.0, det_per_target: str = "best",
-                 resize: Optional[int] = None):
+                 resize: Optional[int] = None, model_points: str = "vertices", surface_oversample: int = 4):
         if layout not in ("linemod", "bop"):
             raise ValueError(f"layout must be 'linemod' or 'bop', got {layout!r}")
+        if model_points not in ("vertices", "surface"):
+            raise ValueError(f"model_points must be 'vertices' or 'surface', got {model_points!r}")
         if masks not in ("png", "render"):
             raise ValueError(f"masks must be 'png' or 'render', got {masks!r}")
         if detections is not None and layout != "bop":
@@ -521,6 +534,17 @@ class PoseDataset(torch.utils.data.Dataset):
         if self.meshes and root is None:
             raise ValueError("gt_maps=True / meshes=True render from the objects' meshes and need a LineMOD tree "
                              "(root=None serves synthetic frames, which have no mesh)")
+        self.model_points_mode, self.surface_oversample = model_points, int(surface_oversample)
+        self.n_model_pts, self.seed = int(n_model_pts), int(seed)
+        if model_points == "surface":
+            if not self.meshes:
+                raise ValueError("model_points='surface' samples the model points on the objects' meshes: it needs "
+                                 "meshes=True (or gt_maps=True)")
+            if self.surface_oversample < 1 or (self.surface_oversample > 1
+                                               and self.n_model_pts * self.surface_oversample > FPS_MAX):
+                raise ValueError(f"n_model_pts * surface_oversample = {self.n_model_pts * self.surface_oversample} "
+                                 f"candidates: surface_oversample must be >= 1 and the product at most the FPS "
+                                 f"kernel's {FPS_MAX}")
         if masks == "render" and not (layout == "bop" and self.meshes):
             raise ValueError("masks='render' renders mask_label from the objects' meshes: it needs layout='bop' and "
                              "meshes=True (or gt_maps=True)")
@@ -539,7 +563,7 @@ class PoseDataset(torch.utils.data.Dataset):
             self.tree = BopTree(root, split=split, targets=targets,
                                 objlist=None if cls_type in (None, "all") else self.objlist, n_model_pts=n_model_pts,
                                 seed=seed, meshes=self.meshes, min_visib=min_visib, detections=detections,
-                                det_min_score=det_min_score, det_per_target=det_per_target)
+                                det_min_score=det_min_score, det_per_target=det_per_target, model_points=model_points)
             self.objlist = list(self.tree.objlist)
             self.obj_info = {o: {"min": [e["min_x"], e["min_y"], e["min_z"]], "size": [e["size_x"], e["size_y"], e["size_z"]],
                                  "diameter": e["diameter"]} for o, e in ((o, self.tree.info[o]) for o in self.objlist)}
@@ -548,7 +572,8 @@ class PoseDataset(torch.utils.data.Dataset):
             self.frames_np = None
             self.boxes = [get_square_bbox(it["bbox"], *self.frame_hw) for it in self.tree.items]
         elif root is not None:
-            self.tree = _LinemodTree(root, mode, self.objlist, n_model_pts, seed, meshes=self.meshes)
+            self.tree = _LinemodTree(root, mode, self.objlist, n_model_pts, seed, meshes=self.meshes,
+                                     model_points=model_points)
             self.frames_np = None
             self.boxes = [get_square_bbox(it["bbox"]) for it in self.tree.items]
         else:
@@ -633,6 +658,22 @@ class PoseDataset(torch.utils.data.Dataset):
         return (int(f["obj_id"][i]), f["target_r"][i].astype(np.float64), f["target_t"][i].astype(np.float64),
                 f["model_points"][i])
 
+    def _sample_model_points(self, device) -> None:
+        """model_points="surface": the n_model_pts points of every object, drawn once on `device` uniformly on its
+        mesh (models.sample_surface: generator row = the object id, the dataset's seed, FPS-thinned from
+        surface_oversample times as many candidates) and kept as the tree's model_points, where the default mode keeps
+        its vertex subset. The draw depends on (seed, object id, mesh) only, so every device gives the same points."""
+        mesh = self._mesh_for(device)
+        s = sample_surface(mesh["verts"], mesh["faces"], torch.tensor([mesh["range"][o] for o in self.objlist],
+                                                                       dtype=torch.int32),
+                           self.n_model_pts, seed=self.seed, row_id=torch.tensor(self.objlist, dtype=torch.int32),
+                           oversample=self.surface_oversample)
+        status, pts = s["status"].cpu().tolist(), s["points"].cpu().numpy()
+        for j, obj in enumerate(self.objlist):
+            if status[j] != 0:
+                raise ValueError(f"model_points='surface': the mesh of object {obj} has no area (only degenerate faces)")
+            self.tree.model_points[obj] = pts[j]
+
     def _mesh_for(self, device) -> Dict[str, object]:
         """The objects' meshes on `device`, concatenated (faces index the concatenated vertices), each
         object's face range (`range`), vertex range (`vrange`) and symmetry range (`srange`) into the
@@ -689,6 +730,8 @@ class PoseDataset(torch.utils.data.Dataset):
         device = torch.device(device)
         idx = list(indices)
         bop = bop or verify
+        if self.model_points_mode == "surface" and not self.tree.model_points:
+            self._sample_model_points(device)
         if zoom and self.resize is None:
             raise ValueError("zoom needs a dataset built with resize: a re-cut window has a side of its own, which "
                              "only the resized input path takes")
